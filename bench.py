@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — headline metric of BASELINE.json on MI355X: Msamples/s (pixels x spp) of the ReSTIR + path-tracing forward render.
 
-    python bench.py [--gpus N --steps K --warmup W] [--res 800 --ssaa 2 --spp 512 --bounces 2]
+    python bench.py [--gpus N --steps K --warmup W] [--res 800 --ssaa 2 --spp 512 --bounces 2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it reports (rooflines, the CPU baseline and the parity of the benched
+frame against it, the other mesh, the configs[2] training step, at N > 1 the second sharding scheme) is measured with --full only.
 
 One "step" = one frame of the hot path: LBVH rebuild (restirbvhWorker.update_mesh, as render_stage1 does every frame) + run_restir_di_with_pt
 (spp loop: light tiles, initial / temporal / spatial reservoir passes, final shading, 2 indirect bounces with the material network, EAW
@@ -10,13 +13,13 @@ denoise, composite) over a synthetic scene of BASELINE config 2's shape, with ev
 visibility, nvdiffrast's job in the reference) is built once outside the timed region.
 
 N > 1: the one frame is shared by the ranks (mirres-restir_nerf_mesh_amd/dist.py) — total work is fixed, i.e. STRONG scaling, as BASELINE's "at
-1/2/4/8 GPU" — and BOTH sharding schemes are timed in the same run: `strips` = the north-star's pixel split (row strips, per-sample reservoir halo exchange,
+1/2/4/8 GPU" — and with --full BOTH sharding schemes are timed in the same run: `strips` = the north-star's pixel split (row strips, per-sample reservoir halo exchange,
 all-gather of radiance rows; bit-identical to one GPU; boundaries balanced from the strips' measured times) and `spp` = sample slices + one sum over the ranks of the
 accumulators the finish reads (dist.sum_over_ranks: all-to-all of slices, rank-ordered local sum, all-gather over RCCL; statistically equivalent frame). `value` is the
 DECLARED scheme's (--value-scheme, default `spp`; `config.value_scheme` repeats it); the other scheme is reported beside it with its ratio.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (traversal kernel, measured live with HIP events on the
-launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample; rank 0, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries `roofline` (traversal kernel, measured live with HIP events on the
+launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample; rank 0, N=1 only), null otherwise.
 """
 import argparse
 import json
@@ -26,6 +29,22 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+OUTPUT_NAMES = ("final_color", "diffuse", "spec", "indirect", "indirect_diff", "indirect_spec")     # run_restir_di_with_pt's six [N, 3] outputs, in order
+DUMP_PIXELS = 1 << 19      # 6 outputs x 2^19 pixels x 3 x 4 B = 36 MiB, under the 64 MB a dump may hold
+
+
+def dump_outputs(outs, d):
+    """--dump-outputs: the six outputs of the last timed step as d/<name>.npy (float32). Frames of more than DUMP_PIXELS pixels: the same fixed sample of pixels
+    (seed 0, ascending index order) from every output, so that two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    n = int(outs[0].shape[0])
+    idx = np.arange(n) if n <= DUMP_PIXELS else np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+    sel = torch.from_numpy(idx).to(outs[0].device)
+    for name, t in zip(OUTPUT_NAMES, outs):
+        np.save(os.path.join(d, name + ".npy"), t.detach().index_select(0, sel).to(torch.float32).cpu().numpy())
 
 
 def parse():
@@ -40,15 +59,19 @@ def parse():
     p.add_argument("--subdiv", type=int, default=7, help="icosphere subdivisions (7 -> 327 680 + 8 192 ground triangles)")
     p.add_argument("--mesh", choices=("icosphere", "clustered"), default="icosphere",
                    help="icosphere: SURVEY 8d's synthetic mesh (uniform tessellation); clustered: the lego-like assembly of scene.make_mesh_clustered (studs, cavities, "
-                        "thin plates, triangle areas spread > 1e5 : 1). The default run reports the other mesh as a sub-record")
-    p.add_argument("--no-extras", action="store_true", help="skip the sub-records of the default single-GPU run (the other mesh, the configs[2] training step)")
+                        "thin plates, triangle areas spread > 1e5 : 1). A --full run reports the other mesh as a sub-record")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: rooflines, the CPU baseline and the parity check against it, the sub-records (other mesh, configs[2] training step) and, "
+                        "at N > 1 with --shard both, the second sharding scheme")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the six outputs of the last timed step as DIR/<name>.npy (float32; a fixed sample of pixels above %d)" % DUMP_PIXELS)
+    p.add_argument("--no-extras", action="store_true", help="--full: skip the sub-records of the single-GPU run (the other mesh, the configs[2] training step)")
     p.add_argument("--shard", choices=("both", "strips", "spp"), default="both",
                    help="N > 1: `spp` = sample slices + one sum of the accumulators over the ranks, `strips` = exact row strips + per-sample halo exchange + all-gather (the north-star's "
-                        "tile split), `both` = time the two schemes one after the other; `value` is --value-scheme's")
+                        "tile split), `both` = time the two schemes one after the other (with --full; a plain run times --value-scheme's only); `value` is --value-scheme's")
     p.add_argument("--value-scheme", choices=("spp", "strips"), default="spp",
-                   help="N > 1 with both schemes timed: which one the line's `value` is — declared here, not chosen after the fact (ADVICE r5); the other is reported beside it")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
+                   help="N > 1: which scheme the line's `value` is (a plain run times this one only) — declared here, not chosen after the fact (ADVICE r5); the other is reported beside it")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
+    p.add_argument("--no-roofline", action="store_true", help="--full: skip the rooflines")
     p.add_argument("--const-material", action="store_true", help="constant material instead of the hash-grid + MLP field")
     return p.parse_args()
 
@@ -406,7 +429,12 @@ def main():
         return d, o
 
     samples = float(N) * args.spp * args.steps
-    schemes = ["spp"] if world == 1 else (["spp", "strips"] if args.shard == "both" else [args.shard])
+    if world == 1:
+        schemes = ["spp"]
+    elif args.shard != "both":
+        schemes = [args.shard]
+    else:
+        schemes = ["spp", "strips"] if args.full else [args.value_scheme]
     results = {}
     for i, sc in enumerate(schemes):
         if i == 0:
@@ -457,12 +485,14 @@ def main():
     dt, out = results[primary]
     value = samples / dt / 1e6
     step_ms = dt / args.steps * 1e3
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
     # ---- rooflines, measured live with HIP events on the launch stream (rank 0): the dominant kernel (shadow-ray traversal), the ordered
     #      closest-hit traversal, and the material MLP's GEMM phase
     roof = None
-    pmc = pmc_snapshot() if rank == 0 else None
-    if rank == 0 and not args.no_roofline:
+    pmc = pmc_snapshot() if rank == 0 and args.full else None
+    if rank == 0 and args.full and not args.no_roofline:
         b, e = MD.spp_slice(args.spp, rank, world)
         prof_spp = max(1, min(8, e - b))
         roof = traversal_roofline(args, ctx, W, mlp, env, g, prof_spp, step_ms, world, pmc)
@@ -483,9 +513,9 @@ def main():
                                issued_frac=round(tf * 6144.0 / 4480.0 / MLP_ROOF["peak"], 5), launch_ms=round(ms_mlp, 4), points=N,
                                mfma_busy=None if cnt.get("stale") else cnt.get("mlp_mfma_busy"))
 
-    # ---- sub-records of the default single-GPU run: the other mesh (same frame, same counters), the configs[2] training step
+    # ---- sub-records of a --full single-GPU run: the other mesh (same frame, same counters), the configs[2] training step
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         other = "clustered" if args.mesh == "icosphere" else "icosphere"
         try:
             t2, W2, mlp2, g2 = scene_for(other)
@@ -511,7 +541,7 @@ def main():
 
     cpu = None
     parity_failed = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, cf = cpu_baseline(S, args)
         # the same small frame (same inputs, seed and sample count) through the HIP path: the PSNR half of BASELINE's metric, against the CPU oracle
         cu = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)

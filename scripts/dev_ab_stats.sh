@@ -8,7 +8,7 @@ for i in 1 2; do
   n=0
   for lib in "" "$@"; do
     if [ -n "$lib" ]; then export MIRRES_LIB=$lib; else unset MIRRES_LIB; fi
-    echo "variant $n $(python bench.py --no-cpu-baseline --no-roofline --steps 3 2>&1 | grep -o '"value": [0-9.]*')"; n=$((n+1))
+    echo "variant $n $(python bench.py --full --no-cpu-baseline --no-roofline --steps 3 2>&1 | grep -o '"value": [0-9.]*')"; n=$((n+1))
   done
 done
 n=0
@@ -16,7 +16,7 @@ for lib in "" "$@"; do
   if [ -n "$lib" ]; then export MIRRES_LIB=$lib; else unset MIRRES_LIB; fi
   export MIRRES_STREAMS=1
   D=/tmp/ab_$n; rm -rf $D; mkdir -p $D
-  (cd $D && timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o t -- python3 $R/bench.py --no-cpu-baseline --no-roofline --steps 1 --warmup 1 --spp 32 > $D/log 2>&1) || tail -5 $D/log
+  (cd $D && timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o t -- python3 $R/bench.py --full --no-cpu-baseline --no-roofline --steps 1 --warmup 1 --spp 32 > $D/log 2>&1) || tail -5 $D/log
   unset MIRRES_STREAMS
   echo "== variant $n (serialised, 32 spp)"; python3 - "$D/t_kernel_stats.csv" "$PAT" <<'PY'
 import csv, sys, re

@@ -128,12 +128,13 @@ PY
 cp $O/pmc_any4q_summary.json $O/pmc_chain_summary.json $O/pmc_traffic.json $O/pmc_train_summary.json profiles/      # this box's copy: the bench lines below quote them as fresh
 
 # ---- 3. bench lines (default, driver-style, lego-like as the headline), kernel traces of both meshes, training step, MLP GEMM phase
-timeout -k 5 600 python3 bench.py > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
-timeout -k 5 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_driver_style.json 2> $O/${R}_bench_driver_style.err
-timeout -k 5 600 python3 bench.py --mesh clustered --no-extras > $O/${R}_bench_clustered.json 2> $O/${R}_bench_clustered.err
+timeout -k 5 600 python3 bench.py --full > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
+timeout -k 5 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_driver_style.json 2> $O/${R}_bench_driver_style.err
+timeout -k 5 600 python3 bench.py --full --mesh clustered --no-extras > $O/${R}_bench_clustered.json 2> $O/${R}_bench_clustered.err
 mkdir -p gpurun_out/pf
+PF=${O%/*}/pf      # (the directory made above)
 for mesh in icosphere clustered; do
-  rm -rf gpurun_out/pf/kt; $RP --kernel-trace --stats --output-format csv -d gpurun_out/pf/kt -o kt -- python3 bench.py --mesh $mesh --steps 1 --warmup 1 --no-cpu-baseline --no-extras > gpurun_out/pf/log_$mesh 2>&1
+  rm -rf $PF/kt; $RP --kernel-trace --stats --output-format csv -d $PF/kt -o kt -- python3 bench.py --full --mesh $mesh --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $PF/log_$mesh 2>&1
   grep '^{' gpurun_out/pf/log_$mesh | tail -1 > $O/${R}_bench_under_rocprof_$mesh.json
   find gpurun_out/pf/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${R}_kernel_stats_$mesh.csv
 done
