@@ -210,6 +210,29 @@ int mirres_interpolate_bwd(const float* attr, int C, const float* rast, const in
  * regularisers): tex f32[H,W,C], uv f32[n,2] in [0,1] (texel centres at (i + 0.5) / W) -> out f32[n,C]; the backward ACCUMULATES into g_tex. */
 int mirres_texture2d(const float* tex, int H, int W, int C, const float* uv, int n, float* out, void* stream);
 int mirres_texture2d_bwd(int H, int W, int C, const float* uv, int n, const float* g_out, float* g_tex, void* stream);
+/* Texture bake of the stage-1 mesh export (nerf/renderer.py:319-462 `_export_obj`, called per cascade by :464-476; Trainer.export_stage1,
+ * nerf/utils.py:1271-1281), csrc/bake.hip.  H x W is the SSAA bake grid (h0 * ssaa, w0 * ssaa); texel (row r, col c) has its centre at UV
+ * ((c + 0.5) / W, (r + 0.5) / H), the row growing with v (dr.rasterize on uv * 2 - 1 at (h, w), :357).  All four only enqueue work.
+ *
+ * mirres_uv_rasterize (:352-357): uv f32[n_uv,2], ft i32[T,3] (T < 2^24: the id is stored in fp32) -> rast f32[H*W,4] = (b0, b1, 0, triangle_id + 1),
+ * zeros where nothing covers the centre — the record mirres_interpolate reads (:358-359).  Coverage is exact integer arithmetic: vertices snapped to
+ * 1/256 texel (floor(u W 256 + 0.5)), int64 edge functions at the texel centres, a centre on an edge taken by one side (top-left rule), both windings,
+ * zero-area / non-finite / out-of-range triangles cover nothing, the lowest triangle index wins where triangles overlap.  scratch = a device buffer
+ * of mirres_uv_rasterize_scratch(T) bytes (-1 when T is out of range).                                                                        */
+long long mirres_uv_rasterize_scratch(int T);
+int mirres_uv_rasterize(const float* uv, int n_uv, const int32_t* ft, int T, int W, int H, float* rast, void* scratch, long long scratch_bytes, void* stream);
+/* (:390-398) feats6 f32[n,6] of the covered texels index i32[n] (linear texel index) -> out0 / out1 u8[H*W*3] (channels 0-2 / 3-5): clip to
+ * [0, 1], linear_to_srgb_np (nerf/utils.py:60, pow of the device library), x 255, truncated; 0 at every texel not listed.                     */
+int mirres_bake_quantise(const float* feats6, const int32_t* index, int n, int W, int H, uint8_t* out0, uint8_t* out1, void* stream);
+/* (:400-414) mask u8[H*W] (nonzero = covered), in0 / in1 u8[H*W*3] -> out0 / out1: covered texels keep their bytes; a texel within L1 distance
+ * `radius` (<= 32) of the mask (binary_dilation, `radius` iterations, minus the mask) copies the bytes of its Euclidean-nearest covered texel —
+ * what the kd-tree over the 3-texel band returns (that texel lies on the band); ties go to the smallest (d^2, row, col); everything else is 0.
+ * scratch_dy = device i8[H*W].                                                                                                           */
+int mirres_texture_inpaint(int W, int H, int radius, const uint8_t* mask, const uint8_t* in0, const uint8_t* in1, int8_t* scratch_dy,
+                           uint8_t* out0, uint8_t* out1, void* stream);
+/* (:420-422) cv2.resize(INTER_LINEAR) of in u8[H*W*3] to (W / ssaa) x (H / ssaa) (both divisible): odd ssaa the centre texel, even ssaa the mean of
+ * the 2 x 2 centre texels rounded half up.                                                                                                */
+int mirres_texture_downsample(int W, int H, int ssaa, const uint8_t* in, uint8_t* out, void* stream);
 /* dr.antialias (nerf/renderer.py:1184-1206; nvdiffrast is un-vendored: the published algorithm, csrc/antialias.hip): color f32[H*W,C], rast f32[H*W,4]
  * (mirres_raster_raycast's record: .z orders the two triangles of a pixel pair by distance, .w = triangle id + 1), pos_clip f32[V,4] clip-space
  * vertex positions (pixel (i, j)'s centre is NDC ((2i + 1) / W - 1, (2j + 1) / H - 1)), tri i32[T,3], opp i32[T,3] the vertex across each edge

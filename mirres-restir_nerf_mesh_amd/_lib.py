@@ -105,6 +105,11 @@ SIGNATURES = {
     "mirres_interpolate_bwd": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "mirres_texture2d": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "mirres_texture2d_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "mirres_uv_rasterize_scratch": (C.c_longlong, [C.c_int]),
+    "mirres_uv_rasterize": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong, vp]),
+    "mirres_bake_quantise": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "mirres_texture_inpaint": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mirres_texture_downsample": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "mirres_antialias": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mirres_antialias_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]),
     "mirres_dump_render": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),

@@ -4,6 +4,10 @@ PSNR / SSIM against the dataset images when they can be read.
 
     python scripts/evaluate.py --workspace <ws> --ckpt <ws>/checkpoints/ngp_stage1_ep0100.pth --transforms <data>/transforms_test.json \
         [--spp 512 --ssaa 2 --downscale 1 --bound 2 --roughness_min 0.08 --me_max 0 --out <ws>/results_brdf --limit 0 --synthetic]
+        [--export_mesh --texture_size 4096]
+
+`--export_mesh` (off by default) writes the stage-1 textured mesh after the views, as the reference's `--test` does unless `--test_no_mesh`
+(main.py:256-258): <ws>/mesh_stage1/mesh_{cas}.obj / .mtl / feat0_{cas}.png / feat1_{cas}.png (mirres_restir_nerf_mesh_amd/export.py, with --ssaa).
 
 The material-field constants are the reference's CLI ones and MUST equal the training run's (nerf/network.py:119-125): `--bound` (hash-grid AABB
 = +-bound, main.py:39 default 2; also the mesh cascade count 1 + ceil(log2(bound)), nerf/renderer.py:97, unless `--cascade` overrides it),
@@ -77,6 +81,8 @@ def main():
     p.add_argument("--shard", choices=("views", "strips", "spp"), default="views", help="how N > 1 ranks (torch.distributed.run) divide the work")
     p.add_argument("--lpips_vgg", default=None, help="torchvision vgg16 state dict (or a state dict of lpips.LPIPS): adds the reference's LPIPS (vgg) meter; no weights ship with the image")
     p.add_argument("--lpips_lin", default=None, help="the lpips package's weights/v0.1/vgg.pth (the five linear heads)")
+    p.add_argument("--export_mesh", action="store_true", help="after the views, export the stage-1 textured mesh to <workspace>/mesh_stage1 (main.py:256-258; off by default)")
+    p.add_argument("--texture_size", type=int, default=4096, help="main.py --texture_size: texture side of the first cascade of --export_mesh (baked at --ssaa)")
     a = p.parse_args()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
@@ -98,7 +104,7 @@ def main():
     ck = CK.read_checkpoint(a.ckpt)
     cfg = CK.resolve_material_config(ck.get("material_config"), bound=a.bound, roughness_min=a.roughness_min, me_max=a.me_max, kd_min=a.kd_min, kd_max=a.kd_max)
     cascade = a.cascade if a.cascade is not None else CK.cascade_of_bound(cfg["bound"])
-    v, t, v_cumsum, _ = CK.load_stage0_mesh(a.workspace, cascade)
+    v, t, v_cumsum, f_cumsum = CK.load_stage0_mesh(a.workspace, cascade)
     aabb, mn, mx = CK.material_field_args(cfg)     # nerf/network.py:119-125
     mlp = MLPTexture3D(aabb, channels=6, min_max=(mn.cuda(), mx.cuda()))
     voff, light = CK.apply_checkpoint(ck, mlp, n_vertices=v.shape[0])
@@ -167,6 +173,9 @@ def main():
             n, Ww, Hh, a.ssaa, a.spp, world, (" [%s]" % a.shard) if world > 1 else "", 1e3 * t_render / max(n, 1), n * Ww * Hh * a.ssaa ** 2 * a.spp / max(t_render, 1e-9) / 1e6))
         if pm.N:
             print(pm.report(), sm.report(), lm.report() if lm and lm.N else "")
+        if a.export_mesh:          # trainer.export_stage1(resolution=opt.texture_size) after the test views (main.py:256-258)
+            from mirres_restir_nerf_mesh_amd import export as EX
+            EX.export_stage1(os.path.join(a.workspace, "mesh_stage1"), verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa)
     if world > 1:
         dist.destroy_process_group()
 
