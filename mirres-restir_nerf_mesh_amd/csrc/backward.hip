@@ -184,9 +184,10 @@ __global__ void __launch_bounds__(MR_BLOCK) k_final_shading_bwd(int N, const flo
 // 21 G scattered fp32 atomic requests per second whatever the scope (every device-scope atomic leaves the XCD's L2: TCC_EA0_ATOMIC == TCC_ATOMIC), but the lanes of ONE
 // instruction that fall into the same 32-byte sector travel as one request (G consecutive lanes on G consecutive dwords: G x 21 G lane-atomics/s). A texel's three
 // channels are 12 consecutive bytes. So no contribution goes to global memory from the sample loop any more: what the hash table cannot hold (both probes taken by other
-// texels: a flat map spreads a workgroup's 4096 texel updates over as many texels) is appended to an LDS list, and table and list are flushed at the end by FOUR
-// lanes per entry (three channels + an idle lane) — a third of the requests. A full list (cannot happen: 2048 + 2048 entries per workgroup of 4096 updates) still falls
-// back to direct atomics.
+// texels: a flat map spreads a workgroup's texel updates over nearly as many texels) is appended to an LDS list, and table and list are flushed at the end by FOUR
+// lanes per entry (three channels + an idle lane) — a third of the requests. A workgroup (32 pixels) makes up to 32 x spp x 4 footprint updates (4096 at 32 spp,
+// 8192 at 64 spp), and every update whose two probes are taken by other texels takes a list entry. So the list can fill; the updates that find it full go to
+// global memory with direct atomics (tests/test_gpu_render_bwd.py reaches that path).
 struct EnvScatter { int* keys; float* vals; int* lkeys; float* lvals; int* lcount; };
 MR_DEV void env_grad_add(const EnvScatter& S, float* g_env, int texel, v3 g) {
     uint32_t h = ((uint32_t)texel * 2654435761u) >> (32 - 11);

@@ -112,3 +112,22 @@ def eaw(fx, fy, step, c_phi, n_phi, p_phi, occ, color, normal, pos):
         total = total + ct * w; cum = cum + w
     out = total / cum
     return torch.where((occ.view(fy, fx, 1) < 0.1), C, out).reshape(-1, 3)
+
+
+def direct_sums(tape, env, occ, normal, ray_dir_raw, kd, rm):
+    """The three direct sums that mirres_render_bwd differentiates (color, diffuse light, specular light; [N,3] each), restated from the forward's tape
+    f32[S*N, 8] — per sample and pixel {light_data.xyz, inv_pdf | M bits, weight, vis, 0} — so that every discrete choice of the forward (which light sample,
+    visible or not) is the one it recorded:  sum over s of final_shading(eval_final(...)).  env is [H,W,3] in the caller's layout (flipped row for row here
+    like k_flip_env), ray_dir_raw is normalised like k_prep (eps 1e-6), occ is the forward's thresholded map.  Differentiable in env, normal, kd and rm."""
+    H, W = env.shape[0], env.shape[1]
+    N = normal.shape[0]
+    S = tape.shape[0] // N
+    assert tape.shape == (S * N, 8)
+    tex = env.flip(0).reshape(H * W, 3)
+    rd = ray_dir_raw / torch.clamp(torch.sqrt((ray_dir_raw * ray_dir_raw).sum(1, keepdim=True)), min=1e-6)
+    rep = lambda t: t.repeat(S, 1)                        # row s * N + p of the tape belongs to pixel p
+    light_data, weight, vis = tape[:, 0:3], tape[:, 5:6], tape[:, 6:7]
+    Li = eval_final(tex, W, H, light_data, weight, vis)
+    fdist = torch.where((light_data[:, 0:1] > 0.1) & (vis > 0), torch.full_like(vis, 1e6), torch.zeros_like(vis))
+    c, d, s = final_shading(rep(occ.reshape(N, 1)), rep(normal), rep(rd), rep(kd), rep(rm), oct_decode(light_data[:, 1:3]), fdist, Li)
+    return tuple(x.reshape(S, N, 3).sum(0) for x in (c, d, s))

@@ -50,6 +50,18 @@ class SmallFrame:
                                   self.tri, self.tex, self.Wc, self.Hc, self.tables)
 
 
+def elementwise(got, want, what, rtol=1e-3, atol_scale=1e-4, min_frac=1.0):
+    """Element-by-element gradient check against a float64 reference: |got - want| <= rtol |want| + atol_scale max|want| for at least min_frac of the elements."""
+    got = got.detach().double().cpu().numpy(); want = want.detach().double().cpu().numpy()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    scale = float(np.abs(want).max())
+    assert scale > 0, what + ": reference gradient is identically zero"
+    err = np.abs(got - want)
+    ok = err <= rtol * np.abs(want) + atol_scale * scale
+    assert ok.mean() >= min_frac, "%s: %d of %d gradient elements differ (max err %.3e at reference %.3e, scale %.3e)" % (
+        what, int((~ok).sum()), ok.size, float(err.max()), float(np.abs(want).ravel()[np.argmax(err)]), scale)
+
+
 def match_fraction(a, b, rtol=1e-4, atol=1e-6):
     """Fraction of rows whose every component agrees within tolerance."""
     a = np.asarray(a, np.float64).reshape(len(a), -1); b = np.asarray(b, np.float64).reshape(len(b), -1)
@@ -70,12 +82,14 @@ def psnr(a, b, peak=1.0):
     return 99.0 if mse == 0 else 10.0 * np.log10(peak * peak / mse)
 
 
-def torch_material_field(O, params_f32, w0, w1, w2, aabb_min, aabb_max, mn, mx, pos, dtype=None, table=None):
+def torch_material_field(O, params_f32, w0, w1, w2, aabb_min, aabb_max, mn, mx, pos, dtype=None, table=None, enc=None):
     """Plain-torch reference of MLPTexture3D.sample (render_helper.py:93-104) with autograd: position normalisation + clamp, the hash-grid encoding
     (tcnn's published algorithm: `fmaf(scale, x, 0.5)`, floor, 8-corner trilinear weights, dense / coherent-prime-hash index; the table holds the
     fp16-rounded parameters but the interpolation is carried out in `dtype`, not fp16), the bias-free 32-32-32-6 ReLU MLP, sigmoid and range.
     `pos` may require grad; everything stays on pos.device.  The level layout comes from the oracle (`hashgrid_layout`).  `table`: the (fp16-valued) parameter
-    table as a flat tensor that may require grad (then params_f32 is not read) — for the table's own gradient."""
+    table as a flat tensor that may require grad (then params_f32 is not read) — for the table's own gradient.  `enc`: the encoding [n,32] the kernel computed
+    (O.hashgrid_encode, its fp16 interpolation bit for bit) as the forward value of the encoding, with the derivative of the `dtype` interpolation — so every
+    ReLU of the MLP takes the kernel's decision."""
     import torch
     dtype = dtype or torch.float64
     dev = pos.device
@@ -104,6 +118,8 @@ def torch_material_field(O, params_f32, w0, w1, w2, aabb_min, aabb_max, mn, mx, 
             acc = acc + wt[:, None] * tab[index]
         feats.append(acc)
     a = torch.cat(feats, dim=1)
+    if enc is not None:
+        a = a + (enc.to(dev, dtype) - a).detach()
     W = [torch.as_tensor(t).to(dev, dtype) for t in (w0, w1, w2)]
     h = torch.relu(a @ W[0].T); h = torch.relu(h @ W[1].T); z = h @ W[2].T
     mn_t = torch.tensor(np.asarray(mn, np.float64), device=dev, dtype=dtype); mx_t = torch.tensor(np.asarray(mx, np.float64), device=dev, dtype=dtype)
