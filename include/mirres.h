@@ -143,6 +143,7 @@ typedef struct mirres_path {
     const float *occ, *pos, *normal, *ray_dir, *kd, *rough_metal; /* vertex inputs                              */
     float* prd;                                                   /* f32[N,5] throughput rgb, specularBounce, stop */
     float *new_pos, *new_ray_d, *new_occ, *new_normal;            /* next-vertex outputs                        */
+    int32_t* new_prim;   /* i32[N] or NULL (no write): the mesh triangle of the next vertex, -1 where new_occ = 0 (what a textured material looks up) */
 } mirres_path_t;
 /* process_new_dir_for_pt (Resampling.py:216-232; FinalShading.slang:113-265)                                  */
 int mirres_pt_new_dir(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_path_t* p, uint32_t frameIndex, uint32_t bounce_count, void* stream);
@@ -275,6 +276,31 @@ int mirres_matnet_scatter(const mirres_matnet_t* m, const float* occ, const floa
 int mirres_matnet_bwd(const mirres_matnet_t* m, const float* pos, int n, const float* grad_out, float* g_params_f32, float* g_w0,
                       float* g_w1, float* g_w2, float* g_pos, void* stream);
 
+/* ------------------------------------------------------------------ textured material (the exported stage-1 asset, nerf/renderer.py:390-398; csrc/texmat.hip)
+ * The render mesh verts f32[V,3] / tris i32[T,3] (what the BVH was built from), per-corner UVs ft i32[T,3] into vt f32[Nt,2] in the reference's convention
+ * (v = 1 - v' of the OBJ).  Cascade c owns the triangles [tri_end[c-1], tri_end[c]) (tri_end[-1] = 0, tri_end[n_cas-1] = T, n_cas <= 8) and the W[c] x H[c]
+ * texel plane texels[c]: 8 bytes per texel, row-major, row 0 = smallest v, bytes (feat0 R, G, B, feat1 G, feat1 B, 0, 0, 0) = (kd.rgb, roughness, metallic)
+ * as 8-bit sRGB.  decode f32[256] maps every byte to linear (q -> srgb_to_linear(q / 255)); decoded roughness is clamped to [rough_min, 1].
+ * Lookup of a point p on triangle prim, every operation one correctly rounded fp32 operation in this order, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z:
+ *   e1 = v1 - v0, e2 = v2 - v0, d = p - v0;  d00 = dot(e1,e1), d01 = dot(e1,e2), d11 = dot(e2,e2), d20 = dot(d,e1), d21 = dot(d,e2);
+ *   den = d00 d11 - d01 d01;  b1 = (d11 d20 - d01 d21) / den;  b2 = (d00 d21 - d01 d20) / den;  b0 = (1 - b1) - b2;
+ *   uv = (b0 uv0 + b1 uv1) + b2 uv2;  x = fmax(fmin(u W - 0.5, W), -1), y = fmax(fmin(v H - 0.5, H), -1) (a NaN becomes the bound);
+ *   i = floor(x), fx = x - i; taps at columns clamp(i, 0, W-1) and clamp(i+1, 0, W-1), rows likewise (clamp to the edge);
+ *   per channel, decoded taps t00, t10 (row j), t01, t11 (row j+1): a = t00 + fx (t10 - t00), b = t01 + fx (t11 - t01), out = a + fy (b - a).
+ * mirres_texmat_lookup: occ f32[n] (NULL = all 1), prim i32[n], pos f32[n,3] -> kd f32[n,3], rough_metal f32[n,2] with the row rules of
+ * mirres_matnet_scatter: only rows with occ >= 0.5 are written (kd scaled by h_scale3 when use_scale), and with use_scale the kd of EVERY row is
+ * then clamped to [0, 1]; an occupied row whose prim lies outside [0, T) is the caller's error and is left unwritten.                        */
+typedef struct mirres_texmat {
+    const float* verts; const int32_t* tris;
+    const float* vt; const int32_t* ft;
+    int n_cas; int tri_end[8];
+    int W[8], H[8]; const void* texels[8];
+    const float* decode;
+    float rough_min;
+} mirres_texmat_t;
+int mirres_texmat_lookup(const mirres_texmat_t* t, const float* occ, const int32_t* prim, const float* pos, int n, float* kd, float* rough_metal,
+                         int use_scale, const float* h_scale3, void* stream);
+
 /* ------------------------------------------------------------------ whole frame: run_restir_di_with_pt (renderer_restir.py:473-550) */
 typedef struct mirres_render_args {
     int spp; uint32_t random_offset; /* np.random.randint(2**20) in the reference (renderer_restir.py:245)     */
@@ -317,6 +343,9 @@ typedef struct mirres_render_args {
     void* halo_comm;
     int halo_n, halo_peer[2], halo_send0[2], halo_send1[2], halo_recv0[2], halo_recv1[2];
     int halo_time_stride;
+    /* tex != NULL: the material at every indirect hit is looked up in this textured mesh (mirres_texmat_lookup's rule, at the triangle the continuation
+     * ray hit); the BVH must have been built from tex->verts / tex->tris.  NULL: mat / const_kd.  Setting both tex and mat is MIRRES_E_ARG.       */
+    const mirres_texmat_t* tex;
 } mirres_render_args_t;
 int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args_t* a, void* stream);
 /* The library's own RCCL communicator for the native halo exchange (no reference counterpart: /root/reference is single-GPU). librccl is dlopen-ed —

@@ -37,7 +37,12 @@ class Res(C.Structure):
 
 
 class Path(C.Structure):
-    _fields_ = [(n, vp) for n in ("occ", "pos", "normal", "ray_dir", "kd", "rough_metal", "prd", "new_pos", "new_ray_d", "new_occ", "new_normal")]
+    _fields_ = [(n, vp) for n in ("occ", "pos", "normal", "ray_dir", "kd", "rough_metal", "prd", "new_pos", "new_ray_d", "new_occ", "new_normal", "new_prim")]
+
+
+class TexMat(C.Structure):
+    _fields_ = [("verts", vp), ("tris", vp), ("vt", vp), ("ft", vp), ("n_cas", C.c_int), ("tri_end", C.c_int * 8),
+                ("W", C.c_int * 8), ("H", C.c_int * 8), ("texels", vp * 8), ("decode", vp), ("rough_min", C.c_float)]
 
 
 class MatNet(C.Structure):
@@ -54,7 +59,7 @@ class RenderArgs(C.Structure):
                 ("outs", vp * 6), ("tape", vp), ("gb_depth", vp), ("spp_begin", C.c_int), ("spp_end", C.c_int),
                 ("strip_full_fy", C.c_int), ("strip_y_off", C.c_int), ("own_y0", C.c_int), ("own_y1", C.c_int), ("halo", vp), ("halo_user", vp), ("strip_overlap", C.c_int),
                 ("halo_comm", vp), ("halo_n", C.c_int), ("halo_peer", C.c_int * 2), ("halo_send0", C.c_int * 2), ("halo_send1", C.c_int * 2), ("halo_recv0", C.c_int * 2),
-                ("halo_recv1", C.c_int * 2), ("halo_time_stride", C.c_int)]
+                ("halo_recv1", C.c_int * 2), ("halo_time_stride", C.c_int), ("tex", C.POINTER(TexMat))]
 
 
 HALO_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int, vp)   # int halo(void* user, float* records, int sample, void* stream)
@@ -123,6 +128,7 @@ SIGNATURES = {
     "mirres_matnet_mlp": (C.c_int, [PMAT, vp, C.c_int, vp, vp]),
     "mirres_matnet_scatter": (C.c_int, [PMAT, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float), vp]),
     "mirres_matnet_bwd": (C.c_int, [PMAT, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mirres_texmat_lookup": (C.c_int, [C.POINTER(TexMat), vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float), vp]),
     "mirres_ctx_reserve": (C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1129,13 +1129,13 @@ int trace_any_front_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t
     return 0;
 }
 int trace_closest_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
-                        unsigned long long* stats, hipStream_t s, int lane) {
-    if (closest_mode() == 4) return closest_fast<false>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, nullptr, stats, s, lane);
+                        unsigned long long* stats, hipStream_t s, int lane, int32_t* prim) {
+    if (closest_mode() == 4) return closest_fast<false>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, prim, stats, s, lane);
     static const int set_of_lane[5] = {1, 8, 10, 10, 16};
     uint32_t* const heads = bvh->work + set_of_lane[lane] * MR_WSET;
     MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
     k_trace_persist<false><<<persist_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, heads, nullptr, out,
-                                                                             nullptr, nullptr, nullptr, nullptr, stats);
+                                                                             nullptr, nullptr, nullptr, prim, stats);
     MR_LAUNCH_CHECK("trace_closest_queue");
     return 0;
 }
@@ -1152,10 +1152,10 @@ int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32
     return 0;
 }
 int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
-                                unsigned long long* stats, hipStream_t s) {
-    if (closest_mode() == 4) return closest_fast<true>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, nullptr, stats, s);
+                                unsigned long long* stats, hipStream_t s, int32_t* prim) {
+    if (closest_mode() == 4) return closest_fast<true>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, prim, stats, s);
     k_trace_closest<true><<<trace_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, out, nullptr, nullptr,
-                                                                           nullptr, nullptr, nullptr, nullptr, stats);
+                                                                           nullptr, nullptr, prim, nullptr, stats);
     MR_LAUNCH_CHECK("trace_closest_queue_counted");
     return 0;
 }

@@ -156,6 +156,8 @@ struct mirres_ctx {
     // band pipeline of the per-sample chain (render.hip): up to two more chain streams with their own queue sets, one event per unit of a batch
     ChainSet chain_sets[3]; void* chain_mem[2] = {nullptr, nullptr}; hipStream_t chain_streams[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_band;
+    // per-ray triangle ids of the continuation rays (PtQueues::cl_prim): allocated on the first textured frame or mirres_path_t::new_prim request, never for a material field
+    int32_t* ray_prim = nullptr; size_t ray_prim_cap = 0;
 };
 
 namespace mr {
@@ -168,6 +170,14 @@ inline int bvh_sticky_error(const mirres_bvh* bvh, const char* who) {
     if (bvh && bvh->err && *(volatile uint32_t*)bvh->err) { set_error("%s: an earlier traversal launch overflowed its private stack (flag %u): results since then are not trustworthy", who, *(volatile uint32_t*)bvh->err); return MIRRES_E_STATE; }
     return MIRRES_OK;
 }
+// the context's per-ray triangle-id buffer (mirres_ctx::ray_prim), grown to n entries on first use
+inline int ensure_ray_prim(mirres_ctx* ctx, size_t n) {
+    if (ctx->ray_prim_cap >= n) return MIRRES_OK;
+    if (ctx->ray_prim) { MR_HIP(hipDeviceSynchronize()); MR_HIP(hipFree(ctx->ray_prim)); ctx->ray_prim = nullptr; ctx->ray_prim_cap = 0; }
+    MR_HIP(hipMalloc(&ctx->ray_prim, sizeof(int32_t) * n));
+    ctx->ray_prim_cap = n;
+    return MIRRES_OK;
+}
 
 // queue tracing (bvh_trace.hip). count is read on the device; capacity bounds the grid-stride loop.
 int trace_any_items_queue(const mirres_bvh* bvh, const uint2* items, const RaySrc& src, const uint32_t* d_count, size_t capacity, int32_t* hit,
@@ -176,7 +186,7 @@ int trace_any_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_co
                     unsigned long long* stats, hipStream_t s, int lane = 0, int timed = 0, bool heads_clean = false);
 int trace_any_front_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, int32_t* hit, hipStream_t s);
 int trace_closest_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
-                        unsigned long long* stats, hipStream_t s, int lane = 0);
+                        unsigned long long* stats, hipStream_t s, int lane = 0, int32_t* prim = nullptr);
 int trace_any(mirres_ctx* ctx, mirres_bvh* bvh, size_t cap, hipStream_t s);       // ctx->any_rays -> ctx->any_hit
 int trace_closest(mirres_ctx* ctx, mirres_bvh* bvh, size_t cap, hipStream_t s);   // ctx->cl_rays  -> ctx->cl_hit
 // queues and per-slot scratch of the path-tracing stages: the context's own (one sample per pixel — the stepwise ABI) or a K-sample batch
@@ -195,6 +205,9 @@ struct PtQueues {
     // Of a K-sample batch's 82 M slots a few million survive the first indirect vertex; the bounce kernels run over the list instead of over all slots.
     int32_t* live[2]; int live_cur;
     GridSort gs;
+    // Textured frames only (NULL otherwise: the trace runs exactly as for a material field): the closest-hit trace of the continuation rays also writes the hit
+    // triangle of every ray, cl_prim[ray]; the vertex of slot v then lies on triangle cl_prim[slot_c[v]] (texmat.hip).
+    int32_t* cl_prim = nullptr;
 };
 int launch_initial_batch(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res, float* tile_data,
                          float* tile_pdf, float* tile_aux, uint32_t frame0, int K, const PtQueues* q, hipStream_t s);
@@ -204,6 +217,10 @@ int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, co
                    const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s, const mirres_res_t* next_res, uint32_t next_frame, const SpatialBand* band = nullptr);
 int comm_exchange_halos(void* comm, float* rec, int fx, int n, const int* peer, const int* s0, const int* s1, const int* r0, const int* r1, hipStream_t s);   // comm.hip
 int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane = 0);
-int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane = 0);
+int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane = 0, int32_t* prim = nullptr);
+// texmat.hip
+int launch_texmat_live(const mirres_texmat_t* t, const float* occ, const float* pos, int nv, float* kd, float* rm, int use_scale, const float* scale3, const int32_t* live,
+                       const uint32_t* live_count, const int32_t* slot_c, const int32_t* ray_prim, hipStream_t s);
+int launch_slot_prim(int n, const int32_t* slot_c, const float* new_occ, const int32_t* ray_prim, int32_t* out, hipStream_t s);
 inline int grid_for(size_t n, int block) { size_t g = (n + block - 1) / block; return (int)(g < 1 ? 1 : g); }
 }  // namespace mr

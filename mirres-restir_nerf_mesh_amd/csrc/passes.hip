@@ -818,7 +818,7 @@ static ResD resd(const mirres_res_t* r) {
 static EnvD envh(const mirres_env_t* e) { EnvD E; E.tex = e->tex; E.W = e->Wc; E.H = e->Hc; E.pdf = e->pdf; E.cdf = e->cdf; E.mpdf = e->mpdf; E.mcdf = e->mcdf; return E; }
 
 int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
-                                unsigned long long* stats, hipStream_t s);
+                                unsigned long long* stats, hipStream_t s, int32_t* prim = nullptr);
 
 static int ev_pair(std::vector<hipEvent_t>& pool, size_t& used, hipEvent_t** a, hipEvent_t** b) {
     if (used + 2 > pool.size()) {
@@ -851,11 +851,11 @@ static bool ray_items_allowed(const mirres_ctx* ctx) {
     static const bool force_rays = [] { const char* e = getenv("MIRRES_SPATIAL_RAYS"); return e && e[0] == '1'; }();   // A/B: 32-byte rays everywhere, as before
     return ctx->grec && !(ctx->instrument & 1) && !force_rays;
 }
-int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane) {
+int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane, int32_t* prim) {
     hipEvent_t *e0 = nullptr, *e1 = nullptr;
     if (ctx->instrument & 2) { int rc = ev_pair(ctx->ev_cl, ctx->ev_cl_used, &e0, &e1); if (rc) return rc; MR_HIP(hipEventRecord(*e0, s)); }
-    int rc = (ctx->instrument & 1) ? trace_closest_queue_counted(bvh, rays, count, cap, out, ctx->stats, s)
-                                   : trace_closest_queue(bvh, rays, count, cap, out, ctx->stats, s, lane);
+    int rc = (ctx->instrument & 1) ? trace_closest_queue_counted(bvh, rays, count, cap, out, ctx->stats, s, prim)
+                                   : trace_closest_queue(bvh, rays, count, cap, out, ctx->stats, s, lane, prim);
     if (e1) MR_HIP(hipEventRecord(*e1, s));
     return rc;
 }
@@ -993,7 +993,8 @@ int mirres_ctx_create(mirres_ctx_t** out, int fx, int fy, const mirres_config_t*
 
 void mirres_ctx_destroy(mirres_ctx_t* c) {
     if (!c) return;
-    void* ptrs[] = {c->any_rays, c->any_hit, c->cl_rays, c->cl_hit, c->counters, c->stats, c->slot_a, c->mask_a, c->slot_c, c->pend, c->noff, c->pool, c->tile_aux, c->ptb};
+    void* ptrs[] = {c->any_rays, c->any_hit, c->cl_rays, c->cl_hit, c->counters, c->stats, c->slot_a, c->mask_a, c->slot_c, c->pend, c->noff, c->pool, c->tile_aux, c->ptb,
+                    c->ray_prim};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev_any) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_cl) (void)hipEventDestroy(e);

@@ -418,6 +418,7 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
         set_error("mirres_render: bad argument"); return MIRRES_E_ARG;
     }
     for (int k = 0; k < 6; k++) if (!a->outs[k]) { set_error("mirres_render: outs[%d] is null", k); return MIRRES_E_ARG; }
+    if (a->tex && a->mat) { set_error("mirres_render: both a textured mesh (tex) and a material field (mat) given"); return MIRRES_E_ARG; }
     if (bvh->T < 2) { set_error("mirres_render: BVH not built"); return MIRRES_E_STATE; }
     if (int e = bvh_sticky_error(bvh, "mirres_render")) return e;
     hipStream_t s = (hipStream_t)stream;
@@ -481,6 +482,7 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
       const int mb = e ? (atoi(e) > 0 ? atoi(e) : 1) : ((n >= 16 && n <= Kuse && ((size_t)N <= (size_t)1024 * 1024 || n > 32)) ? 2 : 1);
       if (n < mb * Kuse) Kuse = (n + mb - 1) / mb; if (Kuse < 1) Kuse = 1; if (Kuse > Kmax) Kuse = Kmax; if (Kuse > n) Kuse = n; }
     PtBatch PB; rc = carve_batch(ctx, N, Kuse, max_bounce, TS, PB); if (rc) return rc;
+    if (a->tex) { rc = ensure_ray_prim(ctx, (size_t)PB.K * (size_t)N); if (rc) return rc; }   // textured frames only: the batch pool of a material-field frame does not grow
     // ---- schedule. Per batch b of K samples:
     //   I(b)  initial resampling of the K samples (light tiles, candidates, shadow rays)              bulk stream, K * N slots per launch
     //   C(b)  temporal + spatial reuse, one sample after the other (needs the previous sample)        caller's stream, N pixels per launch
@@ -710,6 +712,7 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
             hipStream_t sq = h ? st2 : st;
             PtSet T = pt_set(PB, h, (size_t)Kp * (size_t)N, nbq);
             PtQueues Q = T.q; Q.NV = ks * N; Q.first_sample_is_zero = (is == 0); if (h) Q.lane = 4;
+            if (a->tex) Q.cl_prim = ctx->ray_prim + (size_t)h * (size_t)Kp * (size_t)N;     // textured frame: the continuation rays' triangles (this half's rays)
             uint32_t fi = a->random_offset + passes * (uint32_t)is + 5;   // pass number of new_dir for a sample with a temporal pass before it
             mirres_path_t P0 = {occ, a->pos, a->normal, B.ray_dir, a->kd, a->rough_metal, T.prd, T.pos[0], T.rd[0], T.occ[0], T.n[0]};
             // the bounce kernels run over live-slot lists and leave the other slots alone: the per-bounce masks k_pt_reduce reads must say "nothing" there
@@ -719,8 +722,11 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
             fi += 5;
             int src = 0;
             for (int bo = 1; bo <= max_bounce; bo++) {
-                // material lookup at the new vertices: compacted slot list -> hash-grid gather -> MFMA MLP -> scatter (slot_c is free between passes)
-                if (a->mat && !(getenv("MIRRES_MATNET") && getenv("MIRRES_MATNET")[0] == 'v')) rc = launch_matnet_scatter_mfma(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.slot_c, &Q.counters[2], sq, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur], &Q.gs);
+                // material lookup at the new vertices: compacted slot list -> hash-grid gather -> MFMA MLP -> scatter (slot_c is free between passes);
+                // a textured mesh instead: the live slots' texels at the triangles their continuation rays hit (slot_c still maps a slot to its ray)
+                if (a->tex) rc = launch_texmat_live(a->tex, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur],
+                                                    Q.slot_c, Q.cl_prim, sq);
+                else if (a->mat && !(getenv("MIRRES_MATNET") && getenv("MIRRES_MATNET")[0] == 'v')) rc = launch_matnet_scatter_mfma(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.slot_c, &Q.counters[2], sq, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur], &Q.gs);
                 else rc = launch_matnet_scatter(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, a->const_kd, a->const_rm, sq);
                 if (rc) return rc;
                 mirres_path_t Pb = {T.occ[src], T.pos[src], T.n[src], T.rd[src], T.kd, T.rm, T.prd, T.pos[src ^ 1], T.rd[src ^ 1], T.occ[src ^ 1], T.n[src ^ 1]};

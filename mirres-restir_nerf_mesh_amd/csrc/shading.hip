@@ -16,7 +16,7 @@ namespace mr {
 int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, int32_t* hit,
                             unsigned long long* stats, hipStream_t s, int reference_order);
 int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
-                                unsigned long long* stats, hipStream_t s);
+                                unsigned long long* stats, hipStream_t s, int32_t* prim);
 
 #define MR_BLOCK 256
 #ifndef MR_GEN_BLOCK
@@ -349,11 +349,15 @@ int launch_new_dir(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_path_t* p, uin
     MR_HIP(hipMemsetAsync(&Q.counters[1], 0, sizeof(uint32_t), s));
     k_new_dir_gen<<<grid_for(NV, MR_GEN_BLOCK), MR_GEN_BLOCK, 0, s>>>(*p, ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, ctx->y_off,
                                                                        Q.cl_rays, &Q.counters[1], Q.slot_c);
-    int rc = trace_closest_q(ctx, bvh, Q.cl_rays, &Q.counters[1], (size_t)NV, Q.cl_hit, s, Q.lane);
+    int32_t* cl_prim = Q.cl_prim;
+    const bool want_prim = !qq && p->new_prim;       // stepwise ABI: the triangle of every next vertex (mirres_path_t::new_prim)
+    if (want_prim) { int rc = ensure_ray_prim(ctx, (size_t)NV); if (rc) return rc; cl_prim = ctx->ray_prim; }
+    int rc = trace_closest_q(ctx, bvh, Q.cl_rays, &Q.counters[1], (size_t)NV, Q.cl_hit, s, Q.lane, cl_prim);
     if (rc) return rc;
     if (Q.live[0]) MR_HIP(hipMemsetAsync(&Q.counters[3 + Q.live_cur], 0, sizeof(uint32_t), s));
     k_new_dir_resolve<<<grid_for(NV, MR_BLOCK * MR_RES_PER), MR_BLOCK, 0, s>>>(*p, NV, Q.slot_c, Q.cl_hit, Q.live[0] ? Q.live[Q.live_cur] : nullptr, &Q.counters[3 + Q.live_cur]);
     MR_LAUNCH_CHECK("pt_new_dir");
+    if (want_prim) return launch_slot_prim(NV, Q.slot_c, p->new_occ, cl_prim, p->new_prim, s);
     return 0;
 }
 int launch_bounce(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_path_t* p, uint32_t frameIndex, uint32_t bounce_count, float* color,
@@ -369,11 +373,15 @@ int launch_bounce(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, con
     k_bounce_gen<<<ggen, MR_BGEN_BLOCK, 0, s>>>(*p, envh(env), ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, ctx->y_off, qq ? 1 : 0,
                                                                       color, dc, sc, Q.any_rays, &Q.counters[0], Q.cl_rays, &Q.counters[1], Q.slot_a, Q.mask_a, Q.slot_c, Q.pend, lin, lin_n);
     int rc = trace_any_q(ctx, bvh, Q.any_rays, &Q.counters[0], 2 * (size_t)NV, Q.any_hit, s, Q.lane); if (rc) return rc;
-    rc = trace_closest_q(ctx, bvh, Q.cl_rays, &Q.counters[1], (size_t)NV, Q.cl_hit, s, Q.lane); if (rc) return rc;
+    int32_t* cl_prim = Q.cl_prim;
+    const bool want_prim = !qq && p->new_prim;
+    if (want_prim) { rc = ensure_ray_prim(ctx, (size_t)NV); if (rc) return rc; cl_prim = ctx->ray_prim; }
+    rc = trace_closest_q(ctx, bvh, Q.cl_rays, &Q.counters[1], (size_t)NV, Q.cl_hit, s, Q.lane, cl_prim); if (rc) return rc;
     if (lout) MR_HIP(hipMemsetAsync(lout_n, 0, sizeof(uint32_t), s));
     if (acc_c) k_bounce_resolve<true><<<gres, MR_BLOCK, 0, s>>>(*p, NV, Q.slot_a, Q.mask_a, Q.slot_c, Q.any_hit, Q.cl_hit, Q.pend, color, dc, sc, acc_c, acc_d, acc_s, qq ? 1 : 0, lin, lin_n, lout, lout_n);
     else k_bounce_resolve<false><<<gres, MR_BLOCK, 0, s>>>(*p, NV, Q.slot_a, Q.mask_a, Q.slot_c, Q.any_hit, Q.cl_hit, Q.pend, color, dc, sc, nullptr, nullptr, nullptr, qq ? 1 : 0, lin, lin_n, lout, lout_n);
     MR_LAUNCH_CHECK("pt_bounce");
+    if (want_prim) return launch_slot_prim(NV, Q.slot_c, p->new_occ, cl_prim, p->new_prim, s);
     return 0;
 }
 

@@ -16,6 +16,7 @@ import time
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import lib, check, stream_ptr
 from . import raster, meters
 
@@ -357,3 +358,112 @@ def export_stage1(path, vertices, triangles, v_cumsum, f_cumsum, mlp, texture_si
             log("[export] cascade %d: v=%d f=%d, %dx%d (ssaa %d), %s, texel coverage %.3f -> %s" % (cas, v.shape[0], f.shape[0], w0, h0, ssaa, note,
                                                                                               r["fill"], files[-2]))
     return files
+
+
+# ------------------------------------------------------------------------------------------------------------------- the asset read back
+def srgb_decode_table():
+    """decode[q] = srgb_to_linear(q / 255) (harness.srgb_to_linear): what a viewer does with an 8-bit sRGB texture.  The bake truncates when it
+    quantises (mirres_bake_quantise), so the decoded value sits up to one LSB below the field's value, half an LSB on average."""
+    from .harness import srgb_to_linear
+    return srgb_to_linear(torch.arange(256, dtype=torch.float32) / 255.0).to(torch.float32)
+
+
+class TexturedMaterial:
+    """The exported stage-1 asset as a material source of the renderer (mirres_texmat_t): the concatenated render mesh (build the BVH from `verts` /
+    `tris`), per-corner UVs in the reference's convention (v = 1 - v'), and per cascade one packed texel plane u8[H, W, 8] = (kd.rgb, roughness,
+    metallic, 0, 0, 0) of the 8-bit sRGB bytes.  There is no gradient path through a lookup: training and the stepwise loop refuse it."""
+    is_textured = True
+
+    def __init__(self, verts, tris, vt, ft, tri_end, planes, roughness_min=0.08, device="cuda"):
+        if not 1 <= len(planes) <= 8 or len(tri_end) != len(planes):
+            raise ValueError("TexturedMaterial: 1 to 8 cascades, one triangle range each (%d planes, %d ranges)" % (len(planes), len(tri_end)))
+        dev = torch.device(device)
+        self.verts = torch.as_tensor(verts, dtype=torch.float32).to(dev).contiguous()
+        self.tris = torch.as_tensor(tris).to(dev, torch.int32).contiguous()
+        self.vt = torch.as_tensor(vt, dtype=torch.float32).to(dev).contiguous()
+        self.ft = torch.as_tensor(ft).to(dev, torch.int32).contiguous()
+        self.tri_end = [int(x) for x in tri_end]
+        self.planes = [torch.as_tensor(p).to(dev, torch.uint8).contiguous() for p in planes]
+        for p in self.planes:
+            if p.dim() != 3 or p.shape[2] != 8:
+                raise ValueError("TexturedMaterial: a texel plane is u8[H, W, 8], got %s" % (tuple(p.shape),))
+        self.decode = srgb_decode_table().to(dev).contiguous()
+        self.roughness_min = float(roughness_min)
+        self.n_cas = len(self.planes)
+        self._st = None
+
+    def _struct(self):
+        if self._st is None:
+            st = _lib.TexMat()
+            st.verts, st.tris, st.vt, st.ft = (t.data_ptr() for t in (self.verts, self.tris, self.vt, self.ft))
+            st.n_cas = self.n_cas
+            for c, p in enumerate(self.planes):
+                st.tri_end[c] = self.tri_end[c]; st.H[c] = int(p.shape[0]); st.W[c] = int(p.shape[1]); st.texels[c] = p.data_ptr()
+            st.decode = self.decode.data_ptr(); st.rough_min = self.roughness_min
+            self._st = st
+        return self._st
+
+    @torch.no_grad()
+    def lookup(self, prim, pos, occ=None, kd=None, rough_metal=None, use_scale=False, scale=(1.0, 1.0, 1.0)):
+        """mirres_texmat_lookup: rows with occ >= 0.5 (all when occ is None) get kd f32[n,3] / (roughness, metallic) f32[n,2] of the texel under
+        `pos` on triangle `prim`; other rows of `kd` / `rough_metal` (given or zeros) are left as they are, apart from the use_scale clamp of kd."""
+        n = int(prim.shape[0])
+        dev = self.verts.device
+        prim = prim.to(dev, torch.int32).contiguous(); pos = pos.to(dev, torch.float32).contiguous()
+        if pos.numel() != 3 * n or (occ is not None and occ.numel() != n):
+            raise ValueError("TexturedMaterial.lookup: prim [%d], pos %s, occ %s" % (n, tuple(pos.shape), None if occ is None else tuple(occ.shape)))
+        occ = occ.to(dev, torch.float32).contiguous() if occ is not None else None
+        kd = torch.zeros((n, 3), dtype=torch.float32, device=dev) if kd is None else kd
+        rough_metal = torch.zeros((n, 2), dtype=torch.float32, device=dev) if rough_metal is None else rough_metal
+        for t, w in ((kd, 3), (rough_metal, 2)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != w * n:
+                raise ValueError("TexturedMaterial.lookup: outputs are contiguous f32[n, 3] / f32[n, 2]")
+        s3 = (C.c_float * 3)(*[float(x) for x in scale])
+        check(lib().mirres_texmat_lookup(C.byref(self._struct()), occ.data_ptr() if occ is not None else None, prim.data_ptr(), pos.data_ptr(), n,
+                                         kd.data_ptr(), rough_metal.data_ptr(), int(bool(use_scale)), s3, stream_ptr()), "mirres_texmat_lookup")
+        return kd, rough_metal
+
+
+def _read_texture(path_base):
+    from PIL import Image
+    for ext in (".png", ".jpg", ".jpeg"):
+        if os.path.exists(path_base + ext):
+            return np.asarray(Image.open(path_base + ext).convert("RGB"), np.uint8), path_base + ext
+    raise FileNotFoundError("%s.png / .jpg: no such texture" % path_base)
+
+
+def load_stage1(path, cascades=None, roughness_min=0.08, device="cuda"):
+    """The stage-1 asset export_stage1 writes (`mesh_{cas}.obj`, `feat0_{cas}`, `feat1_{cas}` as .png or .jpg, e.g. the reference's own JPEG export) ->
+    TexturedMaterial.  cascades=None: every cascade found from 0 on.  Cascades are concatenated with their vertex / UV indices shifted
+    (checkpoint.load_stage0_mesh).  Refuses missing files, faces without UVs and feat0 / feat1 of different sizes."""
+    if cascades is None:
+        cascades = 0
+        while os.path.exists(os.path.join(path, "mesh_%d.obj" % cascades)):
+            cascades += 1
+        if cascades == 0:
+            raise FileNotFoundError("%s: no mesh_0.obj" % path)
+    vs, vts, fs, fts, planes, tri_end = [], [], [], [], [], []
+    nv = nt = nf = 0
+    for cas in range(int(cascades)):
+        obj = os.path.join(path, "mesh_%d.obj" % cas)
+        if not os.path.exists(obj):
+            raise FileNotFoundError("%s: no such mesh" % obj)
+        v, vt_raw, f, ft = read_obj(obj)
+        if f.shape[0] == 0:
+            raise ValueError("%s: no faces" % obj)
+        if (ft < 0).any():
+            raise ValueError("%s: faces without texture coordinates" % obj)
+        if f.max() >= v.shape[0] or f.min() < 0 or ft.max() >= vt_raw.shape[0]:
+            raise ValueError("%s: a face refers to a vertex or texture coordinate that does not exist" % obj)
+        t0, p0 = _read_texture(os.path.join(path, "feat0_%d" % cas))
+        t1, p1 = _read_texture(os.path.join(path, "feat1_%d" % cas))
+        if t0.shape != t1.shape:
+            raise ValueError("%s is %dx%d, %s %dx%d: the two textures of a cascade must have one size" % (p0, t0.shape[1], t0.shape[0], p1, t1.shape[1], t1.shape[0]))
+        plane = np.zeros(t0.shape[:2] + (8,), np.uint8)
+        plane[..., 0:3] = t0; plane[..., 3] = t1[..., 1]; plane[..., 4] = t1[..., 2]
+        vs.append(v); vts.append(np.stack((vt_raw[:, 0], np.float32(1) - vt_raw[:, 1]), 1).astype(np.float32))
+        fs.append(f + nv); fts.append(ft + nt)
+        nv += v.shape[0]; nt += vt_raw.shape[0]; nf += f.shape[0]
+        planes.append(plane); tri_end.append(nf)
+    return TexturedMaterial(np.concatenate(vs), np.concatenate(fs).astype(np.int32), np.concatenate(vts), np.concatenate(fts).astype(np.int32), tri_end, planes,
+                            roughness_min=roughness_min, device=device)

@@ -138,7 +138,13 @@ def build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa=1, mlp_mat=None
     normal = torch.where(occ > 0.5, r["normal"], torch.zeros_like(r["normal"])).contiguous()
     depth = torch.norm(pos - rays_o, dim=1, keepdim=True).contiguous()
     N = h * w
-    if mlp_mat is not None:
+    if getattr(mlp_mat, "is_textured", False):
+        # the exported asset (export.TexturedMaterial): the hit pixels' texels at the primary triangle, by the rule the indirect hits use (mirres_texmat_lookup);
+        # background pixels keep the constants below. `worker` must hold the asset's own mesh.
+        kd_map = torch.tensor(kd, dtype=torch.float32, device=dev)[None].expand(N, 3).contiguous()
+        rm = torch.tensor([roughness, metallic], dtype=torch.float32, device=dev)[None].expand(N, 2).contiguous()
+        mlp_mat.lookup(r["prim"], pos, occ=occ, kd=kd_map, rough_metal=rm)
+    elif mlp_mat is not None:
         kdks = mlp_mat.sample_no_di(pos)
         kd_map = kdks[:, 0:3].contiguous(); rm = torch.cat((kdks[:, 4:5], kdks[:, 5:6]), dim=-1).contiguous()
     else:
@@ -149,7 +155,7 @@ def build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa=1, mlp_mat=None
 
 
 def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, random_offset=0, de=2, c=2.0, n=0.1, p=0.001, max_bounce=None,
-              albedo_scale=None, shard=None, rank=0, world=1, group=None, return_maps=False, balancer=None):
+              albedo_scale=None, shard=None, rank=0, world=1, group=None, return_maps=False, balancer=None, gbuffer_consts=None):
     """One `--test --spp N` frame of the BRDF branch (Trainer.test_step -> render_stage1(is_test=True), nerf/renderer.py:1083-1129, 1162-1164,
     1208-1209, 1265-1302): G-buffer for the dataset camera, the fused frame (mirres_render), tone curve, alpha, SSAA down-scale, white background.
     Returns the [H, W, 3] image in [0, 1]; with `return_maps` also the dict of float maps that Trainer.test saves as EXR files (meters.write_test_maps).
@@ -157,11 +163,13 @@ def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, ran
     _z): the primary albedo is scaled here and `use_scale` does the same at the indirect hits.
     One view on several GPUs: `shard` = "strips" (exact row strips + halo exchange + all-gather of radiance rows, dist.render_strips) or "spp"
     (sample slices + all-reduce, dist.render_sharded) with this process's `rank` of `world`; every rank returns the whole image. `balancer`: a
-    dist.StripBalancer kept by the caller across the views of a run — strip boundaries then follow the strips' measured times (same pixels for any boundaries)."""
+    dist.StripBalancer kept by the caller across the views of a run — strip boundaries then follow the strips' measured times (same pixels for any boundaries).
+    `mlp_mat` may also be an export.TexturedMaterial (the exported stage-1 asset; `worker` then holds the asset's mesh): primary and indirect hits read its
+    texels.  `gbuffer_consts` = dict(kd=, roughness=, metallic=): the G-buffer constants of build_gbuffer_from_pose (pixels without a looked-up material)."""
     from . import renderer_restir as RR
     from . import dist as MD
     from ._ops import get_ctx
-    g = build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa, mlp_mat)
+    g = build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa, mlp_mat, **(gbuffer_consts or {}))
     use_scale = albedo_scale is not None
     scale = tuple(float(x) for x in albedo_scale) if use_scale else (1.0, 1.0, 1.0)
     if use_scale:

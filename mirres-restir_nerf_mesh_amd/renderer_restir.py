@@ -219,6 +219,9 @@ def restir_di_with_pt(use_scale, scale_x, scale_y, scale_z, mlp_mat, bvh_restir_
     caller asks for the reference-shaped loop under autograd (MIRRES_TRAIN_FUSED=0): EvaluateFinalSamples_di and FinalShading are autograd Functions exactly
     where the reference has them; everything else runs on detached inputs.  The caller's prev_* arguments are ignored and history starts empty, as in the
     reference (:291-302)."""
+    if getattr(mlp_mat, "is_textured", False):
+        raise _lib.MirresError("restir_di_with_pt: the stepwise loop looks a material up by position; a textured mesh needs the hit triangle — render it with "
+                               "render_fused (mirres_render)")
     fx, fy = int(framedim_x), int(framedim_y)
     N = fx * fy
     dev = occ_map.device
@@ -322,7 +325,10 @@ def render_fused(ctx, bvh_restir_worker, mlp_mat, use_scale, scale, env_map, occ
         if t.numel() != N * width:
             raise _lib.MirresError("%s must have %d x %d elements, got %s" % (name, N, width, tuple(t.shape)))
         t = _f32(t.detach()); keep.append(t); setattr(a, name, t.data_ptr())
-    if mlp_mat is not None:
+    if getattr(mlp_mat, "is_textured", False):      # export.TexturedMaterial: the exported asset at every indirect hit (mirres_texmat_t)
+        st = mlp_mat._struct(); keep += [st, mlp_mat]
+        a.tex = C.pointer(st); a.mat = None
+    elif mlp_mat is not None:
         st = mlp_mat._struct(); keep.append(st)
         a.mat = C.pointer(st)
     else:
@@ -405,7 +411,9 @@ def run_restir_di_with_pt(use_scale, scale_x, scale_y, scale_z, mlp_mat, gb_dept
     denoised_indirect_diff, denoised_indirect_spec), each f32[N,3]."""
     from .render_helper import MLPTexture3D
     grad = _needs_grad(env_map, normal_map, diffuse_map, roughness_specular)
-    if not grad and (mlp_mat is None or isinstance(mlp_mat, MLPTexture3D)):
+    if getattr(mlp_mat, "is_textured", False) and grad:
+        raise _lib.MirresError("a textured mesh (export.TexturedMaterial) has no gradient path: it renders without autograd only (no training against textures)")
+    if not grad and (mlp_mat is None or isinstance(mlp_mat, MLPTexture3D) or getattr(mlp_mat, "is_textured", False)):
         random_offset = np.random.randint(2**20) if _FIXED_RANDOM_OFFSET is None else int(_FIXED_RANDOM_OFFSET)
         outs, _, _ = render_fused(InitialResampling_m.ctx, bvh_restir_worker, mlp_mat, use_scale, (scale_x, scale_y, scale_z), env_map, occ_map, normal_map,
                                   depth_map, diffuse_map, roughness_specular, ray_dir_map, pos_map, spp, denoise_iter, stepWidth, c_phi_scale, n_phi_scale,

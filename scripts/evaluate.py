@@ -4,10 +4,15 @@ PSNR / SSIM against the dataset images when they can be read.
 
     python scripts/evaluate.py --workspace <ws> --ckpt <ws>/checkpoints/ngp_stage1_ep0100.pth --transforms <data>/transforms_test.json \
         [--spp 512 --ssaa 2 --downscale 1 --bound 2 --roughness_min 0.08 --me_max 0 --out <ws>/results_brdf --limit 0 --synthetic]
-        [--export_mesh --texture_size 4096]
+        [--export_mesh --texture_size 4096] [--textured_mesh <ws>/mesh_stage1]
 
 `--export_mesh` (off by default) writes the stage-1 textured mesh after the views, as the reference's `--test` does unless `--test_no_mesh`
 (main.py:256-258): <ws>/mesh_stage1/mesh_{cas}.obj / .mtl / feat0_{cas}.png / feat1_{cas}.png (mirres_restir_nerf_mesh_amd/export.py, with --ssaa).
+
+`--textured_mesh DIR` renders the dataset views from an exported stage-1 asset (mesh_{cas}.obj + feat0 / feat1_{cas}.png or .jpg, export.load_stage1) instead
+of the checkpoint's mesh and field: every primary and indirect hit reads the textures (mirres_texmat_lookup).  The environment map comes from the checkpoint
+or from --envmap_path (relighting and albedo scale as usual).  With a checkpoint the field's own frames are rendered first and every textured frame
+reports its PSNR against the field's frame at the same seed (what the export lost); with --export_mesh the asset is the one just written.
 
 The material-field constants are the reference's CLI ones and MUST equal the training run's (nerf/network.py:119-125): `--bound` (hash-grid AABB
 = +-bound, main.py:39 default 2; also the mesh cascade count 1 + ceil(log2(bound)), nerf/renderer.py:97, unless `--cascade` overrides it),
@@ -83,6 +88,8 @@ def main():
     p.add_argument("--lpips_lin", default=None, help="the lpips package's weights/v0.1/vgg.pth (the five linear heads)")
     p.add_argument("--export_mesh", action="store_true", help="after the views, export the stage-1 textured mesh to <workspace>/mesh_stage1 (main.py:256-258; off by default)")
     p.add_argument("--texture_size", type=int, default=4096, help="main.py --texture_size: texture side of the first cascade of --export_mesh (baked at --ssaa)")
+    p.add_argument("--textured_mesh", default=None, help="render the views from this exported stage-1 asset (mesh_{cas}.obj, feat0/feat1_{cas}.png|.jpg); with "
+                   "--ckpt also report each textured frame's PSNR against the field's frame")
     a = p.parse_args()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
@@ -98,6 +105,8 @@ def main():
         if world > 1:
             dist.barrier()
         a.ckpt, a.transforms = os.path.join(a.workspace, "checkpoints", "ngp_stage1_ep0001.pth"), os.path.join(a.workspace, "transforms_test.json")
+    if a.textured_mesh and not a.ckpt and a.transforms:
+        return textured_only(a, p, rank, world)
     if not (a.workspace and a.ckpt and a.transforms):
         p.error("--workspace, --ckpt and --transforms are required (or --synthetic)")
     out_dir = a.out or os.path.join(a.workspace, "results_brdf")
@@ -132,6 +141,7 @@ def main():
     n_mine = 0
     # exact strip sharding: the boundaries follow the strips' measured times from view to view (a test set's cameras move smoothly; same pixels for any boundaries)
     balancer = MD.StripBalancer(Hh * a.ssaa, world) if (world > 1 and a.shard == "strips") else None
+    field_imgs = {}
     for i, fr in enumerate(frames):
         if world > 1 and a.shard == "views" and i % world != rank:
             continue
@@ -144,6 +154,8 @@ def main():
         if a.save_maps:
             img, maps = img
         torch.cuda.synchronize(); t_render += time.perf_counter() - t0
+        if a.textured_mesh:
+            field_imgs[i] = img
         if world > 1 and a.shard != "views" and rank != 0:
             continue                                                       # every rank holds the whole frame; rank 0 writes and scores it
         files = meters.write_test_frame(out_dir, name, i, img)
@@ -176,6 +188,55 @@ def main():
         if a.export_mesh:          # trainer.export_stage1(resolution=opt.texture_size) after the test views (main.py:256-258)
             from mirres_restir_nerf_mesh_amd import export as EX
             EX.export_stage1(os.path.join(a.workspace, "mesh_stage1"), verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa)
+    if a.textured_mesh:
+        if world > 1:
+            dist.barrier()                                                 # the asset may just have been written by rank 0
+        render_textured(a, frames, base, intr, Hh, Ww, light, albedo_scale, out_dir, name, rank, world, field_imgs, cfg["roughness_min"])
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def render_textured(a, frames, base, intr, Hh, Ww, light, albedo_scale, out_dir, name, rank, world, field_imgs, roughness_min):
+    """The views from the exported asset (export.load_stage1 -> mirres_texmat_t): BVH of the asset's own mesh, the same seeds as the field's views; per view
+    the PSNR against the field's frame when there is one (the export's loss: atlas, 8-bit sRGB, gutter inpaint, SSAA downsample)."""
+    from mirres_restir_nerf_mesh_amd import export as EX
+    tex = EX.load_stage1(a.textured_mesh, roughness_min=roughness_min)
+    Wt = RR.restirbvhWorker(tex.verts, tex.tris); Wt.update_mesh(Wt.vrt, Wt.v_ind)
+    shard = a.shard if world > 1 and a.shard != "views" else None
+    psnrs = []
+    for i, fr in enumerate(frames):
+        if world > 1 and a.shard == "views" and i % world != rank:
+            continue
+        pose = nerf_pose(fr["transform_matrix"], a.scale, a.offset)
+        img = harness.test_view(Wt, tex, light, torch.from_numpy(pose), intr, Hh, Ww, a.spp, a.ssaa, random_offset=i * 7919, albedo_scale=albedo_scale,
+                                shard=shard, rank=rank, world=world)
+        if world > 1 and shard is not None and rank != 0:
+            continue
+        files = meters.write_test_frame(out_dir, name + "_textured", i, img)
+        note = ""
+        if i in field_imgs:
+            v = harness.psnr(img, field_imgs[i]); psnrs.append(v)
+            note = "  PSNR vs field %.3f" % v
+        print("[textured %d/%d] %s%s" % (i + 1, len(frames), os.path.basename(files[0]), note), flush=True)
+    if psnrs:
+        print("textured vs field: mean PSNR %.3f over %d view(s)" % (float(np.mean(psnrs)), len(psnrs)), flush=True)
+
+
+def textured_only(a, p, rank, world):
+    """--textured_mesh without a checkpoint: the asset under --envmap_path (relighting; there is no trained environment map to take)."""
+    if a.envmap_path == "None":
+        p.error("--textured_mesh without --ckpt needs --envmap_path")
+    if world > 1:
+        import torch.distributed as dist
+    light = torch.from_numpy(np.ascontiguousarray(harness.read_hdr(a.envmap_path))).cuda()
+    albedo_scale = (a.albedo_scale_x, a.albedo_scale_y, a.albedo_scale_z)
+    tf = json.load(open(a.transforms)); base = os.path.dirname(os.path.abspath(a.transforms))
+    Hh, Ww = int(tf.get("h", a.H)) // a.downscale, int(tf.get("w", a.W)) // a.downscale
+    focal = 0.5 * Ww / np.tan(0.5 * tf["camera_angle_x"])
+    frames = tf["frames"][: a.limit] if a.limit > 0 else tf["frames"]
+    out_dir = a.out or os.path.join(a.workspace or os.path.dirname(os.path.abspath(a.textured_mesh)), "results_textured")
+    rmin = a.roughness_min if a.roughness_min is not None else 0.08
+    render_textured(a, frames, base, (focal, focal, Ww * 0.5, Hh * 0.5), Hh, Ww, light, albedo_scale, out_dir, "asset", rank, world, {}, rmin)
     if world > 1:
         dist.destroy_process_group()
 
