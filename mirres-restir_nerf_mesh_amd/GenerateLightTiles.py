@@ -7,7 +7,10 @@ from ._ops import _f32
 
 def make_sampleable(m, env_map, width, height):
     """GenerateLightTiles.py:4-29 -> (pdf_ [Hc*Wc,1], cdf_ [Hc*(Wc+1),1], mpdf_ [Hc,1], mcdf_ [Hc+1,1]).
-    env_map: vertically flipped, flattened [Hc*Wc,3] (renderer_restir.py:305-311)."""
+    env_map: vertically flipped, flattened [Hc*Wc,3] (renderer_restir.py:305-311).
+    A map of total weight 0 (all black) keeps the reference's arithmetic: every row falls back to uniform and the marginal divides by 0, so mpdf_ and
+    mcdf_[:-1] are NaN.  It is not refused: no light sample then carries radiance, no reservoir takes one, and the frame comes out finite and black
+    (tests/test_gpu_envmap.py::test_all_black_map)."""
     env_map = _f32(env_map.contiguous())
     width, height = int(width), int(height)
     dev = env_map.device

@@ -291,7 +291,8 @@ def psnr(pred, gt):
 
 def read_hdr(path):
     """Radiance RGBE (.hdr) reader -> float32 [H,W,3] RGB, for `--envmap_path` relighting (the reference uses cv2.imread(..., IMREAD_ANYDEPTH),
-    nerf/network.py:136). Supports flat and new-style RLE scanlines."""
+    nerf/network.py:136). Supports flat and new-style RLE scanlines.  An all-black map is accepted: it renders black, not NaN (see
+    GenerateLightTiles.make_sampleable)."""
     with open(path, "rb") as f:
         data = f.read()
     pos = 0

@@ -131,3 +131,21 @@ def direct_sums(tape, env, occ, normal, ray_dir_raw, kd, rm):
     fdist = torch.where((light_data[:, 0:1] > 0.1) & (vis > 0), torch.full_like(vis, 1e6), torch.zeros_like(vis))
     c, d, s = final_shading(rep(occ.reshape(N, 1)), rep(normal), rep(rd), rep(kd), rep(rm), oct_decode(light_data[:, 1:3]), fdist, Li)
     return tuple(x.reshape(S, N, 3).sum(0) for x in (c, d, s))
+
+
+def direct_emission_cotangent(tape, env, occ, normal, ray_dir_raw, kd, rm, cot):
+    """Per tape row, the derivative of sum_k <cot[k], direct_sums[k]> with respect to the emission env_le returned for the row's light sample
+    ([S*N, 3], zero for rows that contribute nothing): W x d/dLi.  The environment gradient is this, scattered through the rows' bilinear footprints."""
+    H, W = env.shape[0], env.shape[1]
+    N = normal.shape[0]
+    S = tape.shape[0] // N
+    tex = env.flip(0).reshape(H * W, 3)
+    rd = ray_dir_raw / torch.clamp(torch.sqrt((ray_dir_raw * ray_dir_raw).sum(1, keepdim=True)), min=1e-6)
+    rep = lambda t: t.repeat(S, 1)
+    light_data, weight, vis = tape[:, 0:3], tape[:, 5:6], tape[:, 6:7]
+    Li = eval_final(tex, W, H, light_data, weight, vis).detach().requires_grad_(True)
+    fdist = torch.where((light_data[:, 0:1] > 0.1) & (vis > 0), torch.full_like(vis, 1e6), torch.zeros_like(vis))
+    out = final_shading(rep(occ.reshape(N, 1)), rep(normal), rep(rd), rep(kd), rep(rm), oct_decode(light_data[:, 1:3]), fdist, Li)
+    sum((x.reshape(S, N, 3).sum(0) * c).sum() for x, c in zip(out, cot)).backward()
+    on = (light_data[:, 0:1] > 0.1) & (vis > 0)
+    return torch.where(on, Li.grad * weight, torch.zeros_like(Li.grad))

@@ -20,10 +20,14 @@ TABLE, LIST = 2048, 2048      # backward.hip: MR_DBW_TABLE keys and MR_DBW_LIST 
 WG_PX = 32                    # pixels per workgroup of k_direct_bwd: 256 threads / MR_DBW_SPLIT lanes per pixel
 
 
-def _frame(oracle, scene_mod, fx, fy, env_hw, flat=False, rough=False):
+def _frame(oracle, scene_mod, fx, fy, env_hw, env_kind=None, rough=False):
+    """env_kind: None = SmallFrame's sky with a sun lobe; "flat"; "black_lower_sun"."""
     F = SmallFrame(oracle, scene_mod, fx=fx, fy=fy, env_hw=env_hw)
     env = F.env
-    if flat:     # low contrast, no sun: light samples spread over the whole sky instead of the few texels of a sun lobe
+    if env_kind == "black_lower_sun":     # black where world y < 0 (whole table rows fall back) next to a one-texel sun 1e5 x the median (tests/envmap_refs.py)
+        import envmap_refs as E
+        env = E.black_world_lower(E.with_sun(E.sky(env_hw[0], env_hw[1], 2)))
+    elif env_kind == "flat":     # low contrast, no sun: light samples spread over the whole sky instead of the few texels of a sun lobe
         env = (0.4 + 0.25 * scene_mod.make_env(env_hw[0], env_hw[1], sun=0.0)).astype(np.float32)
     rm = F.rm.copy()
     if rough:
@@ -73,7 +77,7 @@ def _cotangents(N, seed):
     return [torch.rand((N, 3), device="cuda", generator=gen) for _ in range(3)]
 
 
-def _footprints(tape, occ, N, H, W):
+def _footprints(tape, occ, N, H, W, weights=False):
     """The environment texels (caller's layout) k_direct_bwd scatters into, per tape row: [rows, 4] indices of the rows that contribute (non-empty reservoir,
     visible, foreground pixel, not at a pole), and those rows. float64 restatement of env_le_footprint(ngp_dir(oct_decode(light_data.yz)))."""
     S = tape.shape[0] // N
@@ -94,7 +98,84 @@ def _footprints(tape, occ, N, H, W):
     x1, y1 = np.clip(x0 + 1, 0, W - 1), np.clip(y0 + 1, 0, H - 1)
     x0, y0 = np.clip(x0, 0, W - 1), np.clip(y0, 0, H - 1)
     caller = lambda yy, xx: (H - 1 - yy) * W + xx         # tex row y = caller's row H - 1 - y (k_flip_env)
-    return np.stack((caller(y0, x0), caller(y0, x1), caller(y1, x0), caller(y1, x1)), 1), rows
+    idx = np.stack((caller(y0, x0), caller(y0, x1), caller(y1, x0), caller(y1, x1)), 1)
+    if not weights:
+        return idx, rows
+    u, v = x - x0, y - y0                                 # against the clamped corner, as helper.slang:46-71
+    return idx, rows, np.stack(((1 - u) * (1 - v), u * (1 - v), (1 - u) * v, u * v), 1)
+
+
+def _f32_footprints(oracle, ld, H, W):
+    """The kernel's own footprints, env_le_footprint(ngp_dir(oct_decode(light_data.yz))) in fp32, for tape rows ld [n, 3]: texel indices (caller layout)
+    and weights [n, 4].  Read off the oracle's env_le, which evaluates the same fp32 arithmetic (include/mirres_fmath.h) and is linear in the texture: the four
+    texels of a footprint have the four parities (x % 2, y % 2), so a texture that is 1 on one parity class returns that corner's weight exactly
+    ((1 - u) * (1 - v) and so on: the other products are 0), and one that holds x or y on it returns weight * x or weight * y.  A clamped corner (x1 = x0)
+    shares its texel's class and adds to its weight, as the scatter adds it to the texel."""
+    d = np.stack([oracle.oct_decode(f) for f in np.asarray(ld, np.float32)[:, 1:3]]).astype(np.float32)
+    m = np.ascontiguousarray(np.stack([-d[:, 0], d[:, 2], d[:, 1]], 1))                       # ngp_dir: exact in fp32
+    ty, tx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    cls = ((tx % 2) + 2 * (ty % 2)).ravel()
+    idx = np.full((len(m), 4), -1, np.int64); w = np.zeros((len(m), 4))
+    for c in range(4):
+        on = (cls == c).astype(np.float32)
+        probe = np.ascontiguousarray(np.stack([on, on * tx.ravel(), on * ty.ravel()], 1).astype(np.float32))
+        r = oracle.env_le(probe, W, H, m).astype(np.float64)
+        nz = r[:, 0] != 0
+        xx = np.rint(r[nz, 1] / r[nz, 0]).astype(np.int64); yy = np.rint(r[nz, 2] / r[nz, 0]).astype(np.int64)
+        assert ((xx % 2) + 2 * (yy % 2) == c).all() and (xx >= 0).all() and (xx < W).all() and (yy >= 0).all() and (yy < H).all()
+        idx[nz, c] = (H - 1 - yy) * W + xx; w[nz, c] = r[nz, 0]
+    return idx, w
+
+
+def _env_grad_past_2e22(oracle, tape, x, cot, g_env, ref64, N, H, W):
+    """The environment gradient of a map with more than 2^22 texels.  At W = 4096 the fp32 texel coordinate x = phi / 2 pi W - 1/2 of a footprint carries an
+    error of order W x a few ulp, up to ~1e-3 of a texel, so the kernel's bilinear weights and the float64 reference's differ by that much; a texel reached
+    by one heavy sample near its far edge then differs by more than the element-wise tolerance.  So the element-wise check, at its usual tolerances, is made
+    against a float64 scatter of the reference's per-sample derivative W x d/dLi through the KERNEL's fp32 footprints (weights and texels, _f32_footprints);
+    and the difference between that scatter and the pure float64 gradient is shown to be a weight difference within the fp32 error bound, with texel
+    choices that differ only at texel borders."""
+    import torch
+    import adjoint_refs as R
+    t = tape.cpu().numpy()
+    rows = np.nonzero(t[:, 0] > 0.1)[0]
+    gl = R.direct_emission_cotangent(tape.double(), x["env"].double(), x["occ"].double(), x["normal"].double(), x["rd"].double(), x["kd"].double(),
+                                     x["rm"].double(), [c.double() for c in cot]).detach().cpu().numpy()[rows]
+    idx32, w32 = _f32_footprints(oracle, t[rows], H, W)
+    ref32 = np.zeros((H * W, 3))
+    for k in range(4):
+        ok = idx32[:, k] >= 0
+        np.add.at(ref32, idx32[ok, k], gl[ok] * w32[ok, k, None])
+    elementwise(g_env, torch.from_numpy(ref32.reshape(H, W, 3)), "k_direct_bwd d/d(env texel), fp32 footprints")
+    # the whole gap to the float64 gradient is in the weights: per (sample, texel) the float64 minus the fp32 footprint weight
+    idx64, rows64, w64 = _footprints(t, x["occ"][:, 0].cpu().numpy(), N, H, W, weights=True)
+    pos = np.searchsorted(rows, rows64)
+    HW = H * W
+    keys = np.concatenate([(pos[:, None] * HW + idx64).ravel(), (np.arange(len(rows))[:, None] * HW + np.maximum(idx32, 0)).ravel()])
+    vals = np.concatenate([w64.ravel(), -np.where(idx32 >= 0, w32, 0).ravel()])
+    uk, inv = np.unique(keys, return_inverse=True)
+    dw = np.zeros(len(uk)); np.add.at(dw, inv, vals)
+    r_of, tex_of = uk // HW, uk % HW
+    live = np.abs(gl[r_of]).sum(1) > 0
+    # fp32 error of a footprint weight: the texel coordinates x = W phi / 2 pi, y = H theta / pi of an fp32 direction that is a few ulp off; phi = atan2 and
+    # theta = acos are ill-conditioned by 1 / sin(theta) near the map's poles; with the roundings of the products, 4 (W + H) u (1 + 1 / sin theta) bounds
+    # both with room.  A corner that changes texel at a border has a weight within that bound of 0
+    f = t[rows, 1:3].astype(np.float64) * 2 - 1
+    z = 1 - np.abs(f[:, 0]) - np.abs(f[:, 1]); c = np.clip(-z, 0, 1)
+    lx = f[:, 0] + np.where(f[:, 0] >= 0, -c, c); ly = f[:, 1] + np.where(f[:, 1] >= 0, -c, c)
+    cos_t = z / np.sqrt(lx * lx + ly * ly + z * z)                                    # map-frame y = world z (ngp_dir)
+    sin_t = np.sqrt(np.maximum(1 - cos_t * cos_t, 0.0))
+    bound = 4 * (W + H) * 2.0 ** -24 * (1 + 1 / np.maximum(sin_t[r_of], 1e-4))
+    over = np.abs(dw) > bound
+    assert not (over & live).any(), "%d footprint weights differ from float64 by more than the fp32 bound (max ratio %.2f): not an fp32 weight error" % (
+        int((over & live).sum()), float((np.abs(dw) / bound)[live].max()))
+    g = ref64.detach().cpu().numpy().reshape(-1, 3)
+    gap = np.abs(g - ref32)
+    lim = np.zeros((HW, 3)); np.add.at(lim, tex_of, np.abs(gl[r_of]) * np.abs(dw)[:, None])
+    assert (gap <= lim + 1e-12 * np.abs(g).max()).all()
+    scale = np.abs(g).max()
+    n_out = int((gap > 1e-3 * np.abs(g) + 1e-4 * scale).sum())
+    print("[env %dx%d] fp32 vs float64 footprint weights: max difference %.3e (%.2f of its bound); %d gradient elements off the pure float64 gradient by "
+          "more than the element-wise tolerance, max %.3e" % (H, W, np.abs(dw[live]).max(), float((np.abs(dw) / bound)[live].max()), n_out, gap.max()))
 
 
 def _distinct_per_workgroup(idx, rows, N, HW):
@@ -103,12 +184,14 @@ def _distinct_per_workgroup(idx, rows, N, HW):
     return np.bincount(keys // HW, minlength=(N + WG_PX - 1) // WG_PX)
 
 
-# frame fx x fy, env H x W, samples, MIRRES_PT_BATCH, flat env, rough materials
+# frame fx x fy, env H x W, samples, MIRRES_PT_BATCH, env kind (_frame), rough materials
 CASES = [
-    pytest.param((37, 23, (24, 80), 1, None, False, False), id="37x23_env24x80_1spp"),             # S < MR_DBW_SPLIT; N % 32 != 0; non-2:1 env (W/H swap, row flip)
-    pytest.param((37, 23, (24, 80), 9, "4", False, False), id="37x23_env24x80_9spp_batch4"),       # S % 8 != 0; batches of 4, 4, 1 samples: tape offsets
-    pytest.param((48, 40, (8, 16), 17, None, False, False), id="48x40_env8x16_17spp"),             # many samples onto few texels: same-key contention
-    pytest.param((64, 32, (256, 512), 1024, None, True, True), id="64x32_env256x512_1024spp_flat"),  # table, overflow list and direct global atomics
+    pytest.param((37, 23, (24, 80), 1, None, None, False), id="37x23_env24x80_1spp"),              # S < MR_DBW_SPLIT; N % 32 != 0; non-2:1 env (W/H swap, row flip)
+    pytest.param((37, 23, (24, 80), 9, "4", None, False), id="37x23_env24x80_9spp_batch4"),        # S % 8 != 0; batches of 4, 4, 1 samples: tape offsets
+    pytest.param((48, 40, (8, 16), 17, None, None, False), id="48x40_env8x16_17spp"),              # many samples onto few texels: same-key contention
+    pytest.param((64, 32, (256, 512), 1024, None, "flat", True), id="64x32_env256x512_1024spp_flat"),  # table, overflow list and direct global atomics
+    pytest.param((32, 24, (2048, 4096), 16, None, "flat", False), id="32x24_env2048x4096_16spp_flat"),  # texel indices past 2^22: the hash's whole key range
+    pytest.param((48, 40, (64, 128), 8, None, "black_lower_sun", False), id="48x40_env64x128_8spp_black_lower_sun"),  # fallback rows next to a sun
 ]
 
 
@@ -116,12 +199,12 @@ CASES = [
 def test_fused_backward_matches_float64_reference_from_the_tape(case, oracle, scene_mod, monkeypatch):
     import torch
     import adjoint_refs as R
-    fx, fy, env_hw, spp, batch, flat, rough = case
+    fx, fy, env_hw, spp, batch, env_kind, rough = case
     if batch is not None:
         monkeypatch.setenv("MIRRES_PT_BATCH", batch)
     else:
         monkeypatch.delenv("MIRRES_PT_BATCH", raising=False)
-    F, env, rm = _frame(oracle, scene_mod, fx, fy, env_hw, flat, rough)
+    F, env, rm = _frame(oracle, scene_mod, fx, fy, env_hw, env_kind, rough)
     W = _worker(F)
     fw = _forward(F, W, env, rm, spp, seed=777)
     x, N, (H, Wd) = fw["x"], F.N, env_hw
@@ -145,7 +228,10 @@ def test_fused_backward_matches_float64_reference_from_the_tape(case, oracle, sc
         assert float(got[~fg].abs().sum()) == 0.0, nm + ": background pixels carry no gradient"
         elementwise(got, ref.grad, "k_direct_bwd d/d" + nm)
     assert bool(torch.isfinite(g_env).all())
-    elementwise(g_env, x64["env"].grad, "k_direct_bwd d/d(env texel)")
+    if H * Wd <= 1 << 22:
+        elementwise(g_env, x64["env"].grad, "k_direct_bwd d/d(env texel)")
+    else:
+        _env_grad_past_2e22(oracle, tape, x, cot, g_env, x64["env"].grad, N, H, Wd)
     # texels that no footprint reaches (nor a neighbour of one: a boundary sample's truncation may fall either way in fp32) receive exactly nothing
     idx, rows = _footprints(tape.cpu().numpy(), x["occ"][:, 0].cpu().numpy(), N, H, Wd)
     touched = np.zeros(H * Wd, bool); touched[idx.ravel()] = True
@@ -160,6 +246,9 @@ def test_fused_backward_matches_float64_reference_from_the_tape(case, oracle, sc
     distinct = _distinct_per_workgroup(idx, rows, N, H * Wd)
     print("[%dx%d env %dx%d %d spp] %d contributing samples, %d texels touched, distinct texels per workgroup: max %d, median %d" % (
         fx, fy, H, Wd, spp, len(rows), int(touched.sum()), int(distinct.max()), int(np.median(distinct))))
+    if env_kind == "black_lower_sun":
+        bright = np.argmax(env.reshape(-1, 3).sum(1))
+        assert touched[bright] and (env.reshape(-1, 3)[touched].sum(1) == 0).any(), "no footprint on both the sun and a black texel"
     if env_hw == (256, 512):
         # a workgroup with more distinct texels than the table holds spills into the list; with more than table + list, the list is full and the rest
         # goes to global memory directly (each texel outside the table appends at least one list entry)
