@@ -301,6 +301,33 @@ typedef struct mirres_texmat {
 int mirres_texmat_lookup(const mirres_texmat_t* t, const float* occ, const int32_t* prim, const float* pos, int n, float* kd, float* rough_metal,
                          int use_scale, const float* h_scale3, void* stream);
 
+/* ------------------------------------------------------------------ albedo evaluation (the reference's albedo_eval.py; csrc/albedo.hip)
+ * The TensoIR protocol aligns the predicted albedo to the ground truth by one scale per channel before scoring it, and the same three numbers are the
+ * --albedo_scale_x/y/z of the relighting commands.  pred f32[n,3] is a view's albedo, gt_rgba f32[n,4] its ground truth (diffuse-color.exr); a pixel is
+ * masked in iff double(alpha) >= mask_thr (albedo_eval.py:94-95 clears the mask where alpha < thr).  scratch = a device buffer of
+ * MIRRES_ALBEDO_SCRATCH_BYTES bytes (one per stream in use).  All three only enqueue work; results are the same bits on every run.
+ *
+ * mirres_albedo_compact (:93-111): appends the masked-in (pred, gt rgb) pairs of one view, in pixel order, to pool_pred / pool_gt f32[pool_cap,3].
+ * state u64[3] (device, zeroed by the caller before the first view): [0] pairs in the pool (where the append starts; advanced by the kept count),
+ * [1] kept pixels so far with a ground-truth channel > 1 (:98-100 raises on them; the caller reads it after each view), [2] set when the pool was too
+ * small — pairs beyond pool_cap are dropped and [0] stops at pool_cap (the caller sizes the pool for [0] + n beforehand; the flag stays set until the
+ * caller clears it).  Only KEPT pixels are tested against 1: the script takes the maximum over the whole image before masking (:98), so a file it
+ * refuses for a value above 1 outside the mask is accepted here.
+ * mirres_albedo_median (:116-118): out3 f64[3] = np.median(float64(gt) / float64(pred).clip(min=1e-6), axis=0) over the first `count` pairs, exactly
+ * (fp64 division is correctly rounded; an even count gives (a + b) / 2 of the two middle values; one NaN ratio makes its channel NaN).  count <= 0 is
+ * MIRRES_E_ARG: an empty pool has no median.  Both pools 16-byte aligned, count < 2^40.
+ * mirres_albedo_score (:142-172): masked pixels pred * h_scale3 (host f64[3], NULL = 1) in fp64, unmasked pixels of both images 1, prediction clipped
+ * to [0, 1]  ->  out_sums2 f64[2] = the sums over the n * 3 values of (gt - now)^2 and of (gt^(1/2.2) - now^(1/2.2))^2 (fixed summation order; the
+ * script rounds the two gamma images to fp32 before that difference, this sum keeps fp64), and out_pred_u8 / out_gt_u8 u8[n,3] (either may be NULL) =
+ * the gamma images x 255, truncated.                                                                                                              */
+#define MIRRES_ALBEDO_SCRATCH_BYTES 32768
+long long mirres_albedo_scratch_bytes(void);               /* MIRRES_ALBEDO_SCRATCH_BYTES of the library that is loaded: bindings size the buffer by this */
+int mirres_albedo_compact(const float* pred, const float* gt_rgba, long long n, double mask_thr, float* pool_pred, float* pool_gt, long long pool_cap,
+                          unsigned long long* state, void* scratch, void* stream);
+int mirres_albedo_median(const float* pool_pred, const float* pool_gt, long long count, double* out3, void* scratch, void* stream);
+int mirres_albedo_score(const float* pred, const float* gt_rgba, long long n, double mask_thr, const double* h_scale3, double* out_sums2,
+                        uint8_t* out_pred_u8, uint8_t* out_gt_u8, void* scratch, void* stream);
+
 /* ------------------------------------------------------------------ whole frame: run_restir_di_with_pt (renderer_restir.py:473-550) */
 typedef struct mirres_render_args {
     int spp; uint32_t random_offset; /* np.random.randint(2**20) in the reference (renderer_restir.py:245)     */

@@ -129,6 +129,10 @@ SIGNATURES = {
     "mirres_matnet_scatter": (C.c_int, [PMAT, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float), vp]),
     "mirres_matnet_bwd": (C.c_int, [PMAT, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mirres_texmat_lookup": (C.c_int, [C.POINTER(TexMat), vp, vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float), vp]),
+    "mirres_albedo_scratch_bytes": (C.c_longlong, []),
+    "mirres_albedo_compact": (C.c_int, [vp, vp, C.c_longlong, C.c_double, vp, vp, C.c_longlong, vp, vp, vp]),
+    "mirres_albedo_median": (C.c_int, [vp, vp, C.c_longlong, vp, vp, vp]),
+    "mirres_albedo_score": (C.c_int, [vp, vp, C.c_longlong, C.c_double, C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
     "mirres_ctx_reserve": (C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -155,7 +155,7 @@ def build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa=1, mlp_mat=None
 
 
 def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, random_offset=0, de=2, c=2.0, n=0.1, p=0.001, max_bounce=None,
-              albedo_scale=None, shard=None, rank=0, world=1, group=None, return_maps=False, balancer=None, gbuffer_consts=None):
+              albedo_scale=None, shard=None, rank=0, world=1, group=None, return_maps=False, balancer=None, gbuffer_consts=None, exposure=None):
     """One `--test --spp N` frame of the BRDF branch (Trainer.test_step -> render_stage1(is_test=True), nerf/renderer.py:1083-1129, 1162-1164,
     1208-1209, 1265-1302): G-buffer for the dataset camera, the fused frame (mirres_render), tone curve, alpha, SSAA down-scale, white background.
     Returns the [H, W, 3] image in [0, 1]; with `return_maps` also the dict of float maps that Trainer.test saves as EXR files (meters.write_test_maps).
@@ -165,7 +165,9 @@ def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, ran
     (sample slices + all-reduce, dist.render_sharded) with this process's `rank` of `world`; every rank returns the whole image. `balancer`: a
     dist.StripBalancer kept by the caller across the views of a run — strip boundaries then follow the strips' measured times (same pixels for any boundaries).
     `mlp_mat` may also be an export.TexturedMaterial (the exported stage-1 asset; `worker` then holds the asset's mesh): primary and indirect hits read its
-    texels.  `gbuffer_consts` = dict(kd=, roughness=, metallic=): the G-buffer constants of build_gbuffer_from_pose (pixels without a looked-up material)."""
+    texels.  `gbuffer_consts` = dict(kd=, roughness=, metallic=): the G-buffer constants of build_gbuffer_from_pose (pixels without a looked-up material).
+    `exposure` (a float: `--use_hdr --exposure E`, every relighting command of configs/OWL/*.txt): the radiance is multiplied by 2**E before the clamp to
+    [0, 1] (:1125-1127) and so is the `env_map` entry of the maps (:1343-1344); None is the path without --use_hdr."""
     from . import renderer_restir as RR
     from . import dist as MD
     from ._ops import get_ctx
@@ -182,7 +184,10 @@ def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, ran
     else:
         out = RR.render_fused(ctx, worker, mlp_mat, use_scale, scale, env_map, g["occ"].clone(), g["normal"], g["depth"], g["kd"], g["rm"], g["ray_dir"], g["pos"],
                               spp, de, 2 ** (de - 1), c, n, p, random_offset)[0]
-    img = postprocess(torch.nan_to_num(out[0], 0.0), g["occ"], H, W, ssaa)
+    final_color = torch.nan_to_num(out[0], 0.0)
+    if exposure is not None:
+        final_color = final_color * (2.0 ** float(exposure))                                                          # :1125-1126
+    img = postprocess(final_color, g["occ"], H, W, ssaa)
     if not return_maps:
         return img
     # the float maps Trainer.test writes next to the image (preds_brdf_list of render_stage1, nerf/renderer.py:1310-1330; utils.py:1372-1377): albedo, (0, roughness,
@@ -191,16 +196,29 @@ def test_view(worker, mlp_mat, env_map, pose, intrinsics, H, W, spp, ssaa=1, ran
     on = g["occ"]
     m3 = lambda x: (x * on).view(h, w, 3)
     ks = torch.cat((torch.zeros_like(g["rm"][:, :1]), g["rm"]), dim=1)
-    maps = dict(kd=m3(g["kd"]), ks=m3(ks), normal=m3(g["normal"]), env_map=env_map.detach(), rgb_diffuse_light=m3(out[1]), rgb_specular_light=m3(out[2]))
+    env_out = env_map.detach() if exposure is None else env_map.detach() * (2.0 ** float(exposure))                  # :1342-1344
+    maps = dict(kd=m3(g["kd"]), ks=m3(ks), normal=m3(g["normal"]), env_map=env_out, rgb_diffuse_light=m3(out[1]), rgb_specular_light=m3(out[2]))
     return img, maps
 
 
 test_view.__test__ = False      # not a pytest case
 
 
+def albedo_view(worker, mlp_mat, pose, intrinsics, H, W, ssaa=1, gbuffer_consts=None, background=0.0):
+    """The view's albedo [H, W, 3] without the sample loop: the G-buffer of test_view (primary hits, material lookup; `mlp_mat` may be an
+    export.TexturedMaterial), the `kd` image of render_stage1(is_test=True) (nerf/renderer.py:1252-1254) and the SSAA down-scale it gets (:1272-1274,
+    scale_img_hwc).  With `background` 0 and ssaa 1 this is maps["kd"] of test_view(..., return_maps=True) for the same view, bit for bit; the reference
+    composes the image over white (`background` 1.0, :1254), which matters only where the down-scale mixes object and background."""
+    g = build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa, mlp_mat, **(gbuffer_consts or {}))
+    kd = (g["kd"] * g["occ"]).view(g["fy"], g["fx"], 3)
+    if background != 0.0:
+        kd = kd + (1 - g["occ"]).view(g["fy"], g["fx"], 1) * float(background)
+    return scale_img_hwc(kd, (H, W))
+
+
 def render_stage1_outputs(worker, vertices, voffsets, triangles, mlp_mat, env_map, mods, H, W, spp, ssaa=1, azimuth_deg=30.0, elevation_deg=30.0,
                           jitter_std=0.01, bg_color=1.0, gb_depth=None, with_normal_ao=False, de=2, c=2.0, n=0.1, p=0.001, pose=None, intrinsics=None,
-                          topology=None, pos_gradient_boost=1.0):
+                          topology=None, pos_gradient_boost=1.0, exposure=None):
     """`render_stage1` for `--stage 1 --use_brdf --use_restir` training (nerf/renderer.py:960-1302) as far as the material / light / geometry
     branch goes: moved mesh -> BVH update -> G-buffer front half (build_gbuffer_stage1) -> jittered material taps (:1016-1022) ->
     run_restir_di_with_pt (:1112-1123) -> clamp, tone curve (:1125-1129, 1162-1164) -> dr.antialias of alpha and of every output image (:1184-1200;
@@ -208,7 +226,7 @@ def render_stage1_outputs(worker, vertices, voffsets, triangles, mlp_mat, env_ma
     reads, except `image` (the NeRF colour branch belongs to stage 0).  With a dataset camera (`pose`, `intrinsics`) the antialias step runs and the
     image loss reaches the vertex positions through visibility; with the synthetic orbit camera (no projection matrix) it is skipped.  `topology` =
     raster.antialias_topology(triangles) (built per call when None).  `gb_depth` ([N, 2]: z, |dz|; :1070-1081) selects the --use_bi_de bilateral
-    finish, None the a-trous one.  (normal_grad, which needs the perturbed-normal texture the --use_brdf path never enables, is zero)."""
+    finish, None the a-trous one.  `exposure` (a float: --use_hdr --exposure E) multiplies the radiance by 2**E before the clamp (:1125-1127).  (normal_grad, which needs the perturbed-normal texture the --use_brdf path never enables, is zero)."""
     from . import renderer_restir as RR
     from . import raster
     moved = vertices + voffsets
@@ -232,7 +250,10 @@ def render_stage1_outputs(worker, vertices, voffsets, triangles, mlp_mat, env_ma
         mods[7].process_normal_ao(framedim_x=int(fx), framedim_y=int(fy), occ_map=g["occ"], normal_map=g["normal"].detach().contiguous(), ray_dir=g["ray_dir"], out_ao=out_ao) \
             .launchRaw(blockSize=(16, 16, 1), gridSize=((int(fx) + 15) // 16, (int(fy) + 15) // 16, 1))
     alpha = g["occ"]
-    brdf_rgbs = linear2srgb(torch.clamp(torch.nan_to_num(out[0], 0.0), 0.0, 1.0))                                   # :1125-1129, 1162-1164
+    final_color = torch.nan_to_num(out[0], 0.0)
+    if exposure is not None:
+        final_color = final_color * (2.0 ** float(exposure))
+    brdf_rgbs = linear2srgb(torch.clamp(final_color, 0.0, 1.0))                                                     # :1125-1129, 1162-1164
     if "vertices_clip" in g:
         tri32 = triangles.to(torch.int32)
         topo = topology if topology is not None else raster.antialias_topology(tri32)

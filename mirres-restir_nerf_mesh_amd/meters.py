@@ -17,7 +17,7 @@ import zlib
 import numpy as np
 import torch
 
-__all__ = ["PSNRMeter", "SSIMMeter", "LPIPSMeter", "LPIPS", "ssim", "to_uint8", "write_png", "write_test_frame"]
+__all__ = ["PSNRMeter", "SSIMMeter", "LPIPSMeter", "LPIPS", "ssim", "ssim_script", "to_uint8", "write_png", "write_test_frame"]
 
 
 class PSNRMeter:
@@ -61,6 +61,30 @@ def ssim(preds, truths, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03, data_range=
     spp, stt, spt = f(p * p) - mp * mp, f(t * t) - mt * mt, f(p * t) - mp * mt
     m = ((2 * mp * mt + c1) * (2 * spt + c2)) / ((mp * mp + mt * mt + c1) * (spp + stt + c2))
     return m.reshape(m.shape[0], -1).mean(-1).mean()
+
+
+def ssim_script(preds, truths, data_range=1.0, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """The SSIM variant the reference's albedo_eval.py scores the aligned albedo with (its `rgb_ssim`), which is NOT `ssim` above.  Two [H, W, 3] images;
+    the same Gaussian window as `ssim` (centred at (kernel_size - 1) / 2, normalised), but applied separably — down the columns, then along the rows — at the
+    positions where it lies fully inside the image; a fixed `data_range` for the two constants; and two guards `ssim` does not have: a local variance below 0
+    (rounding) counts as 0, and the local covariance is limited in magnitude to the geometric mean of the two variances, keeping its sign.  Mean over all
+    window positions and channels.  Evaluated in float64 (one 800^2 image per view: not a hot path)."""
+    if preds.shape != truths.shape or preds.dim() != 3 or preds.shape[-1] != 3:
+        raise ValueError("ssim_script: expected two [H, W, 3] tensors of one shape")
+    if min(preds.shape[:2]) < kernel_size:
+        raise ValueError("ssim_script: image smaller than the %d-tap window" % kernel_size)
+    p, t = (z.to(torch.float64).permute(2, 0, 1)[:, None] for z in (preds, truths))        # [3, 1, H, W]: every channel is its own image
+    x = torch.arange(kernel_size, dtype=torch.float64, device=p.device) - (kernel_size - 1) / 2
+    g = torch.exp(-(x / sigma) ** 2 / 2); g = g / g.sum()
+    col, row = g.view(1, 1, kernel_size, 1), g.view(1, 1, 1, kernel_size)
+    f = lambda z: torch.nn.functional.conv2d(torch.nn.functional.conv2d(z, col), row)
+    mp, mt = f(p), f(t)
+    spp, stt = torch.clamp(f(p * p) - mp * mp, min=0.0), torch.clamp(f(t * t) - mt * mt, min=0.0)
+    spt = f(p * t) - mp * mt
+    spt = torch.sign(spt) * torch.minimum(spt.abs(), torch.sqrt(spp * stt))
+    c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
+    m = ((2 * mp * mt + c1) * (2 * spt + c2)) / ((mp * mp + mt * mt + c1) * (spp + stt + c2))
+    return m.mean()
 
 
 class SSIMMeter:
@@ -261,11 +285,30 @@ def write_exr(path, img):
     return path
 
 
+_EXR_COMPRESSION = ("NONE", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB")
+_EXR_LINES = {0: 1, 2: 1, 3: 16}                  # scan lines per chunk of the compressions read here
+
+
+def _exr_unzip(chunk):
+    """ZIP / ZIPS chunk -> raw bytes: zlib, then the format's predictor (each byte is the difference to the one before it, biased by 128) and the byte
+    interleave (first half -> even positions, second half -> odd positions)."""
+    t = np.frombuffer(zlib.decompress(chunk), np.uint8).astype(np.int64)
+    t = ((np.cumsum(t) - 128 * np.arange(t.size)) & 255).astype(np.uint8)
+    out = np.empty(t.size, np.uint8)
+    half = (t.size + 1) // 2
+    out[0::2] = t[:half]; out[1::2] = t[half:]
+    return out
+
+
 def read_exr(path):
-    """Reads back what write_exr wrote (uncompressed scan lines, FLOAT channels) -> float32 [H, W, C] in R, G, B (A) / Y order."""
+    """Single-part scan-line OpenEXR -> float32 [H, W, C] in R, G, B (A) / Y order: what write_exr wrote (uncompressed FLOAT) and what Blender writes for
+    the TensoIR ground truth (`test_XXX/diffuse-color.exr`: RGBA, ZIP): compression NONE, ZIPS and ZIP, channel types HALF and FLOAT.  Every other
+    compression raises ValueError naming it."""
     b = open(path, "rb").read()
     if struct.unpack_from("<i", b, 0)[0] != 20000630:
         raise ValueError("%s: not an OpenEXR file" % path)
+    if struct.unpack_from("<i", b, 4)[0] & 0x1A00:
+        raise ValueError("%s: tiled, deep or multi-part files are not read (scan-line single-part only)" % path)
     p, attrs = 8, {}
     while b[p] != 0:
         e = b.index(b"\0", p); name = b[p:e].decode(); p = e + 1
@@ -273,20 +316,36 @@ def read_exr(path):
         n = struct.unpack_from("<i", b, p)[0]; p += 4
         attrs[name] = (typ, b[p:p + n]); p += n
     p += 1
-    if attrs["compression"][1] != b"\0":
-        raise ValueError("%s: only uncompressed files (as write_exr makes them)" % path)
+    comp = attrs["compression"][1][0]
+    if comp not in _EXR_LINES:
+        raise ValueError("%s: %s compression is not read (NONE, ZIPS and ZIP are)" % (path, _EXR_COMPRESSION[comp] if comp < len(_EXR_COMPRESSION) else "unknown (%d)" % comp))
     x0, y0, x1, y1 = struct.unpack("<iiii", attrs["dataWindow"][1]); w, h = x1 - x0 + 1, y1 - y0 + 1
-    ch, q, cl = [], 0, attrs["channels"][1]
+    ch, types, q, cl = [], [], 0, attrs["channels"][1]
     while cl[q] != 0:
         e = cl.index(b"\0", q); nm = cl[q:e].decode(); q = e + 1
-        if struct.unpack_from("<i", cl, q)[0] != 2:
-            raise ValueError("%s: only FLOAT channels" % path)
-        ch.append(nm); q += 16
-    offs = struct.unpack_from("<%dQ" % h, b, p)
+        pt = struct.unpack_from("<i", cl, q)[0]
+        if pt not in (1, 2):
+            raise ValueError("%s: channel %s is neither HALF nor FLOAT" % (path, nm))
+        if struct.unpack_from("<ii", cl, q + 8) != (1, 1):
+            raise ValueError("%s: channel %s is subsampled" % (path, nm))
+        ch.append(nm); types.append(np.dtype("<f2") if pt == 1 else np.dtype("<f4")); q += 16
+    line_bytes = w * sum(t.itemsize for t in types)
+    lines = _EXR_LINES[comp]
+    n_chunks = (h + lines - 1) // lines
+    offs = struct.unpack_from("<%dQ" % n_chunks, b, p)
     out = np.zeros((h, w, len(ch)), np.float32)
-    for y in range(h):
-        yy, nb = struct.unpack_from("<ii", b, offs[y])
-        out[yy - y0] = np.frombuffer(b, np.float32, w * len(ch), offs[y] + 8).reshape(len(ch), w).T
+    for k in range(n_chunks):
+        yy, nb = struct.unpack_from("<ii", b, offs[k])
+        rows = min(lines, y1 - yy + 1)
+        raw = np.frombuffer(b, np.uint8, nb, offs[k] + 8)
+        if comp != 0 and nb < rows * line_bytes:           # a chunk that did not shrink is stored as it is
+            raw = _exr_unzip(raw.tobytes())
+        if raw.size != rows * line_bytes:
+            raise ValueError("%s: the chunk at line %d holds %d bytes, %d expected" % (path, yy, raw.size, rows * line_bytes))
+        at = 0
+        for r in range(rows):                              # per scan line: its channels one after the other, in the file's (alphabetical) order
+            for c, t in enumerate(types):
+                out[yy - y0 + r, :, c] = np.frombuffer(raw, t, w, at); at += w * t.itemsize
     want = [n for n in ("R", "G", "B", "A", "Y") if n in ch]
     return out[:, :, [ch.index(n) for n in want]]
 

@@ -20,7 +20,10 @@ The material-field constants are the reference's CLI ones and MUST equal the tra
 this package record them (`material_config`); a flag given on the command line wins, a mismatch with the recorded value is reported.
 
 Relighting (reference: `--test --envmap_path X.hdr --albedo_scale_x/y/z`, nerf/network.py:134-139, nerf/renderer.py:1025-1026, 1086-1089, 1109-1111):
-`--envmap_path` replaces the trained environment map by a Radiance .hdr file (any size) and switches the albedo scaling on.
+`--envmap_path` replaces the trained environment map by a Radiance .hdr file (any size) and switches the albedo scaling on.  The three scales are what
+`scripts/albedo_eval.py` measures (the reference's albedo_eval.py); `--albedo_scale_file <its albedo_scale.json>` passes them on without retyping.
+`--use_hdr --exposure E` (every relighting command of configs/OWL/*.txt): radiance x 2**E before the clamp (nerf/renderer.py:1125-1127), and the saved
+env_map scaled alike (:1343-1344).
 
 Several GPUs (`python -m torch.distributed.run --nproc-per-node N scripts/evaluate.py ... --shard views|strips|spp`): `views` (default) deals the
 dataset views round-robin to the ranks — no data-path communication, metrics reduced at the end; `strips` / `spp` render EVERY view on all ranks
@@ -69,7 +72,7 @@ def synthetic_workspace(root, H=100, W=100):
     return ck, tf
 
 
-def main():
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--workspace"); p.add_argument("--ckpt"); p.add_argument("--transforms"); p.add_argument("--out")
     p.add_argument("--spp", type=int, default=512); p.add_argument("--ssaa", type=int, default=2); p.add_argument("--downscale", type=int, default=1)
@@ -82,7 +85,11 @@ def main():
     p.add_argument("--save_maps", action="store_true", help="also write kd / ks / normal / env_map / diffuse and specular light as EXR files, like Trainer.test (nerf/utils.py:1372-1377)")
     p.add_argument("--scale", type=float, default=1.0); p.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0]); p.add_argument("--synthetic", action="store_true")
     p.add_argument("--envmap_path", default="None", help="main.py --envmap_path: Radiance .hdr environment map for relighting")
-    p.add_argument("--albedo_scale_x", type=float, default=1.0); p.add_argument("--albedo_scale_y", type=float, default=1.0); p.add_argument("--albedo_scale_z", type=float, default=1.0)
+    p.add_argument("--albedo_scale_x", type=float, default=None, help="default 1.0"); p.add_argument("--albedo_scale_y", type=float, default=None, help="default 1.0")
+    p.add_argument("--albedo_scale_z", type=float, default=None, help="default 1.0")
+    p.add_argument("--albedo_scale_file", default=None, help="albedo_scale.json of scripts/albedo_eval.py: fills the three scales (not together with --albedo_scale_x/y/z)")
+    p.add_argument("--use_hdr", action="store_true", help="main.py --use_hdr (the relighting commands of configs/OWL/*.txt): radiance and the saved env_map x 2**exposure")
+    p.add_argument("--exposure", type=float, default=0.0, help="main.py --exposure, read with --use_hdr")
     p.add_argument("--shard", choices=("views", "strips", "spp"), default="views", help="how N > 1 ranks (torch.distributed.run) divide the work")
     p.add_argument("--lpips_vgg", default=None, help="torchvision vgg16 state dict (or a state dict of lpips.LPIPS): adds the reference's LPIPS (vgg) meter; no weights ship with the image")
     p.add_argument("--lpips_lin", default=None, help="the lpips package's weights/v0.1/vgg.pth (the five linear heads)")
@@ -90,7 +97,31 @@ def main():
     p.add_argument("--texture_size", type=int, default=4096, help="main.py --texture_size: texture side of the first cascade of --export_mesh (baked at --ssaa)")
     p.add_argument("--textured_mesh", default=None, help="render the views from this exported stage-1 asset (mesh_{cas}.obj, feat0/feat1_{cas}.png|.jpg); with "
                    "--ckpt also report each textured frame's PSNR against the field's frame")
-    a = p.parse_args()
+    return p
+
+
+def parse_args(argv=None):
+    """-> (args, parser); a.albedo_scale_x/y/z are floats afterwards (from the command line, from --albedo_scale_file, or 1.0) and a.exposure is the
+    float harness.test_view takes, or None without --use_hdr."""
+    p = build_parser()
+    a = p.parse_args(argv)
+    typed = [k for k in "xyz" if getattr(a, "albedo_scale_" + k) is not None]
+    if a.albedo_scale_file is not None:
+        if typed:
+            p.error("--albedo_scale_file and --albedo_scale_%s are two sources for one number: give one" % "/".join(typed))
+        from mirres_restir_nerf_mesh_amd import albedo
+        a.albedo_scale_x, a.albedo_scale_y, a.albedo_scale_z = albedo.read_scale(a.albedo_scale_file)["scale"]
+    if a.albedo_scale_file is not None and a.envmap_path == "None":
+        p.error("--albedo_scale_file is read for relighting only: give --envmap_path (without it the albedo is not scaled)")
+    for k in "xyz":
+        if getattr(a, "albedo_scale_" + k) is None:
+            setattr(a, "albedo_scale_" + k, 1.0)
+    a.exposure = a.exposure if a.use_hdr else None
+    return a, p
+
+
+def main():
+    a, p = parse_args()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
     if world > 1:
@@ -148,7 +179,7 @@ def main():
         n_mine += 1
         pose = nerf_pose(fr["transform_matrix"], a.scale, a.offset)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        img = harness.test_view(W, mlp, light, torch.from_numpy(pose), intr, Hh, Ww, a.spp, a.ssaa, random_offset=i * 7919, albedo_scale=albedo_scale,
+        img = harness.test_view(W, mlp, light, torch.from_numpy(pose), intr, Hh, Ww, a.spp, a.ssaa, random_offset=i * 7919, albedo_scale=albedo_scale, exposure=a.exposure,
                                 shard=a.shard if world > 1 and a.shard != "views" else None, rank=rank, world=world, return_maps=a.save_maps, balancer=balancer)
         maps = None
         if a.save_maps:
@@ -208,7 +239,7 @@ def render_textured(a, frames, base, intr, Hh, Ww, light, albedo_scale, out_dir,
         if world > 1 and a.shard == "views" and i % world != rank:
             continue
         pose = nerf_pose(fr["transform_matrix"], a.scale, a.offset)
-        img = harness.test_view(Wt, tex, light, torch.from_numpy(pose), intr, Hh, Ww, a.spp, a.ssaa, random_offset=i * 7919, albedo_scale=albedo_scale,
+        img = harness.test_view(Wt, tex, light, torch.from_numpy(pose), intr, Hh, Ww, a.spp, a.ssaa, random_offset=i * 7919, albedo_scale=albedo_scale, exposure=a.exposure,
                                 shard=shard, rank=rank, world=world)
         if world > 1 and shard is not None and rank != 0:
             continue

@@ -73,6 +73,7 @@ def main():
     p.add_argument("--mesh_error", type=float, default=0.0, help="--synthetic: relative error of the starting mesh against the one the images show")
     p.add_argument("--freeze", nargs="*", default=[], choices=["geometry", "material", "light"], help="parameter groups left untouched (their learning rate set to 0)")
     p.add_argument("--pos_gradient_boost", type=float, default=1.0); p.add_argument("--lambda_extra_kd", type=float, default=0.0); p.add_argument("--quiet", action="store_true")
+    p.add_argument("--use_hdr", action="store_true", help="main.py --use_hdr: radiance x 2**exposure before the clamp (nerf/renderer.py:1125-1127)"); p.add_argument("--exposure", type=float, default=0.0)
     a = p.parse_args()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
@@ -173,7 +174,7 @@ def main():
         pose, (gt, gt_lin) = data[int(order[k]) if world == 1 else k]
         for o in (o_geo, o_mat, o_lgt): o.zero_grad(set_to_none=True)
         out = harness.render_stage1_outputs(Wk, verts, voff, tris, mlp, env, mods, H, Wd, a.spp, a.ssaa, pose=pose, intrinsics=intr, topology=topo,
-                                            pos_gradient_boost=a.pos_gradient_boost, with_normal_ao=a.lambda_extra_kd > 0)
+                                            pos_gradient_boost=a.pos_gradient_boost, with_normal_ao=a.lambda_extra_kd > 0, exposure=a.exposure if a.use_hdr else None)
         loss = losses.stage1_loss(out, gt, gt_lin, opt, vertices=verts, voffsets=voff, triangles=tris)
         val = losses.stage1_optimizer_step(loss, o_geo, o_mat, o_lgt, light_base=env, encoder_params=mlp.encoder.params, scheduler=s_geo, scheduler_mat=s_mat,
                                            scheduler_light=s_lgt, grad_sync=sync)
