@@ -420,6 +420,42 @@ int mirres_selfcheck_arith(int log2_b, unsigned long long out[4], void* stream);
 int mirres_fmath_eval(int fn, const float* a, const float* b, float* out, long long n, void* stream);
 int mirres_fmath_checksum(int fn, unsigned int first, unsigned long long count, unsigned long long* out, void* stream);
 
+/* ------------------------------------------------------------------ stage-0 mesh extraction (NeRFRenderer.export_stage0, nerf/renderer.py:498-570)
+ * Marching cubes over a dense volume vol f32[nx][ny][nz] (every size >= 2, at most 2^31 - 1 points) — mcubes.marching_cubes(sigmas, density_thresh),
+ * renderer.py:549-555 — as an indexed mesh: vertices f32[V,3] in index space (the caller maps them with v / (res - 1) * 2 - 1, :553) and triangles
+ * i32[T,3].  Non-finite values count as torch.nan_to_num(., 0) makes them (:541); a corner is inside when value >= iso; triangles are wound so that the
+ * normal points towards decreasing values (for --sdf the caller passes -vol and iso 0, :549).  Every crossed grid edge carries exactly ONE vertex, at
+ * float(i) + clamp((iso - va) / (vb - va), 0, 1) along the edge (va at the lower grid point), numbered in (grid point, axis) order; triangles are numbered in
+ * (cell, case table) order: equal inputs give equal bytes.  The 256 cases are generated (scripts/gen_mc_table.py; ambiguous faces SEPARATE their inside corners).
+ * mirres_mc_count (renderer.py:549-555): classifies, scans, returns h_counts = {V, T}; BLOCKS until the counts are on the host.  `scratch`: mirres_mc_scratch_bytes
+ * device bytes (2 per grid point + 8 per 256 points), handed unchanged to mirres_mc_emit (renderer.py:549-555) together with the same volume and iso; V = T = 0
+ * (no crossing) is a success and launches nothing.                                                                                                  */
+long long mirres_mc_scratch_bytes(int nx, int ny, int nz);
+int mirres_mc_count(const float* vol, int nx, int ny, int nz, float iso, void* scratch, long long scratch_bytes, int* h_counts, void* stream);
+int mirres_mc_emit(const float* vol, int nx, int ny, int nz, float iso, const void* scratch, float* verts, int V, int32_t* tris, int T, void* stream);
+/* renderer.py:511-515: cascade 0 of density_grid (S^3 values in Morton order, raymarching.cu:73-81: x from bits 0, 3, 6, ..., y from >> 1, z from >> 2; S a power of two
+ * <= 1024) -> vol f32[S][S][S].  renderer.py:532-539: vol f32[R][R][R] *= (grid_vol[S][S][S] upsampled by F.interpolate(mode='nearest') > thresh).          */
+int mirres_mc_unpack_morton(const float* grid, int S, float* vol, void* stream);
+int mirres_mc_mask_nearest(float* vol, int R, const float* grid_vol, int S, float thresh, void* stream);
+/* mark_unseen_triangles (renderer.py:1421-1427): seen[id - 1] = 1 for the triangle id (+ 1, fourth component) of every pixel of rast f32[n,4]; id 0 (background)
+ * marks nothing — the reference's mask[-1] += 1 for background pixels is not reproduced.  seen u8[T] is the caller's, cleared by the caller. */
+int mirres_mesh_mark_seen(const float* rast, long long n, int T, uint8_t* seen, void* stream);
+/* One ring of apply_selection_dilatation (meshutils.py:113-114): a vertex is selected when a selected face uses it (vert_flags u8[V], scratch, cleared inside),
+ * then face_out[f] = any of its vertices selected.  face_in and face_out (u8[T]) are different buffers.                                                       */
+int mirres_mesh_dilate(const int32_t* tris, int T, int V, const uint8_t* face_in, uint8_t* vert_flags, uint8_t* face_out, void* stream);
+/* meshing_remove_selected_faces + meshing_remove_unreferenced_vertices (meshutils.py:118-121, :195): keeps the faces with keep_face[f] != 0 and the vertices they
+ * use, both in their old order, indices remapped.  out_verts f32[V,3] / out_tris i32[T,3] are sized for the input; h_counts = {V', T'}; BLOCKS.  `scratch`:
+ * mirres_mesh_scratch_bytes(V, T) device bytes.                                                                                                               */
+long long mirres_mesh_scratch_bytes(int V, int T);
+int mirres_mesh_compact(const float* verts, int V, const int32_t* tris, int T, const uint8_t* keep_face, float* out_verts, int32_t* out_tris, void* scratch,
+                        int* h_counts, void* stream);
+/* Connected components over faces that share an EDGE (MeshLab's face-face topology behind meshing_remove_connected_component_by_*, meshutils.py:203-207):
+ * sorted_keys u64[n_keys] = the undirected edge keys of all faces in ascending order, key_face i32[n_keys] = the face each belongs to; neighbours in the sorted
+ * list with equal keys are joined.  label i32[T] = the smallest face index of the face's component.  Rounds of hooking (atomicMin) + pointer jumping, the host
+ * re-launching while the device flag `changed_flag` (i32[1]) is set; max_rounds = 0 means the cap of 64, past which the call returns MIRRES_E_STATE. BLOCKS. */
+int mirres_mesh_components(const unsigned long long* sorted_keys, const int32_t* key_face, long long n_keys, int T, int32_t* label, int32_t* changed_flag,
+                           int max_rounds, int* h_rounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

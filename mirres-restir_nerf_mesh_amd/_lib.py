@@ -133,6 +133,16 @@ SIGNATURES = {
     "mirres_albedo_compact": (C.c_int, [vp, vp, C.c_longlong, C.c_double, vp, vp, C.c_longlong, vp, vp, vp]),
     "mirres_albedo_median": (C.c_int, [vp, vp, C.c_longlong, vp, vp, vp]),
     "mirres_albedo_score": (C.c_int, [vp, vp, C.c_longlong, C.c_double, C.POINTER(C.c_double), vp, vp, vp, vp, vp]),
+    "mirres_mc_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "mirres_mc_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32, vp, C.c_longlong, C.POINTER(C.c_int), vp]),
+    "mirres_mc_emit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32, vp, vp, C.c_int, vp, C.c_int, vp]),
+    "mirres_mc_unpack_morton": (C.c_int, [vp, C.c_int, vp, vp]),
+    "mirres_mc_mask_nearest": (C.c_int, [vp, C.c_int, vp, C.c_int, f32, vp]),
+    "mirres_mesh_mark_seen": (C.c_int, [vp, C.c_longlong, C.c_int, vp, vp]),
+    "mirres_mesh_dilate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "mirres_mesh_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "mirres_mesh_compact": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+    "mirres_mesh_components": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int), vp]),
     "mirres_ctx_reserve": (C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,0 +1,312 @@
+"""Stage-0 mesh extraction (NeRFRenderer.export_stage0, nerf/renderer.py:498-570; csrc/mcubes.hip): from a stage-0 checkpoint's density grid, a dumped
+sigma / SDF volume or a foreign mesh to the `<workspace>/mesh_stage0/mesh_0.ply` every stage-1 tool starts from, with no PyMCubes / pymeshlab / trimesh /
+nvdiffrast behind it.
+
+    v, t = marching_cubes(vol, iso)                        # mcubes.marching_cubes (:549-555): index-space vertices, welded, deterministic
+    vol = unpack_density_grid(ck["model"]["density_grid"]) # :511-515, cascade 0, Morton order -> [S, S, S]
+    unseen = mark_unseen_triangles(v, t, mvps, H, W)       # :1400-1434 on raster.rasterize
+    v, t = remove_masked_trigs(v, t, unseen, dilation=5)   # meshutils.py:100-130
+    v, t = clean_mesh(v, t, min_f=8, min_d=5)              # meshutils.py:183-225 (repair=True, remesh=False)
+    export_stage0(save_path, ckpt=..., cameras=(mvps, H, W))
+
+Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
+when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair, remeshing and decimation are not built.
+Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import lib, check, ptr, stream_ptr
+
+__all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
+           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "index_to_world", "synthetic_volume", "export_stage0"]
+
+
+def _dev():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _verts(v):
+    return torch.as_tensor(v).to(_dev(), torch.float32).reshape(-1, 3).contiguous()
+
+
+def _tris(t):
+    return torch.as_tensor(t).to(_dev(), torch.int32).reshape(-1, 3).contiguous()
+
+
+def marching_cubes(vol, iso):
+    """vol f32 [nx, ny, nz] (tensor or numpy), iso -> (vertices f32 [V, 3] in index space, triangles i32 [T, 3]); inside = vol >= iso, normals towards
+    decreasing values, non-finite values as torch.nan_to_num(., 0).  V = T = 0 when nothing crosses."""
+    vol = torch.as_tensor(vol).to(_dev(), torch.float32).contiguous()
+    if vol.dim() != 3:
+        raise ValueError("marching_cubes: expected a 3-D volume, got %s" % (tuple(vol.shape),))
+    nx, ny, nz = (int(s) for s in vol.shape)
+    L = lib()
+    nbytes = int(L.mirres_mc_scratch_bytes(nx, ny, nz))
+    if nbytes < 0:
+        check(nbytes, "mirres_mc_scratch_bytes")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    counts = (C.c_int * 2)()
+    check(L.mirres_mc_count(ptr(vol), nx, ny, nz, float(iso), ptr(scratch), nbytes, counts, stream_ptr()), "mirres_mc_count")
+    V, T = int(counts[0]), int(counts[1])
+    verts = torch.empty((V, 3), dtype=torch.float32, device=vol.device); tris = torch.empty((T, 3), dtype=torch.int32, device=vol.device)
+    check(L.mirres_mc_emit(ptr(vol), nx, ny, nz, float(iso), ptr(scratch), ptr(verts) if V else None, V, ptr(tris) if T else None, T, stream_ptr()), "mirres_mc_emit")
+    return verts, tris
+
+
+def morton_indices(S):
+    """i64 [S, S, S]: the Morton index of grid point (x, y, z) — x in bits 0, 3, 6, ..., y in bits 1, 4, ..., z in bits 2, 5, ... (raymarching.cu:73-81)."""
+    S = int(S)
+    if S < 2 or S & (S - 1) or S > 1024:
+        raise ValueError("grid size %d is not a power of two in [2, 1024]" % S)
+    a = np.arange(S, dtype=np.int64)
+    s = np.zeros(S, np.int64)
+    for b in range(10):
+        s |= ((a >> b) & 1) << (3 * b)
+    return s[:, None, None] | (s[None, :, None] << 1) | (s[None, None, :] << 2)
+
+
+def unpack_density_grid(density_grid, cascade=0):
+    """density_grid [cascade, S^3] (or [S^3]) in Morton order -> vol f32 [S, S, S] of one cascade on the device (nerf/renderer.py:511-515)."""
+    g = torch.as_tensor(density_grid).to(_dev(), torch.float32)
+    g = g.reshape(1, -1) if g.dim() == 1 else g
+    n = int(g.shape[1]); S = int(round(n ** (1.0 / 3.0)))
+    if S * S * S != n:
+        raise ValueError("density_grid: %d values per cascade is not a cube" % n)
+    row = g[int(cascade)].contiguous()
+    vol = torch.empty((S, S, S), dtype=torch.float32, device=row.device)
+    check(lib().mirres_mc_unpack_morton(ptr(row), S, ptr(vol), stream_ptr()), "mirres_mc_unpack_morton")
+    return vol
+
+
+def select_iso(mean_density, density_thresh=10.0):
+    """nerf/renderer.py:506."""
+    return min(float(mean_density), float(density_thresh))
+
+
+def mask_by_density_grid(vol, grid_vol, thresh):
+    """nerf/renderer.py:532-539: vol [R, R, R] * (F.interpolate(grid_vol [S, S, S], mode='nearest') > thresh); returns a new tensor."""
+    out = torch.as_tensor(vol).to(_dev(), torch.float32).contiguous().clone(); g = torch.as_tensor(grid_vol).to(_dev(), torch.float32).contiguous()
+    if out.dim() != 3 or len(set(out.shape)) != 1 or g.dim() != 3 or len(set(g.shape)) != 1:
+        raise ValueError("mask_by_density_grid: cubic volumes expected, got %s and %s" % (tuple(out.shape), tuple(g.shape)))
+    check(lib().mirres_mc_mask_nearest(ptr(out), int(out.shape[0]), ptr(g), int(g.shape[0]), float(thresh), stream_ptr()), "mirres_mc_mask_nearest")
+    return out
+
+
+def index_to_world(vertices, resolution):
+    """nerf/renderer.py:553; `resolution` an int or one per axis."""
+    r = torch.as_tensor(resolution, dtype=torch.float32, device=vertices.device)
+    return (vertices / (r - 1.0) * 2 - 1).to(torch.float32)
+
+
+@torch.no_grad()
+def seen_faces(vertices, triangles, mvps, H, W):
+    """u8 [T]: 1 for every face whose id appears in raster.rasterize's output of some view (mvps [B, 4, 4]); background marks nothing.  The BVH is built once."""
+    from . import raster
+    from .renderer_restir import restirbvhWorker
+    v, t = _verts(vertices), _tris(triangles)
+    T = int(t.shape[0])
+    seen = torch.zeros(T, dtype=torch.uint8, device=v.device)
+    if T == 0:
+        return seen
+    worker = restirbvhWorker(v, t); worker.update_mesh(v, t)
+    ctx = raster.RasterizeContext(worker)
+    vh = torch.nn.functional.pad(v, (0, 1), value=1.0)
+    for mvp in mvps:
+        mvp = torch.as_tensor(mvp).to(v.device, torch.float32)
+        rast, _ = raster.rasterize(ctx, (vh @ mvp.t())[None], t, (int(H), int(W)), grad_db=False, mvp=mvp)
+        rast = rast.reshape(-1, 4)
+        check(lib().mirres_mesh_mark_seen(ptr(rast), int(rast.shape[0]), T, ptr(seen), stream_ptr()), "mirres_mesh_mark_seen")
+    return seen
+
+
+def mark_unseen_triangles(vertices, triangles, mvps, H, W, log=None):
+    """nerf/renderer.py:1400-1434 -> bool [T], True = seen by no camera."""
+    mask = seen_faces(vertices, triangles, mvps, H, W) == 0
+    if log:
+        log("[mark unseen trigs] %d from %d" % (int(mask.sum()), mask.shape[0]))
+    return mask
+
+
+def dilate_selection(triangles, n_vertices, selected, rings):
+    """`rings` rings of MeshLab's apply_selection_dilatation on a face selection (u8 / bool [T]) -> u8 [T]."""
+    t = _tris(triangles); T = int(t.shape[0]); V = int(n_vertices)
+    a = torch.as_tensor(selected).to(t.device).ne(0).to(torch.uint8).contiguous()
+    if a.shape[0] != T:
+        raise ValueError("dilate_selection: %d flags for %d faces" % (a.shape[0], T))
+    b = torch.empty_like(a); vf = torch.empty(max(V, 1), dtype=torch.uint8, device=t.device)
+    for _ in range(int(rings)):
+        check(lib().mirres_mesh_dilate(ptr(t), T, V, ptr(a), ptr(vf), ptr(b), stream_ptr()), "mirres_mesh_dilate")
+        a, b = b, a
+    return a
+
+
+def compact_mesh(vertices, triangles, keep_face=None):
+    """Keeps the faces with keep_face != 0 (None: all) and the vertices they use, in their old order."""
+    v, t = _verts(vertices), _tris(triangles)
+    V, T = int(v.shape[0]), int(t.shape[0])
+    keep = torch.ones(T, dtype=torch.uint8, device=v.device) if keep_face is None else torch.as_tensor(keep_face).to(v.device).ne(0).to(torch.uint8).contiguous()
+    if keep.shape[0] != T:
+        raise ValueError("compact_mesh: %d flags for %d faces" % (keep.shape[0], T))
+    if T and (int(t.min()) < 0 or int(t.max()) >= V):
+        raise ValueError("compact_mesh: face index out of range")
+    L = lib()
+    nbytes = int(L.mirres_mesh_scratch_bytes(V, T))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+    ov = torch.empty_like(v); ot = torch.empty_like(t)
+    counts = (C.c_int * 2)()
+    check(L.mirres_mesh_compact(ptr(v), V, ptr(t), T, ptr(keep), ptr(ov), ptr(ot), ptr(scratch), counts, stream_ptr()), "mirres_mesh_compact")
+    return ov[: counts[0]].contiguous(), ot[: counts[1]].contiguous()
+
+
+def remove_masked_trigs(vertices, triangles, mask, dilation=5, log=None):
+    """meshutils.py:100-130: mask 0 = keep, 1 = remove; the kept selection is dilated `dilation` rings before its complement is deleted."""
+    v, t = _verts(vertices), _tris(triangles)
+    keep = dilate_selection(t, v.shape[0], torch.as_tensor(mask).to(v.device).eq(0), dilation)
+    ov, ot = compact_mesh(v, t, keep)
+    if log:
+        log("[INFO] mesh mask trigs: %s --> %s, %s --> %s" % (tuple(v.shape), tuple(ov.shape), tuple(t.shape), tuple(ot.shape)))
+    return ov, ot
+
+
+def face_components(triangles, max_rounds=0):
+    """(labels i32 [T], rounds): the smallest face index of every face's component, components joined across shared EDGES (not shared vertices).
+    `max_rounds` (0: the library's cap of 64) bounds the hook / jump rounds; past it MirresError is raised."""
+    t = _tris(triangles); T = int(t.shape[0])
+    label = torch.empty(T, dtype=torch.int32, device=t.device)
+    if T == 0:
+        return label, 0
+    t64 = t.to(torch.int64)
+    a = t64.reshape(-1); b = t64[:, [1, 2, 0]].reshape(-1)                      # entry 3 f + k: edge (v_k, v_k+1) of face f
+    keys, order = torch.sort((torch.minimum(a, b) << 32) | torch.maximum(a, b), stable=True)
+    face = (order // 3).to(torch.int32).contiguous(); keys = keys.contiguous()
+    flag = torch.zeros(1, dtype=torch.int32, device=t.device)
+    rounds = C.c_int(0)
+    check(lib().mirres_mesh_components(ptr(keys), ptr(face), int(keys.shape[0]), T, ptr(label), ptr(flag), int(max_rounds), C.byref(rounds), stream_ptr()), "mirres_mesh_components")
+    return label, rounds.value
+
+
+def _first_of_group(inverse, n_groups):
+    idx = torch.arange(inverse.shape[0], device=inverse.device)
+    return torch.full((n_groups,), inverse.shape[0], dtype=torch.int64, device=inverse.device).scatter_reduce(0, inverse, idx, "amin")
+
+
+def clean_mesh(vertices, triangles, min_f=8, min_d=5, max_rounds=0, log=None):
+    """meshutils.py:183-225 with repair=True, remesh=False, in the reference's order: unreferenced vertices, duplicate vertices (bit-identical coordinates, lowest
+    index kept), duplicate faces (same vertex set, first kept) and null faces (a repeated index or an exactly zero cross product), components (shared edges)
+    whose bounding-box diagonal is below min_d % of the mesh's, components with fewer than min_f faces.  Order is preserved throughout."""
+    v0, t0 = _verts(vertices), _tris(triangles)
+    v, t = compact_mesh(v0, t0)
+    if v.shape[0]:
+        uniq, inv = torch.unique(v.view(torch.int32), dim=0, return_inverse=True)
+        rep = _first_of_group(inv, uniq.shape[0])[inv]
+        t = rep[t.to(torch.int64)].to(torch.int32)
+    if t.shape[0]:
+        s = torch.sort(t, dim=1).values
+        uniq, inv = torch.unique(s, dim=0, return_inverse=True)
+        keep = _first_of_group(inv, uniq.shape[0])[inv] == torch.arange(t.shape[0], device=t.device)
+        p = v[t.to(torch.int64)]
+        cross = torch.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], dim=-1)
+        null = (s[:, 0] == s[:, 1]) | (s[:, 1] == s[:, 2]) | (cross == 0).all(dim=1)
+        v, t = compact_mesh(v, t, keep & ~null)
+    else:
+        v, t = compact_mesh(v, t)
+    if t.shape[0] and (min_d > 0 or min_f > 0):
+        label, _ = face_components(t, max_rounds)
+        lab = label.to(torch.int64); T = t.shape[0]
+        keep = torch.ones(T, dtype=torch.bool, device=t.device)
+        if min_d > 0:
+            p = v[t.to(torch.int64)].double()                                           # [T, 3, 3]
+            lo = torch.full((T, 3), float("inf"), dtype=torch.float64, device=t.device).scatter_reduce(0, lab[:, None].expand(T, 3), p.amin(dim=1), "amin")
+            hi = torch.full((T, 3), float("-inf"), dtype=torch.float64, device=t.device).scatter_reduce(0, lab[:, None].expand(T, 3), p.amax(dim=1), "amax")
+            diag = (hi - lo).square().sum(dim=1).sqrt()                                   # per label (rows of non-labels hold inf - -inf)
+            whole = (v.double().amax(dim=0) - v.double().amin(dim=0)).square().sum().sqrt()
+            keep &= ~(diag[lab] < whole * (float(min_d) / 100.0))
+        if min_f > 0:
+            size = torch.zeros(T, dtype=torch.int64, device=t.device).index_add_(0, lab, torch.ones(T, dtype=torch.int64, device=t.device))
+            keep &= size[lab] >= int(min_f)
+        v, t = compact_mesh(v, t, keep)
+    if log:
+        log("[INFO] mesh cleaning: %s --> %s, %s --> %s" % (tuple(v0.shape), tuple(v.shape), tuple(t0.shape), tuple(t.shape)))
+    return v, t
+
+
+def synthetic_volume(resolution=64, sdf=False):
+    """An analytic density (or signed distance) of a unit-free scene for smoke runs and timings: a ball with a dent (radius 0.6 at the default threshold) and a small floater far from it
+    that cleaning removes.  Density = -40 * signed distance clipped at 0, so the default threshold 10 cuts it 0.25 inside the zero level."""
+    r = int(resolution)
+    ax = torch.linspace(-1, 1, r, device=_dev())
+    x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+    c = 0.2                                                                           # the ball sits off-centre: the floater's box stays well below 5 % of the mesh's
+    d_ball = torch.sqrt((x - c) ** 2 + (y - c) ** 2 + (z - c) ** 2) - 0.85
+    d_dent = 0.35 - torch.sqrt((x - c - 0.7) ** 2 + (y - c) ** 2 + (z - c) ** 2)
+    d_float = torch.sqrt((x + 0.9) ** 2 + (y + 0.9) ** 2 + (z + 0.9) ** 2) - 0.28
+    sd = torch.minimum(torch.maximum(d_ball, d_dent), d_float)
+    return sd.contiguous() if sdf else torch.clamp(-40.0 * sd, min=0.0).contiguous()
+
+
+def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, density_thresh=10.0, mesh=None, cameras=None, dilation=5, min_f=8, min_d=5,
+                  decimate_target=3e5, overwrite=False, log=print):
+    """NeRFRenderer.export_stage0 (nerf/renderer.py:498-570) -> path of the written mesh_0.ply.
+    Exactly one geometry source, or a volume together with the checkpoint that masks it:
+      ckpt    a stage-0 checkpoint dict (top-level `mean_density`, `model` -> `density_grid` [cascade, S^3]): cascade 0 at the grid's own resolution (:511-515),
+              iso = min(mean_density, density_thresh) (:506);
+      volume  a dense [R, R, R] sigma volume (iso as for ckpt when one is given, else `iso` or density_thresh; with ckpt and not sdf it is masked by the grid,
+              :532-539) or, with sdf, a signed distance extracted as (-volume, 0) (:549);
+      mesh    (vertices, triangles) of a foreign mesh in world space: cull and clean only.
+    cameras = (mvps [B, 4, 4], H, W) switches the visibility cull on (:557-560)."""
+    from . import checkpoint as CK
+    if mesh is not None and (ckpt is not None or volume is not None):
+        raise ValueError("export_stage0: a mesh excludes a checkpoint and a volume")
+    if mesh is None and ckpt is None and volume is None:
+        raise ValueError("export_stage0: nothing to extract from (ckpt, volume or mesh)")
+    if sdf and volume is None:
+        raise ValueError("export_stage0: sdf needs a volume")
+    out = os.path.join(save_path, "mesh_0.ply")
+    if os.path.exists(out) and not overwrite:
+        raise FileExistsError("%s exists (pass overwrite to replace it)" % out)
+    if mesh is not None:
+        v, t = _verts(mesh[0]), _tris(mesh[1])
+    else:
+        grid_vol = None
+        if ckpt is not None:
+            model = ckpt["model"] if "model" in ckpt else ckpt
+            grid = torch.as_tensor(model["density_grid"])
+            if grid.dim() == 2 and grid.shape[0] > 1:
+                log("[INFO] checkpoint has %d cascades: exporting cascade 0 only, the outer meshes (bound > 1) are not built" % grid.shape[0])
+            grid_vol = unpack_density_grid(grid, 0)
+            if not sdf:
+                if "mean_density" not in ckpt:
+                    raise KeyError("checkpoint has no top-level mean_density")
+                thresh = select_iso(ckpt["mean_density"], density_thresh)
+        if volume is not None:
+            vol = torch.as_tensor(volume).to(_dev(), torch.float32).contiguous()
+            if sdf:
+                vol, thresh = -vol, 0.0
+            elif ckpt is not None:
+                vol = mask_by_density_grid(vol, grid_vol, thresh)
+            else:
+                thresh = float(iso) if iso is not None else float(density_thresh)
+        else:
+            vol = grid_vol
+        if iso is not None and not sdf:
+            thresh = float(iso)
+        v, t = marching_cubes(vol, thresh)
+        log("[INFO] marching cubes at %s, iso %g: %d vertices, %d triangles" % ("x".join(str(s) for s in vol.shape), thresh, v.shape[0], t.shape[0]))
+        v = index_to_world(v, [int(s) for s in vol.shape])
+    if cameras is not None and t.shape[0]:
+        mvps, H, W = cameras
+        unseen = mark_unseen_triangles(v, t, mvps, H, W, log=log)
+        v, t = remove_masked_trigs(v, t, unseen, dilation=dilation, log=log)
+    v, t = clean_mesh(v, t, min_f=min_f, min_d=min_d, log=log)
+    if decimate_target > 0 and t.shape[0] > decimate_target:
+        log("[WARN] %d triangles exceed --decimate_target %d: quadric decimation is not built, the mesh is kept as it is" % (t.shape[0], int(decimate_target)))
+    if t.shape[0] == 0:
+        raise RuntimeError("export_stage0: the mesh is empty after cleaning")
+    os.makedirs(save_path, exist_ok=True)
+    CK.write_ply(out, v.cpu().numpy(), t.cpu().numpy())
+    log("[INFO] wrote %s: %d vertices, %d triangles" % (out, v.shape[0], t.shape[0]))
+    return out

@@ -1,0 +1,106 @@
+"""Stage-0 mesh extraction on the HIP path (the reference's NeRFRenderer.export_stage0, nerf/renderer.py:498-570): writes `<workspace>/mesh_stage0/mesh_0.ply`, the
+file train_stage1.py, evaluate.py, export_stage1.py and albedo_eval.py start from.
+
+    python scripts/export_stage0.py --workspace <ws> [--ckpt <ws>/checkpoints/ngp_stage0_epXXXX.pth] [--density_thresh 10]        # the S^3 density grid (S = 128)
+    python scripts/export_stage0.py --workspace <ws> --volume sigma_512.npy [--ckpt ...] [--iso v] [--sdf]                         # a denser dumped volume
+    python scripts/export_stage0.py --workspace <ws> --mesh foreign.ply --transforms <data>/transforms_train.json                  # cull and clean only
+    python scripts/export_stage0.py --synthetic [--workspace <ws>]                                                                 # analytic volume, smoke run
+
+Exactly one geometry source: the checkpoint's grid (default: the latest stage-0 checkpoint of the workspace), `--volume` (a [R, R, R] float .npy the user dumps
+from the reference's density network; with `--ckpt` and without `--sdf` it is masked by the checkpoint's grid and cut at min(mean_density, density_thresh),
+otherwise at `--iso` / `--density_thresh`; `--sdf`: a signed distance, extracted as (-volume, 0)), or `--mesh`.  `--transforms` (with --H/--W/--downscale/--scale/
+--offset as in evaluate.py) gives the training cameras of the visibility cull (--mesh_visibility_culling, which -O switches on); without it nothing is culled.
+Quadric decimation is not built: above `--decimate_target` triangles one warning is printed and the mesh is kept."""
+import argparse, glob, json, os, sys, tempfile
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--workspace"); p.add_argument("--ckpt", default=None); p.add_argument("--density_thresh", type=float, default=10.0)
+    p.add_argument("--volume", default=None); p.add_argument("--iso", type=float, default=None); p.add_argument("--sdf", action="store_true")
+    p.add_argument("--mesh", default=None, help="a foreign mesh (PLY): visibility cull and cleaning only")
+    p.add_argument("--transforms", default=None); p.add_argument("--H", type=int, default=800); p.add_argument("--W", type=int, default=800)
+    p.add_argument("--downscale", type=int, default=1); p.add_argument("--scale", type=float, default=1.0); p.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0])
+    p.add_argument("--visibility_mask_dilation", type=int, default=5); p.add_argument("--clean_min_f", type=int, default=8); p.add_argument("--clean_min_d", type=float, default=5)
+    p.add_argument("--decimate_target", type=float, default=3e5)
+    p.add_argument("--out", default=None); p.add_argument("--overwrite", action="store_true"); p.add_argument("--synthetic", action="store_true")
+    p.add_argument("--resolution", type=int, default=64, help="--synthetic: the analytic volume's resolution")
+    return p
+
+
+def latest_stage0_checkpoint(workspace):
+    files = sorted(glob.glob(os.path.join(workspace, "checkpoints", "*stage0*.pth")))
+    return files[-1] if files else None
+
+
+def parse_args(argv=None):
+    """Validates what can be validated without a device: conflicting sources, missing inputs, an existing mesh_0.ply without --overwrite."""
+    p = build_parser()
+    a = p.parse_args(argv)
+    if a.synthetic:
+        if a.mesh or a.volume or a.ckpt:
+            p.error("--synthetic is a geometry source of its own: drop --mesh / --volume / --ckpt")
+        a.workspace = a.workspace or tempfile.mkdtemp(prefix="stage0_ws_")
+    if not a.workspace and not a.out:
+        p.error("--workspace (or --out) is required")
+    if a.mesh and (a.volume or a.ckpt):
+        p.error("--mesh (cull and clean only) conflicts with --volume / --ckpt: give one geometry source")
+    if a.sdf and not a.volume:
+        p.error("--sdf needs --volume (a checkpoint's density grid is not a signed distance)")
+    if a.sdf and a.iso is not None:
+        p.error("--sdf extracts the zero level: --iso conflicts with it")
+    if a.iso is not None and a.mesh:
+        p.error("--iso has no meaning with --mesh")
+    if not (a.synthetic or a.mesh or a.volume or a.ckpt):
+        a.ckpt = latest_stage0_checkpoint(a.workspace) if a.workspace else None
+        if a.ckpt is None:
+            p.error("no stage-0 checkpoint under %s/checkpoints: give --ckpt, --volume, --mesh or --synthetic" % a.workspace)
+    for f in (a.ckpt, a.volume, a.mesh, a.transforms):
+        if f and not os.path.exists(f):
+            p.error("%s does not exist" % f)
+    a.out = a.out or os.path.join(a.workspace, "mesh_stage0")
+    if os.path.exists(os.path.join(a.out, "mesh_0.ply")) and not a.overwrite:
+        p.error("%s exists: pass --overwrite to replace it" % os.path.join(a.out, "mesh_0.ply"))
+    return a
+
+
+def cameras_of(a):
+    """(mvps, H, W) of the transforms file, as albedo_eval.py / evaluate.py read it."""
+    import numpy as np, torch
+    from mirres_restir_nerf_mesh_amd import harness
+    from evaluate import nerf_pose
+    tf = json.load(open(a.transforms))
+    Hh, Ww = int(tf.get("h", a.H)) // a.downscale, int(tf.get("w", a.W)) // a.downscale
+    focal = 0.5 * Ww / np.tan(0.5 * tf["camera_angle_x"])
+    intr = (focal, focal, Ww * 0.5, Hh * 0.5)
+    mvps = [harness.mvp_from_pose(torch.from_numpy(nerf_pose(fr["transform_matrix"], a.scale, a.offset)).cuda(), intr, Hh, Ww) for fr in tf["frames"]]
+    return mvps, Hh, Ww
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import numpy as np, torch
+    from mirres_restir_nerf_mesh_amd import stage0, checkpoint as CK
+    torch.cuda.set_device(0)
+    log = lambda m: print(m, flush=True)
+    kw = dict(density_thresh=a.density_thresh, iso=a.iso, sdf=a.sdf, dilation=a.visibility_mask_dilation, min_f=a.clean_min_f, min_d=a.clean_min_d,
+              decimate_target=a.decimate_target, overwrite=a.overwrite, log=log)
+    if a.synthetic:
+        kw["volume"] = stage0.synthetic_volume(a.resolution, sdf=a.sdf)
+    elif a.mesh:
+        kw["mesh"] = CK.read_ply(a.mesh)
+    else:
+        if a.ckpt:
+            kw["ckpt"] = torch.load(a.ckpt, map_location="cpu", weights_only=False)
+        if a.volume:
+            kw["volume"] = np.load(a.volume)
+    if a.transforms:
+        kw["cameras"] = cameras_of(a)
+    else:
+        log("[INFO] no --transforms: the visibility cull is skipped")
+    return stage0.export_stage0(a.out, **kw)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,304 @@
+"""The stage-0 extraction on the device (csrc/mcubes.hip) through the C ABI: marching cubes bit for bit against the numpy restatement (tests/stage0_refs.py, same
+generated table, same fp32 expressions), surface properties, the checkpoint's density grid, visibility marking against raster.rasterize's own output, ring
+dilatation, compaction, edge-connected components against scipy, cleaning, and scripts/export_stage0.py --synthetic end to end."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stage0_refs as R      # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def S0():
+    from mirres_restir_nerf_mesh_amd import stage0
+    return stage0
+
+
+def _mc_abi(vol, iso):
+    """(rc_count, rc_emit, verts, tris) through the C ABI."""
+    from mirres_restir_nerf_mesh_amd import _lib as L
+    lib = L.lib()
+    nx, ny, nz = vol.shape
+    v = torch.from_numpy(np.ascontiguousarray(vol, np.float32)).cuda()
+    nb = int(lib.mirres_mc_scratch_bytes(nx, ny, nz))
+    assert nb > 0
+    scratch = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    counts = (C.c_int * 2)(-1, -1)
+    rc = lib.mirres_mc_count(L.ptr(v), nx, ny, nz, float(iso), L.ptr(scratch), nb, counts, L.stream_ptr())
+    if rc:
+        return rc, None, None, None
+    V, T = counts[0], counts[1]
+    verts = torch.full((V, 3), -7.0, dtype=torch.float32, device="cuda"); tris = torch.full((T, 3), -7, dtype=torch.int32, device="cuda")
+    rc2 = lib.mirres_mc_emit(L.ptr(v), nx, ny, nz, float(iso), L.ptr(scratch), L.ptr(verts) if V else None, V, L.ptr(tris) if T else None, T, L.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, rc2, verts.cpu().numpy(), tris.cpu().numpy()
+
+
+def _check_mc(vol, iso, what):
+    rc, rc2, v, t = _mc_abi(vol, iso)
+    assert rc == 0 and rc2 == 0, what
+    rv, rt = R.marching_cubes(vol, iso)
+    assert t.shape == rt.shape and np.array_equal(t, rt), "%s: triangles differ (%s vs %s)" % (what, t.shape, rt.shape)
+    assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32)), "%s: %d of %d vertex words differ" % (
+        what, int((v.view(np.uint32) != rv.view(np.uint32)).sum()) if v.shape == rv.shape else -1, rv.size)
+    return v, t
+
+
+def test_all_256_single_cells():
+    rng = np.random.default_rng(1)
+    for cfg in range(256):
+        inside = np.array([(cfg >> c) & 1 for c in range(8)], bool)
+        vals = np.where(inside, 0.5 + rng.random(8), 0.5 - rng.random(8) - 1e-3).astype(np.float32)
+        vol = np.zeros((2, 2, 2), np.float32)
+        for c in range(8):
+            vol[c & 1, (c >> 1) & 1, (c >> 2) & 1] = vals[c]
+        v, t = _check_mc(vol, 0.5, "configuration %d" % cfg)
+        assert len(t) == R.NTRI[cfg]
+
+
+@pytest.mark.parametrize("shape", [(5, 7, 9), (40, 33, 70)])
+def test_random_volumes_bit_equal(shape):
+    vol = np.random.default_rng(sum(shape)).normal(size=shape).astype(np.float32)
+    v, t = _check_mc(vol, 0.1, "random %s" % (shape,))
+    assert len(t) > 0 and t.min() == 0 and t.max() == len(v) - 1
+
+
+def test_values_on_the_iso_level_and_non_finite_values():
+    rng = np.random.default_rng(5)
+    vol = rng.normal(size=(9, 8, 11)).astype(np.float32)
+    flat = vol.reshape(-1)
+    idx = rng.permutation(flat.size)
+    flat[idx[:60]] = 0.25; flat[idx[60:80]] = np.nan; flat[idx[80:100]] = np.inf; flat[idx[100:120]] = -np.inf
+    flat[idx[120:130]] = np.finfo(np.float32).max; flat[idx[130:140]] = 1e-42          # a subnormal
+    v, t = _check_mc(vol, 0.25, "hostile volume")
+    assert np.isfinite(v).all() and (v >= 0).all() and (v <= np.array(vol.shape, np.float32) - 1).all()
+    _check_mc(vol, 0.0, "hostile volume, iso 0 (the value NaN becomes)")
+
+
+def test_no_crossing_and_bad_sizes():
+    from mirres_restir_nerf_mesh_amd import _lib as L
+    rc, rc2, v, t = _mc_abi(np.zeros((6, 5, 4), np.float32), 1.0)
+    assert rc == 0 and rc2 == 0 and v.shape == (0, 3) and t.shape == (0, 3)
+    rc, rc2, v, t = _mc_abi(np.full((3, 3, 3), 5.0, np.float32), 1.0)
+    assert rc == 0 and rc2 == 0 and len(v) == 0 and len(t) == 0
+    lib = L.lib()
+    buf = torch.zeros(64, device="cuda"); counts = (C.c_int * 2)()
+    for dims in ((1, 4, 4), (4, 1, 4), (4, 4, 1), (0, 2, 2), (-3, 2, 2)):
+        assert lib.mirres_mc_scratch_bytes(*dims) == L.lib().mirres_mc_scratch_bytes(*dims) < 0
+        assert lib.mirres_mc_count(L.ptr(buf), dims[0], dims[1], dims[2], 0.5, L.ptr(buf), 256, counts, L.stream_ptr()) == -1
+        assert lib.mirres_mc_emit(L.ptr(buf), dims[0], dims[1], dims[2], 0.5, L.ptr(buf), L.ptr(buf), 1, L.ptr(buf), 1, L.stream_ptr()) == -1
+    assert lib.mirres_mc_count(None, 4, 4, 4, 0.5, L.ptr(buf), 256, counts, L.stream_ptr()) == -1
+    assert lib.mirres_mc_count(L.ptr(buf), 4, 4, 4, float("nan"), L.ptr(buf), 256, counts, L.stream_ptr()) == -1
+    assert lib.mirres_mc_count(L.ptr(buf), 4, 4, 4, 0.5, L.ptr(buf), 8, counts, L.stream_ptr()) == -1 and b"scratch" in lib.mirres_last_error()
+
+
+def test_random_closed_surface_is_a_two_manifold_of_edges(S0):
+    vol = np.random.default_rng(11).normal(size=(24, 24, 24)).astype(np.float32)
+    vol[0] = vol[-1] = -3; vol[:, 0] = vol[:, -1] = -3; vol[:, :, 0] = vol[:, :, -1] = -3
+    v, t = S0.marching_cubes(vol, 0.0)
+    t = t.cpu().numpy()
+    assert len(t) > 5000 and R.mesh_edges_ok(t)
+
+
+def test_sphere_topology_orientation_and_determinism(S0):
+    ax = np.linspace(-1, 1, 48, dtype=np.float32)
+    x, y, z = np.meshgrid(ax, ax, ax, indexing="ij")
+    sd = (np.sqrt(x * x + y * y + z * z) - np.float32(0.7)).astype(np.float32)
+    dens = np.maximum(-40 * sd, 0).astype(np.float32)
+    v, t = S0.marching_cubes(dens, 10.0)
+    vn, tn = v.cpu().numpy(), t.cpu().numpy()
+    assert R.mesh_edges_ok(tn) and R.euler_characteristic(len(vn), tn) == 2 and R.signed_volume(vn, tn) > 0
+    vs, ts = S0.marching_cubes(-torch.from_numpy(sd), 0.0)                      # --sdf: (-vol, 0)
+    assert R.mesh_edges_ok(ts.cpu().numpy()) and R.euler_characteristic(len(vs), ts.cpu().numpy()) == 2 and R.signed_volume(vs.cpu().numpy(), ts.cpu().numpy()) > 0
+    v2, t2 = S0.marching_cubes(dens, 10.0)
+    assert vn.tobytes() == v2.cpu().numpy().tobytes() and tn.tobytes() == t2.cpu().numpy().tobytes()
+    w = S0.index_to_world(v, 48).cpu().numpy()
+    assert np.abs(np.linalg.norm(w, axis=1) - 0.45).max() < 0.03               # density 10 lies 0.25 inside radius 0.7
+
+
+def test_density_grid_of_a_checkpoint(S0, tmp_path):
+    S = 16
+    ax = np.linspace(-1, 1, S, dtype=np.float32)
+    x, y, z = np.meshgrid(ax, ax, ax, indexing="ij")
+    vol = (np.maximum(30 * (0.8 - np.sqrt(x * x + 1.5 * y * y + 2 * z * z)), 0) + np.random.default_rng(2).random((S, S, S)) * 0.01).astype(np.float32)
+    grid = np.zeros((2, S ** 3), np.float32)
+    grid[0][S0.morton_indices(S).reshape(-1)] = vol.reshape(-1); grid[1] = 99.0
+    ck = {"model": {"density_grid": torch.from_numpy(grid)}, "mean_density": 4.5}
+    got = S0.unpack_density_grid(ck["model"]["density_grid"]).cpu().numpy()
+    assert np.array_equal(got, vol) and np.array_equal(got, R.unpack_morton(grid[0], S))
+    v0, t0 = S0.marching_cubes(vol, 4.5)
+    lines = []
+    out = S0.export_stage0(str(tmp_path), ckpt=ck, min_f=0, min_d=0, log=lines.append)
+    assert any("cascade 0 only" in l for l in lines)
+    from mirres_restir_nerf_mesh_amd import checkpoint as CK
+    v, t = CK.read_ply(out)
+    assert np.array_equal(t, t0.cpu().numpy()) and np.array_equal(v, S0.index_to_world(v0, S).cpu().numpy())
+    with pytest.raises(FileExistsError):
+        S0.export_stage0(str(tmp_path), ckpt=ck, log=lines.append)
+    # a denser volume beside the checkpoint is masked by the nearest-upsampled grid > thresh (F.interpolate's index rule)
+    Rr = 40
+    dense = np.random.default_rng(4).random((Rr, Rr, Rr)).astype(np.float32) * 9 + 1
+    dense[3, 3, 3] = np.nan; dense[20, 20, 20] = np.inf
+    want = torch.from_numpy(dense) * (torch.nn.functional.interpolate(torch.from_numpy(vol)[None, None], size=[Rr] * 3, mode="nearest")[0, 0] > 4.5)
+    got = S0.mask_by_density_grid(dense, vol, 4.5).cpu()
+    assert torch.equal(torch.nan_to_num(got, 0), torch.nan_to_num(want, 0)) and torch.equal(torch.isnan(got), torch.isnan(want))
+
+
+# ------------------------------------------------------------------------------------------------ visibility, dilation, removal
+@pytest.fixture(scope="module")
+def hidden_cube_scene(S0):
+    """An icosphere (320 faces) with a small closed cube hidden inside it, 6 cameras at 64 x 64; the last face of the mesh belongs to the cube."""
+    from mirres_restir_nerf_mesh_amd import harness
+    v, t = R.join([R.icosphere(2, 1.0), R.cube(0.1)])
+    poses, intr = R.orbit_cameras(6, 3.0, 64, 64)
+    mvps = [harness.mvp_from_pose(torch.from_numpy(p).cuda(), intr, 64, 64) for p in poses]
+    return dict(v=v, t=t, mvps=mvps, n_sphere=320, n_sphere_v=162)
+
+
+def test_seen_faces_equal_the_ids_of_the_rasteriser(S0, hidden_cube_scene):
+    from mirres_restir_nerf_mesh_amd import raster, _lib as L
+    from mirres_restir_nerf_mesh_amd.renderer_restir import restirbvhWorker
+    sc = hidden_cube_scene
+    v, t = torch.from_numpy(sc["v"]).cuda(), torch.from_numpy(sc["t"]).cuda()
+    T = len(sc["t"])
+    seen = S0.seen_faces(v, t, sc["mvps"], 64, 64).cpu().numpy()
+    W = restirbvhWorker(v, t); W.update_mesh(v, t)
+    ids = set(); background = 0
+    for mvp in sc["mvps"]:
+        rast, _ = raster.rasterize(raster.RasterizeContext(W), (torch.nn.functional.pad(v, (0, 1), value=1.0) @ mvp.t())[None], t, (64, 64), grad_db=False, mvp=mvp)
+        k = rast[..., 3].long().reshape(-1).cpu().numpy()
+        background += int((k == 0).sum()); ids |= set((k[k > 0] - 1).tolist())
+    assert background > 0 and len(ids) > 100
+    want = np.zeros(T, np.uint8); want[sorted(ids)] = 1
+    assert np.array_equal(seen, want)
+    assert seen[-1] == 0 and not seen[sc["n_sphere"]:].any()                      # background marks nothing (not the last face); no cube face is seen
+    assert np.array_equal(S0.mark_unseen_triangles(v, t, sc["mvps"], 64, 64).cpu().numpy(), want == 0)
+    # id 0 and ids beyond T mark nothing
+    rast = torch.zeros((5, 4), device="cuda"); rast[1, 3] = 3.0; rast[2, 3] = T + 1.0; rast[3, 3] = float("nan"); rast[4, 3] = -2.0
+    flags = torch.zeros(T + 1, dtype=torch.uint8, device="cuda")
+    assert L.lib().mirres_mesh_mark_seen(L.ptr(rast), 5, T, L.ptr(flags), L.stream_ptr()) == 0
+    assert flags.cpu().numpy().nonzero()[0].tolist() == [2]
+
+
+@pytest.mark.parametrize("k", [0, 1, 2, 5])
+def test_dilation_rings_equal_the_restatement(S0, hidden_cube_scene, k):
+    sc = hidden_cube_scene
+    seen = S0.seen_faces(sc["v"], sc["t"], sc["mvps"], 64, 64).cpu().numpy()
+    for sel in (seen, np.eye(1, len(sc["t"]), 17, dtype=np.uint8)[0]):
+        got = S0.dilate_selection(sc["t"], len(sc["v"]), sel, k).cpu().numpy()
+        assert np.array_equal(got.astype(bool), R.dilate(sc["t"], len(sc["v"]), sel, k)), k
+
+
+def test_remove_masked_trigs_drops_the_hidden_cube_and_keeps_the_order(S0, hidden_cube_scene):
+    sc = hidden_cube_scene
+    unseen = S0.mark_unseen_triangles(sc["v"], sc["t"], sc["mvps"], 64, 64)
+    v, t = S0.remove_masked_trigs(sc["v"], sc["t"], unseen, dilation=5)
+    assert np.array_equal(t.cpu().numpy(), sc["t"][: sc["n_sphere"]]) and np.array_equal(v.cpu().numpy(), sc["v"][: sc["n_sphere_v"]])
+    # an arbitrary mask, no dilation: order-preserving compaction against the restatement
+    mask = np.random.default_rng(8).random(len(sc["t"])) < 0.6
+    v, t = S0.remove_masked_trigs(sc["v"], sc["t"], mask, dilation=0)
+    rv, rt = R.compact(sc["v"], sc["t"], ~mask)
+    assert np.array_equal(v.cpu().numpy(), rv) and np.array_equal(t.cpu().numpy(), rt)
+
+
+# ------------------------------------------------------------------------------------------------ cleaning
+def _dirty_mesh():
+    """Pieces in order: icosphere (320 faces, with 3 of its vertices duplicated bit for bit and one face repeated with rotated indices, a zero-area face), a 6-face
+    fragment, a tiny far-away closed tetrahedron, two 10-face fans touching at one vertex only, an unreferenced vertex."""
+    sv, st = R.icosphere(2, 1.0)
+    dup = np.array([5, 40, 100]); sv2 = np.concatenate([sv, sv[dup]], 0)           # duplicated vertices 162, 163, 164
+    st2 = st.copy()
+    for j, d in enumerate(dup):
+        rows = np.nonzero((st2 == d).any(axis=1))[0][:2]                           # two of the faces around d use the duplicate instead
+        st2[rows] = np.where(st2[rows] == d, 162 + j, st2[rows])
+    extra = np.array([st2[7][[1, 2, 0]], [0, 1, 1], [10, 10, 10]], np.int32)        # a duplicate face (rotated), two faces with a repeated index
+    sphere = (np.concatenate([sv2, np.array([[0, 0, 2], [1, 0, 2], [2, 0, 2]], np.float32)], 0), np.concatenate([st2, extra, np.array([[165, 166, 167]], np.int32)], 0))   # + a collinear (zero-area) face
+    fan = lambda c, z, n: (np.array([[c, 0, z]] + [[c + 0.6 * np.cos(a), 0.6 * np.sin(a), z] for a in np.linspace(0, np.pi, n + 1)], np.float32),
+                           np.array([(0, i + 1, i + 2) for i in range(n)], np.int32))
+    frag = fan(3.0, 0.0, 6)
+    tet = (np.array([[8, 8, 8], [8.01, 8, 8], [8, 8.01, 8], [8, 8, 8.01]], np.float32), np.array([(0, 2, 1), (0, 1, 3), (0, 3, 2), (1, 2, 3)], np.int32))
+    fa = fan(0.0, 3.0, 10)
+    fb_v, fb_t = fan(0.0, 3.0, 10); fb_v = fb_v * np.array([1, -1, 1], np.float32); fb_t = fb_t[:, [0, 2, 1]]
+    fb_v[0] = fa[0][0]                                                              # the second fan's centre is bit-identical to the first one's: merged, then shared
+    lone = (np.array([[4, 4, 4]], np.float32), np.zeros((0, 3), np.int32))
+    return R.join([sphere, frag, tet, fa, (fb_v, fb_t), lone])
+
+
+def _scipy_labels(tris):
+    from test_stage0_host import _scipy_labels as f
+    return f(tris)
+
+
+def test_components_equal_scipy_and_ignore_shared_vertices(S0):
+    v, t = _dirty_mesh()
+    lab, rounds = S0.face_components(t)
+    lab = lab.cpu().numpy()
+    assert np.array_equal(lab, _scipy_labels(t)) and np.array_equal(lab, R.components(t)) and 1 <= rounds <= 64
+    assert all(lab[f] == np.nonzero(lab == lab[f])[0].min() for f in range(len(t)))
+    # after the vertex merge the two fans share ONE vertex and still are two components
+    vc, tc = S0.clean_mesh(v, t, min_f=0, min_d=0)
+    lc = S0.face_components(tc)[0].cpu().numpy()
+    assert np.array_equal(lc, _scipy_labels(tc.cpu().numpy()))
+    tcn = tc.cpu().numpy()
+    fans = [l for l in np.unique(lc) if (lc == l).sum() == 10]
+    assert len(fans) == 2 and len(set(tcn[lc == fans[0]].reshape(-1)) & set(tcn[lc == fans[1]].reshape(-1))) == 1
+    perm = np.random.default_rng(6).permutation(len(t))
+    assert np.array_equal(S0.face_components(t[perm])[0].cpu().numpy(), _scipy_labels(t[perm]))
+
+
+def test_clean_mesh_keeps_exactly_the_expected_pieces_in_order(S0):
+    v, t = _dirty_mesh()
+    vc, tc = S0.clean_mesh(v, t, min_f=0, min_d=0)
+    vc, tc = vc.cpu().numpy(), tc.cpu().numpy()
+    # steps 1-3: 3 duplicate vertices, 3 zero-area-face vertices and the lone vertex leave; the duplicate face, the two repeated-index faces and the collinear face leave
+    assert len(vc) == len(v) - 3 - 3 - 1 - 1 and len(tc) == len(t) - 4              # (- 1: the second fan's centre merges into the first one's)
+    sv, st = R.icosphere(2, 1.0)
+    assert np.array_equal(tc[:320], st) and np.array_equal(vc[:162], sv)            # the sphere is the clean icosphere again, order kept
+    v8, t8 = S0.clean_mesh(v, t, min_f=8, min_d=5)
+    v8, t8 = v8.cpu().numpy(), t8.cpu().numpy()
+    # min_d = 5 % of the mesh's diagonal (~15.6, i.e. 0.78): the tetrahedron (0.017) leaves, the fans and the fragment (1.34) do not; min_f = 8: the 6-face fragment leaves; sphere and both 10-face fans stay, in order
+    assert len(t8) == 320 + 10 + 10
+    lab = R.components(tc); keep = np.array([(lab == l).sum() >= 8 and np.ptp(vc[tc[lab == l].reshape(-1)], axis=0).max() > 0.1 for l in lab])
+    rv, rt = R.compact(vc, tc, keep)
+    assert np.array_equal(t8, rt) and np.array_equal(v8, rv)
+    vd, td = S0.clean_mesh(v, t, min_f=0, min_d=5)
+    assert len(td) == 320 + 6 + 10 + 10
+
+
+def test_strip_converges_and_a_forced_round_cap_is_an_error(S0):
+    from mirres_restir_nerf_mesh_amd import _lib as L
+    v, t = R.strip(3000)
+    lab, rounds = S0.face_components(t)
+    assert np.array_equal(lab.cpu().numpy(), np.zeros(3000, np.int32)) and rounds <= 64
+    print("strip of 3000 faces: %d rounds" % rounds)
+    with pytest.raises(L.MirresError, match="still changing after 1 rounds"):
+        S0.face_components(t, max_rounds=1)
+    lab, rounds = S0.face_components(t)                                             # the library is usable after the error
+    assert not lab.any()
+
+
+def test_export_stage0_synthetic_end_to_end(S0, tmp_path):
+    ws = str(tmp_path / "ws")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "export_stage0.py"), "--synthetic", "--workspace", ws, "--resolution", "48"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "marching cubes" in r.stdout and "mesh cleaning" in r.stdout
+    from mirres_restir_nerf_mesh_amd import checkpoint as CK, harness, scene
+    from mirres_restir_nerf_mesh_amd.renderer_restir import restirbvhWorker
+    v, t, vc, fc = CK.load_stage0_mesh(ws, 1)
+    assert len(t) > 1000 and R.signed_volume(v, t) > 0
+    assert len(np.unique(R.components(t))) == 1                                       # the floater is gone
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "export_stage0.py"), "--synthetic", "--workspace", ws], capture_output=True, text=True, timeout=300)
+    assert r2.returncode == 2 and "--overwrite" in r2.stderr
+    W = restirbvhWorker(torch.from_numpy(v).cuda(), torch.from_numpy(t).cuda()); W.update_mesh(W.vrt, W.v_ind)
+    poses, intr = R.orbit_cameras(1, 3.0, 32, 32)
+    env = torch.from_numpy(scene.make_env(32, 64)).cuda()
+    img = harness.test_view(W, None, env, torch.from_numpy(poses[0]), intr, 32, 32, 2)
+    assert tuple(img.shape) == (32, 32, 3) and torch.isfinite(img).all() and float(img.min()) >= 0 and float((img < 0.999).float().mean()) > 0.05
