@@ -51,69 +51,92 @@ MR_DEV Slab slab(const float* __restrict__ bmin, const float* __restrict__ bmax,
     return s;
 }
 
+// the exact box a leaf carries beside its triangle (engine.hpp LeafRec: min in l2.yzw, max in l3.xyz), tested as the reference tests a node's box
+MR_DEV Slab leaf_slab(const float4& l2, const float4& l3, float ox, float oy, float oz, float ix, float iy, float iz, float t_min) {
+    const float bmin[3] = {l2.y, l2.z, l2.w}, bmax[3] = {l3.x, l3.y, l3.z}, o[3] = {ox, oy, oz}, inv[3] = {ix, iy, iz};
+    return slab(bmin, bmax, o, inv, t_min);
+}
+
+// What every traversal derives from a ray's direction (helperDi.slang:201-210): the normalised direction and the reciprocals of its components, a zero component
+// replaced by 0.000001 first. k_trace_any4q keeps a copy of its own: it switches to the short square root / reciprocal for its pixel-pair source, and going
+// through this function cost its production form two SGPRs and eight instructions (profiles/trace_refactor_isa.txt).
+struct RaySetup { v3 d; float ix, iy, iz; };
+MR_DEV RaySetup ray_setup(v3 rd) {
+    RaySetup r;
+    r.d = normalize(rd);
+    float dx = r.d.x, dy = r.d.y, dz = r.d.z;
+    if (dx == 0.f) dx = 0.000001f; if (dy == 0.f) dy = 0.000001f; if (dz == 0.f) dz = 0.000001f;
+    r.ix = 1.0f / dx; r.iy = 1.0f / dy; r.iz = 1.0f / dz;
+    return r;
+}
+// the root's box test: is there anything to traverse for a ray limited to [t_min, t_far]?
+MR_DEV bool root_passes(const BvhView& B, const float o[3], const float inv[3], float t_min, float t_far) {
+    const Slab s = slab(B.root_box, B.root_box + 3, o, inv, t_min);
+    return s.tf > s.tn && t_far > s.tn;
+}
+
+// Reference-order traversal state shared by traverse<> and k_trace_persist: `cur` >= 0 is an internal node to visit, < 0 a leaf (~slot), WIDE_NONE nothing.
+static constexpr int WIDE_NONE = 0x40000000;
+// pop deferred (left) children until one passes the closest-dependent half of its box test; false: the stack is empty
+MR_DEV bool pop_deferred(const uint2* lds_stack, const uint2* spill, int& sp, float closest, int& cur) {
+    while (sp > 0) {
+        --sp;
+        uint2 e = (sp < MR_LDS_STACK) ? lds_stack[sp * MR_TRACE_BLOCK] : spill[sp - MR_LDS_STACK];
+        if (closest > __uint_as_float(e.y)) { cur = (int)e.x; return true; }
+    }
+    return false;
+}
+// visit internal node `cur`: one 64-byte fetch (4 x dwordx4), both children's slabs, the left child deferred, the right one taken at once. false: the stack is full
+MR_DEV bool wide_visit(const BvhView& B, int& cur, const float o[3], const float inv[3], float t_min, float closest, uint2* lds_stack, uint2* spill, int& sp) {
+    const WideNode* __restrict__ n = B.nodes + cur;
+    const float4 q0 = reinterpret_cast<const float4*>(n)[0];
+    const float4 q1 = reinterpret_cast<const float4*>(n)[1];
+    const float4 q2 = reinterpret_cast<const float4*>(n)[2];
+    const float4 q3 = reinterpret_cast<const float4*>(n)[3];
+    const float lmin[3] = {q0.x, q0.y, q0.z}, lmax[3] = {q0.w, q1.x, q1.y};
+    const float rmin[3] = {q1.z, q1.w, q2.x}, rmax[3] = {q2.y, q2.z, q2.w};
+    const int left = __float_as_int(q3.x), right = __float_as_int(q3.y);
+    Slab sl = slab(lmin, lmax, o, inv, t_min);
+    Slab sr = slab(rmin, rmax, o, inv, t_min);
+    bool room = true;
+    if (sl.tf > sl.tn) {  // may still be rejected at pop time when closest has shrunk
+        uint2 e; e.x = (uint32_t)left; e.y = __float_as_uint(sl.tn);
+        if (sp < MR_LDS_STACK) lds_stack[sp * MR_TRACE_BLOCK] = e;
+        else if (sp < MR_STACK) spill[sp - MR_LDS_STACK] = e;
+        if (sp < MR_STACK) sp++; else room = false;
+    }
+    cur = (sr.tf > sr.tn && closest > sr.tn) ? right : WIDE_NONE;
+    return room;
+}
+
 struct TraceOut { bool hit; float t, u, v; int slot; v3 d; };
 
-template <bool ANY, bool COUNT>
+template <bool ANY>
 MR_DEV TraceOut traverse(const BvhView& B, v3 ro, v3 rd_in, float t_min, float t_max, uint2* lds_stack, uint32_t* cnt) {
     TraceOut out; out.hit = false; out.t = 0.f; out.u = 0.f; out.v = 0.f; out.slot = -1;
-    const v3 d = normalize(rd_in);  // helperDi.slang:201
+    const RaySetup rs = ray_setup(rd_in);
+    const v3 d = rs.d;
     out.d = d;
-    const float o[3] = {ro.x, ro.y, ro.z};
-    float inv[3];
-    {
-        float dd[3] = {d.x, d.y, d.z};
-#pragma unroll
-        for (int i = 0; i < 3; i++) { float di = dd[i]; if (di == 0.f) di = 0.000001f; inv[i] = 1.0f / di; }
-    }
+    const float o[3] = {ro.x, ro.y, ro.z}, inv[3] = {rs.ix, rs.iy, rs.iz};
     float closest = t_max;
     uint2 spill[MR_STACK - MR_LDS_STACK];
     int sp = 0;
     uint32_t popped = 1, entered = 0, leaves = 0, overflow = 0;
     // root (node 0) box test
-    int cur;  // >= 0: internal node to visit; otherwise leaf (~slot) pending a triangle test; INT_MIN/2 = nothing
-    const int NONE = 0x40000000;
-    {
-        Slab s = slab(B.root_box, B.root_box + 3, o, inv, t_min);
-        cur = (s.tf > s.tn && closest > s.tn) ? 0 : NONE;
-    }
+    const int NONE = WIDE_NONE;
+    int cur = root_passes(B, o, inv, t_min, closest) ? 0 : NONE;  // >= 0: internal node to visit; otherwise leaf (~slot) pending a triangle test; NONE = nothing
     while (true) {
-        if (cur == NONE) {
-            // pop deferred (left) children until one passes the closest-dependent half of its box test
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                uint2 e = (sp < MR_LDS_STACK) ? lds_stack[sp * MR_TRACE_BLOCK] : spill[sp - MR_LDS_STACK];
-                if (closest > __uint_as_float(e.y)) { cur = (int)e.x; found = true; break; }
-            }
-            if (!found) break;
-        }
+        if (cur == NONE && !pop_deferred(lds_stack, spill, sp, closest, cur)) break;
         if (cur >= 0) {
-            if (COUNT) { entered++; popped += 2; }
-            const WideNode* __restrict__ n = B.nodes + cur;
-            // one 64-byte fetch: 4 x dwordx4
-            const float4 q0 = reinterpret_cast<const float4*>(n)[0];
-            const float4 q1 = reinterpret_cast<const float4*>(n)[1];
-            const float4 q2 = reinterpret_cast<const float4*>(n)[2];
-            const float4 q3 = reinterpret_cast<const float4*>(n)[3];
-            const float lmin[3] = {q0.x, q0.y, q0.z}, lmax[3] = {q0.w, q1.x, q1.y};
-            const float rmin[3] = {q1.z, q1.w, q2.x}, rmax[3] = {q2.y, q2.z, q2.w};
-            const int left = __float_as_int(q3.x), right = __float_as_int(q3.y);
-            Slab sl = slab(lmin, lmax, o, inv, t_min);
-            Slab sr = slab(rmin, rmax, o, inv, t_min);
-            if (sl.tf > sl.tn) {  // may still be rejected at pop time when closest has shrunk
-                uint2 e; e.x = (uint32_t)left; e.y = __float_as_uint(sl.tn);
-                if (sp < MR_LDS_STACK) lds_stack[sp * MR_TRACE_BLOCK] = e;
-                else if (sp < MR_STACK) spill[sp - MR_LDS_STACK] = e;
-                if (sp < MR_STACK) sp++; else overflow++;
-            }
-            cur = (sr.tf > sr.tn && closest > sr.tn) ? right : NONE;
+            entered++; popped += 2;
+            if (!wide_visit(B, cur, o, inv, t_min, closest, lds_stack, spill, sp)) overflow++;
             continue;
         }
         // leaf: triangle_hit (helperDi.slang:172-195), accepts any t
         {
             const int slot = ~cur;
             cur = NONE;
-            if (COUNT) leaves++;
+            leaves++;
             const TriRec* __restrict__ tr = B.tris + slot;
             const float4 a = reinterpret_cast<const float4*>(tr)[0];
             const float4 b = reinterpret_cast<const float4*>(tr)[1];
@@ -137,7 +160,7 @@ MR_DEV TraceOut traverse(const BvhView& B, v3 ro, v3 rd_in, float t_min, float t
             out.t = closest;
         }
     }
-    if (COUNT && cnt) { cnt[0] = popped; cnt[1] = entered; cnt[2] = leaves; cnt[3] = overflow; }
+    if (cnt) { cnt[0] = popped; cnt[1] = entered; cnt[2] = leaves; cnt[3] = overflow; }
     return out;
 }
 
@@ -158,7 +181,27 @@ MR_DEV void finish_closest(const BvhView& B, const TraceOut& r, v3 ro, v3& pos, 
     }
 }
 
-template <bool COUNT>
+// one closest-hit result: the packed HitRec (position | hit, normal | t) and / or the separate arrays, whichever the caller asked for
+MR_DEV void write_closest(HitRec* rec, int32_t* hit, float* t, float* pos, float* normal,
+                          int32_t* prim, uint32_t i, bool h, float tv, const v3& p, const v3& nn, int pr) {
+    if (rec) {
+        float4 o0, o1;
+        o0.x = p.x; o0.y = p.y; o0.z = p.z; o0.w = __int_as_float(h ? 1 : 0);
+        o1.x = nn.x; o1.y = nn.y; o1.z = nn.z; o1.w = tv;
+        reinterpret_cast<float4*>(rec + i)[0] = o0; reinterpret_cast<float4*>(rec + i)[1] = o1;
+    }
+    if (hit) hit[i] = h ? 1 : 0;
+    if (t) t[i] = tv;
+    if (pos) st3(pos, i, p);
+    if (normal) st3(normal, i, nn);
+    if (prim) prim[i] = pr;
+}
+// per-ray visit counters of the reference-order kernels (popped, entered, leaves, overflow) and the thread's running sums of the first three
+MR_DEV void write_counters(uint32_t* counters, uint32_t i, const uint32_t c[4], unsigned long long& sp, unsigned long long& se, unsigned long long& sl) {
+    if (counters) { counters[4 * (size_t)i] = c[0]; counters[4 * (size_t)i + 1] = c[1]; counters[4 * (size_t)i + 2] = c[2]; counters[4 * (size_t)i + 3] = c[3]; }
+    sp += c[0]; se += c[1]; sl += c[2];
+}
+
 __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any(BvhView B, const Ray* __restrict__ rays, const uint32_t* __restrict__ d_count,
                                                               uint32_t n_fixed, int32_t* __restrict__ hit, uint32_t* __restrict__ counters,
                                                               unsigned long long* __restrict__ stats) {
@@ -168,18 +211,14 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any(BvhView B, const R
     for (uint32_t i = blockIdx.x * MR_TRACE_BLOCK + threadIdx.x; i < n; i += gridDim.x * MR_TRACE_BLOCK) {
         const float4 a = reinterpret_cast<const float4*>(rays + i)[0], b = reinterpret_cast<const float4*>(rays + i)[1];
         uint32_t c[4];
-        TraceOut r = traverse<true, COUNT>(B, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), a.w, b.w, lds + threadIdx.x, c);
+        TraceOut r = traverse<true>(B, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), a.w, b.w, lds + threadIdx.x, c);
         hit[i] = r.hit ? 1 : 0;
-        if (COUNT) {
-            if (counters) { counters[4 * (size_t)i] = c[0]; counters[4 * (size_t)i + 1] = c[1]; counters[4 * (size_t)i + 2] = c[2]; counters[4 * (size_t)i + 3] = c[3]; }
-            sp += c[0]; se += c[1]; sl += c[2];
-        }
+        write_counters(counters, i, c, sp, se, sl);
     }
-    if (COUNT && stats) { atomicAdd(&stats[2], sp); atomicAdd(&stats[3], se); atomicAdd(&stats[4], sl); }
+    if (stats) { atomicAdd(&stats[2], sp); atomicAdd(&stats[3], se); atomicAdd(&stats[4], sl); }
     if (stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[0], (unsigned long long)n);
 }
 
-template <bool COUNT>
 __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest(BvhView B, const Ray* __restrict__ rays, const uint32_t* __restrict__ d_count,
                                                                   uint32_t n_fixed, HitRec* __restrict__ rec, int32_t* __restrict__ hit,
                                                                   float* __restrict__ t, float* __restrict__ pos, float* __restrict__ normal,
@@ -192,26 +231,13 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest(BvhView B, con
         const float4 a = reinterpret_cast<const float4*>(rays + i)[0], b = reinterpret_cast<const float4*>(rays + i)[1];
         uint32_t c[4];
         const v3 ro = V3(a.x, a.y, a.z);
-        TraceOut r = traverse<false, COUNT>(B, ro, V3(b.x, b.y, b.z), a.w, b.w, lds + threadIdx.x, c);
+        TraceOut r = traverse<false>(B, ro, V3(b.x, b.y, b.z), a.w, b.w, lds + threadIdx.x, c);
         v3 p, nn; int pr;
         finish_closest(B, r, ro, p, nn, pr);
-        if (rec) {
-            float4 o0, o1;
-            o0.x = p.x; o0.y = p.y; o0.z = p.z; o0.w = __int_as_float(r.hit ? 1 : 0);
-            o1.x = nn.x; o1.y = nn.y; o1.z = nn.z; o1.w = r.t;
-            reinterpret_cast<float4*>(rec + i)[0] = o0; reinterpret_cast<float4*>(rec + i)[1] = o1;
-        }
-        if (hit) hit[i] = r.hit ? 1 : 0;
-        if (t) t[i] = r.t;
-        if (pos) st3(pos, i, p);
-        if (normal) st3(normal, i, nn);
-        if (prim) prim[i] = pr;
-        if (COUNT) {
-            if (counters) { counters[4 * (size_t)i] = c[0]; counters[4 * (size_t)i + 1] = c[1]; counters[4 * (size_t)i + 2] = c[2]; counters[4 * (size_t)i + 3] = c[3]; }
-            sp += c[0]; se += c[1]; sl += c[2];
-        }
+        write_closest(rec, hit, t, pos, normal, prim, i, r.hit, r.t, p, nn, pr);
+        write_counters(counters, i, c, sp, se, sl);
     }
-    if (COUNT && stats) { atomicAdd(&stats[5], sp); atomicAdd(&stats[6], se); atomicAdd(&stats[7], sl); }
+    if (stats) { atomicAdd(&stats[5], sp); atomicAdd(&stats[6], se); atomicAdd(&stats[7], sl); }
     if (stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[1], (unsigned long long)n);
 }
 
@@ -241,34 +267,29 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest(BvhView B, con
 // the wave whose atomicAdd lands in [end, end + chunk) — exactly one per sub-queue, chunks being equal — publishes the sub-queue's bit in a mask word on a line of
 // its own (32 atomics per launch), and a wave that has just failed reads the mask once and skips what is known to be empty. Sub-queues beyond n are never touched.
 // Which wave gets which rays does not change any ray's answer; a mask that lags only costs the atomic it would have saved.
-#ifndef MR_GRAB_MODE
-#define MR_GRAB_MODE 3     // 0: every probe is an atomicAdd (rounds 1-4); 3: + the mask of empty sub-queues, published once per sub-queue
-#endif
 MR_DEV bool grab_chunk(uint32_t* __restrict__ heads, uint32_t n, uint32_t per, uint32_t chunk, uint32_t& q, uint32_t& fails, uint32_t& known, uint32_t& c_next, uint32_t& c_end, int lane) {
     uint32_t* const empty_mask = heads + MR_NQ * MR_QSTRIDE;
     while (fails < MR_NQ) {
         const uint32_t qb = q * per;
-        if (MR_GRAB_MODE == 0 || (qb < n && !((known >> q) & 1u))) {
+        if (qb < n && !((known >> q) & 1u)) {
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(heads + q * MR_QSTRIDE, chunk);
             base = __builtin_amdgcn_readfirstlane(base);
             const uint32_t qe = (qb + per < n) ? qb + per : n;
             if (qb < n && base < qe - qb) { c_next = qb + base; c_end = (c_next + chunk < qe) ? c_next + chunk : qe; return true; }
-            if (MR_GRAB_MODE == 3) {
-                uint32_t m = 0;
-                if (lane == 0) {
-                    if (base - (qe - qb) < chunk) (void)__hip_atomic_fetch_or(empty_mask, 1u << q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    m = __hip_atomic_load(empty_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                known |= __builtin_amdgcn_readfirstlane(m) | (1u << q);
+            uint32_t m = 0;
+            if (lane == 0) {
+                if (base - (qe - qb) < chunk) (void)__hip_atomic_fetch_or(empty_mask, 1u << q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                m = __hip_atomic_load(empty_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            known |= __builtin_amdgcn_readfirstlane(m) | (1u << q);
         }
         q = (q + 1 == MR_NQ) ? 0 : q + 1; fails++;
     }
     return false;
 }
 
-template <bool ANY, bool FRONT = false>   // FRONT: a conventional closest hit — only triangles met in (t_min, t_max] count (mirres_bvh_trace mode 4; the reference's own rule is FRONT = false)
+template <bool FRONT = false>   // FRONT: a conventional closest hit — only triangles met in (t_min, t_max] count (mirres_bvh_trace mode 4; the reference's own rule is FRONT = false)
 __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, const Ray* __restrict__ rays, const uint32_t* __restrict__ d_count,
                                                                   uint32_t n_fixed, uint32_t* __restrict__ work_head, int32_t* __restrict__ hit_out,
                                                                   HitRec* __restrict__ rec, float* __restrict__ t_out, float* __restrict__ pos_out,
@@ -279,7 +300,7 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
     const uint32_t n = d_count ? *d_count : n_fixed;
     const int lane = lane_id();
     const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int NONE = 0x40000000;
+    const int NONE = WIDE_NONE;
     // chunk size: ~4 chunks per resident wave so that the tail balances, 64..1024 rays (one global atomic per chunk)
     uint32_t chunk = n / (gridDim.x * (MR_TRACE_BLOCK / 64) * MR_CHUNK_DIV);
     chunk = chunk < 64 ? 64 : (chunk > MR_CHUNK_MAX ? MR_CHUNK_MAX : (chunk & ~63u));
@@ -305,14 +326,11 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
                     const uint32_t rid = redo ? redo[idx] : idx;   // redo: the few rays the ordered fast path hands back (see k_trace_closest4)
                     const float4 a = reinterpret_cast<const float4*>(rays + rid)[0], b = reinterpret_cast<const float4*>(rays + rid)[1];
                     ridx = rid; ro = V3(a.x, a.y, a.z); t_min = a.w; closest = b.w;
-                    d = normalize(V3(b.x, b.y, b.z));
+                    const RaySetup rs = ray_setup(V3(b.x, b.y, b.z));
+                    d = rs.d; inv[0] = rs.ix; inv[1] = rs.iy; inv[2] = rs.iz;
                     o[0] = ro.x; o[1] = ro.y; o[2] = ro.z;
-                    { float dd[3] = {d.x, d.y, d.z};
-#pragma unroll
-                      for (int i = 0; i < 3; i++) { float di = dd[i]; if (di == 0.f) di = 0.000001f; inv[i] = 1.0f / di; } }
                     sp = 0; any_hit = false; best_t = 0.f; best_u = 0.f; best_v = 0.f; best_slot = -1;
-                    Slab s0 = slab(B.root_box, B.root_box + 3, o, inv, t_min);
-                    cur = (s0.tf > s0.tn && closest > s0.tn) ? 0 : NONE;
+                    cur = root_passes(B, o, inv, t_min, closest) ? 0 : NONE;
                     have = true;
                 }
                 const uint32_t want = (uint32_t)__popcll(need);
@@ -324,35 +342,10 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
         do {
             if (have) {
                 bool done = false;
-                if (cur == NONE) {
-                    bool found = false;
-                    while (sp > 0) {
-                        --sp;
-                        uint2 e = (sp < MR_LDS_STACK) ? lds_stack[sp * MR_TRACE_BLOCK] : spill[sp - MR_LDS_STACK];
-                        if (closest > __uint_as_float(e.y)) { cur = (int)e.x; found = true; break; }
-                    }
-                    if (!found) done = true;
-                }
+                if (cur == NONE && !pop_deferred(lds_stack, spill, sp, closest, cur)) done = true;
                 if (!done) {
-                    if (cur >= 0) {
-                        const WideNode* __restrict__ nd = B.nodes + cur;
-                        const float4 q0 = reinterpret_cast<const float4*>(nd)[0];
-                        const float4 q1 = reinterpret_cast<const float4*>(nd)[1];
-                        const float4 q2 = reinterpret_cast<const float4*>(nd)[2];
-                        const float4 q3 = reinterpret_cast<const float4*>(nd)[3];
-                        const float lmin[3] = {q0.x, q0.y, q0.z}, lmax[3] = {q0.w, q1.x, q1.y};
-                        const float rmin[3] = {q1.z, q1.w, q2.x}, rmax[3] = {q2.y, q2.z, q2.w};
-                        const int left = __float_as_int(q3.x), right = __float_as_int(q3.y);
-                        Slab sl = slab(lmin, lmax, o, inv, t_min);
-                        Slab sr = slab(rmin, rmax, o, inv, t_min);
-                        if (sl.tf > sl.tn) {
-                            uint2 e; e.x = (uint32_t)left; e.y = __float_as_uint(sl.tn);
-                            if (sp < MR_LDS_STACK) lds_stack[sp * MR_TRACE_BLOCK] = e;
-                            else if (sp < MR_STACK) spill[sp - MR_LDS_STACK] = e;
-                            if (sp < MR_STACK) sp++;
-                        }
-                        cur = (sr.tf > sr.tn && closest > sr.tn) ? right : NONE;
-                    } else {
+                    if (cur >= 0) (void)wide_visit(B, cur, o, inv, t_min, closest, lds_stack, spill, sp);   // a full stack drops the entry, as the reference does
+                    else {
                         const int slot = ~cur;
                         cur = NONE;
                         const TriRec* __restrict__ tr = B.tris + slot;
@@ -370,15 +363,12 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
                                 const v3 Q = cross(Tv, E1);
                                 const float v = dot(d, Q) * invDet;
                                 if (!(v < 0 || u + v > 1)) {
-                                    if (ANY) { any_hit = true; done = true; }
-                                    else {
-                                        const float t = dot(E2, Q) * invDet;
-                                        if (!FRONT || (t > t_min && t <= closest)) {
-                                            any_hit = true;
-                                            closest = fminf(t, closest);
-                                            if (t <= closest) { best_u = u; best_v = v; best_slot = slot; }
-                                            best_t = closest;
-                                        }
+                                    const float t = dot(E2, Q) * invDet;
+                                    if (!FRONT || (t > t_min && t <= closest)) {
+                                        any_hit = true;
+                                        closest = fminf(t, closest);
+                                        if (t <= closest) { best_u = u; best_v = v; best_slot = slot; }
+                                        best_t = closest;
                                     }
                                 }
                             }
@@ -387,28 +377,15 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
                 }
                 if (done) {
                     have = false;
-                    if (ANY) hit_out[ridx] = any_hit ? 1 : 0;
-                    else {
-                        TraceOut r; r.hit = any_hit; r.t = best_t; r.u = best_u; r.v = best_v; r.slot = best_slot; r.d = d;
-                        v3 p, nn; int pr;
-                        finish_closest(B, r, ro, p, nn, pr);
-                        if (rec) {
-                            float4 o0, o1;
-                            o0.x = p.x; o0.y = p.y; o0.z = p.z; o0.w = __int_as_float(any_hit ? 1 : 0);
-                            o1.x = nn.x; o1.y = nn.y; o1.z = nn.z; o1.w = best_t;
-                            reinterpret_cast<float4*>(rec + ridx)[0] = o0; reinterpret_cast<float4*>(rec + ridx)[1] = o1;
-                        }
-                        if (hit_out) hit_out[ridx] = any_hit ? 1 : 0;
-                        if (t_out) t_out[ridx] = best_t;
-                        if (pos_out) st3(pos_out, ridx, p);
-                        if (nrm_out) st3(nrm_out, ridx, nn);
-                        if (prim_out) prim_out[ridx] = pr;
-                    }
+                    TraceOut r; r.hit = any_hit; r.t = best_t; r.u = best_u; r.v = best_v; r.slot = best_slot; r.d = d;
+                    v3 p, nn; int pr;
+                    finish_closest(B, r, ro, p, nn, pr);
+                    write_closest(rec, hit_out, t_out, pos_out, nrm_out, prim_out, ridx, any_hit, best_t, p, nn, pr);
                 }
             }
         } while (__popcll(__ballot(have)) >= MR_REFILL || (exhausted && __ballot(have)));
     }
-    if (stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[redo ? 10 : (ANY ? 0 : 1)], (unsigned long long)n);   // [10]: rays the ordered fast path handed back
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[redo ? 10 : 1], (unsigned long long)n);   // [10]: rays the ordered fast path handed back
 }
 
 
@@ -680,12 +657,8 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                     const float4 l1 = make_float4(__uint_as_float(h1.x), __uint_as_float(h1.y), __uint_as_float(h1.z), __uint_as_float(h1.w));
                     const float4 l2 = make_float4(__uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(h2.z), __uint_as_float(h2.w));
                     const float4 l3 = make_float4(__uint_as_float(rf.x), __uint_as_float(rf.y), __uint_as_float(rf.z), __uint_as_float(rf.w));
-                    const float ex0 = (l2.y - ox) * ix, ex1 = (l3.x - ox) * ix;
-                    const float ey0 = (l2.z - oy) * iy, ey1 = (l3.y - oy) * iy;
-                    const float ez0 = (l2.w - oz) * iz, ez1 = (l3.z - oz) * iz;
-                    const bool nx_ = ix < 0.f, ny_ = iy < 0.f, nz_ = iz < 0.f;           // the reference's swap (see slab(): a NaN plane stays in its slot)
-                    const float etn = fmaxf(fmaxf(fmaxf(nx_ ? ex1 : ex0, ny_ ? ey1 : ey0), nz_ ? ez1 : ez0), t_min);
-                    const float etf = fminf(fminf(nx_ ? ex0 : ex1, ny_ ? ey0 : ey1), nz_ ? ez0 : ez1);
+                    const Slab es = leaf_slab(l2, l3, ox, oy, oz, ix, iy, iz, t_min);
+                    const float etn = es.tn, etf = es.tf;
                     if (COUNT) c_boxes++;
                     if (etf > etn && t_max > etn) { hit = tri_accepts_regs<TIMED == 2>(l0, l1, l2, ro, d); if (COUNT) c_leaves++; }
                 } else {
@@ -858,17 +831,14 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest4(BvhView B, co
                 if (!have && idx < chunk_end) {
                     const float4 a = reinterpret_cast<const float4*>(rays + idx)[0], b = reinterpret_cast<const float4*>(rays + idx)[1];
                     ridx = idx; ro = V3(a.x, a.y, a.z); t_min = a.w; closest = b.w;
-                    d = normalize(V3(b.x, b.y, b.z));
+                    const RaySetup rs = ray_setup(V3(b.x, b.y, b.z));
+                    d = rs.d; ix = rs.ix; iy = rs.iy; iz = rs.iz;
                     ox = ro.x; oy = ro.y; oz = ro.z;
-                    { float dx = d.x, dy = d.y, dz = d.z;
-                      if (dx == 0.f) dx = 0.000001f; if (dy == 0.f) dy = 0.000001f; if (dz == 0.f) dz = 0.000001f;
-                      ix = 1.0f / dx; iy = 1.0f / dy; iz = 1.0f / dz; }
                     sp = 0; any_hit = false; need_redo = false; best_u = 0.f; best_v = 0.f; best_slot = -1; neg_t = NO_NEG;
                     rc = ray_margins(scene_bs, ox, oy, oz, ix, iy, iz);
                     const float o3[3] = {ox, oy, oz}, i3[3] = {ix, iy, iz};
-                    Slab s0 = slab(B.root_box, B.root_box + 3, o3, i3, t_min);
                     if (COUNT) c_boxes++;
-                    cur = (s0.tf > s0.tn && closest > s0.tn) ? 0 : NONE;
+                    cur = root_passes(B, o3, i3, t_min, closest) ? 0 : NONE;
                     have = true;
                 }
                 const uint32_t want = (uint32_t)__popcll(need);
@@ -905,12 +875,8 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest4(BvhView B, co
                         const float4 l2 = make_float4(__uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(h2.z), __uint_as_float(h2.w));
                         const float4 l3 = make_float4(__uint_as_float(rf.x), __uint_as_float(rf.y), __uint_as_float(rf.z), __uint_as_float(rf.w));
                         // the reference tests a leaf iff its OWN box passes against the current `closest`
-                        const float ex0 = (l2.y - ox) * ix, ex1 = (l3.x - ox) * ix;
-                        const float ey0 = (l2.z - oy) * iy, ey1 = (l3.y - oy) * iy;
-                        const float ez0 = (l2.w - oz) * iz, ez1 = (l3.z - oz) * iz;
-                        const bool nx_ = ix < 0.f, ny_ = iy < 0.f, nz_ = iz < 0.f;       // the reference's swap (see slab(): a NaN plane stays in its slot)
-                        const float etn = fmaxf(fmaxf(fmaxf(nx_ ? ex1 : ex0, ny_ ? ey1 : ey0), nz_ ? ez1 : ez0), t_min);
-                        const float etf = fminf(fminf(nx_ ? ex0 : ex1, ny_ ? ey0 : ey1), nz_ ? ez0 : ez1);
+                        const Slab es = leaf_slab(l2, l3, ox, oy, oz, ix, iy, iz, t_min);
+                        const float etn = es.tn, etf = es.tf;
                         if (COUNT) c_boxes++;
                         if (etf > etn && closest == etn && any_hit) need_redo = true;
                         if (etf > etn && closest > etn) {
@@ -1009,22 +975,24 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_closest4(BvhView B, co
             if (neg_t != NO_NEG) r.t = neg_t;      // case (a): the reference's search ended at that triangle
             v3 p, nn_; int pr;
             finish_closest(B, r, ro, p, nn_, pr);
-            if (rec) {
-                float4 o0, o1;
-                o0.x = p.x; o0.y = p.y; o0.z = p.z; o0.w = __int_as_float(any_hit ? 1 : 0);
-                o1.x = nn_.x; o1.y = nn_.y; o1.z = nn_.z; o1.w = r.t;
-                reinterpret_cast<float4*>(rec + ridx)[0] = o0; reinterpret_cast<float4*>(rec + ridx)[1] = o1;
-            }
-            if (hit_out) hit_out[ridx] = any_hit ? 1 : 0;
-            if (t_out) t_out[ridx] = r.t;
-            if (pos_out) st3(pos_out, ridx, p);
-            if (nrm_out) st3(nrm_out, ridx, nn_);
-            if (prim_out) prim_out[ridx] = pr;
+            write_closest(rec, hit_out, t_out, pos_out, nrm_out, prim_out, ridx, any_hit, r.t, p, nn_, pr);
         }
     }
     if (COUNT && stats) { atomicAdd(&stats[5], c_boxes); atomicAdd(&stats[6], c_nodes); atomicAdd(&stats[7], c_leaves); atomicMax(&stats[9], (unsigned long long)c_maxsp); }
     if (stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats[1], (unsigned long long)n);
 }
+
+// Head sets (engine.hpp HeadSet) by `lane`, the stream role a launch of mirres_render runs under: launches that may overlap on different streams use different
+// sets. 0 the chain (and everything single-stream), 1 the bulk stream, 2 the path-tracing stream, 3 the final-stage stream, 4 the second path-tracing stream.
+// `fast`: the three consecutive sets of the ordered closest-hit path (+0 fast heads, +1 [0] redo count, +2 redo heads), which go with one redo list (mirres_bvh::redo).
+// Lanes 0-3 share HS_FAST, and lanes 2 and 3 share HS_PT_CLOSEST: of these only ONE traces closest-hit rays in a frame — the path-tracing queue (render.hip PB.q),
+// whose lane is 0, 1 or 2 by the number of streams; the initial / final-visibility queues (PB.qf, PB.qv — lane 3 is PB.qv) carry shadow rays only (cl_rays = nullptr),
+// so lane 3's `closest` and `fast` entries are never used. The second path-tracing stream (lane 4) does run beside the first and has sets and a redo list of its own.
+// Not covered: mirres_bvh_trace mode 2 also runs on lane 0's HS_FAST and redo list, so such an API call must not overlap a render of the same BVH (as before this table existed).
+struct LaneSets { int any, closest, fast, redo_list; };
+static const LaneSets lane_sets[5] = {{HS_CHAIN_ANY, HS_CHAIN_CLOSEST, HS_FAST, 0}, {HS_BULK_ANY, HS_BULK_CLOSEST, HS_FAST, 0}, {HS_PT_ANY, HS_PT_CLOSEST, HS_FAST, 0},
+                                      {HS_FIN_ANY, HS_PT_CLOSEST, HS_FAST, 0}, {HS_PT2_ANY, HS_PT2_CLOSEST, HS_FAST2, 1}};
+static uint32_t* heads_of(const mirres_bvh* bvh, int set) { return bvh->work + (size_t)set * MR_WSET; }
 
 static int persist_grid(size_t capacity);
 static int ensure_redo(mirres_bvh* bvh, int alt, size_t capacity) {
@@ -1039,9 +1007,9 @@ static int ensure_redo(mirres_bvh* bvh, int alt, size_t capacity) {
 template <bool COUNT>
 static int closest_fast(mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* rec, int32_t* hit, float* t, float* pos,
                         float* nrm, int32_t* prim, unsigned long long* stats, hipStream_t s, int lane = 0) {
-    const int alt = lane == 4 ? 1 : 0;
+    const int alt = lane_sets[lane].redo_list;
     int rc = ensure_redo(bvh, alt, capacity); if (rc) return rc;
-    uint32_t* const w = bvh->work + (alt ? 12 : 4) * MR_WSET;   // set +0 fast heads, set +1 [0] redo count, set +2 redo heads
+    uint32_t* const w = heads_of(bvh, lane_sets[lane].fast);   // set +0 fast heads, set +1 [0] redo count, set +2 redo heads
     MR_HIP(hipMemsetAsync(w, 0, 3 * MR_WSET * sizeof(uint32_t), s));
     k_trace_closest4<COUNT><<<persist_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, w, rec, hit, t, pos, nrm, prim,
                                                                                bvh->redo[alt], w + MR_WSET, stats);
@@ -1050,18 +1018,26 @@ static int closest_fast(mirres_bvh* bvh, const Ray* rays, const uint32_t* d_coun
     return 0;
 }
 
-static int g_timed_tag = 0;   // set by trace_any_queue for event-timed launches (mirres_ctx_set_instrument bit 1)
 static int any_top();
-template <bool COUNT>
-static void launch_any4q(const mirres_bvh* bvh, int grid, const Ray* rays, const uint32_t* d_count, uint32_t cap, uint32_t* head, int32_t* hit,
-                         unsigned long long* stats, hipStream_t s) {
-    const int top = (bvh->T - 1 >= 341 * 4) ? any_top() : 0;
-    if (top == 85 && !COUNT && g_timed_tag) k_trace_any4q<false, 85, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, cap, head, hit, stats);
-    else if (top == 85) k_trace_any4q<COUNT, 85><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, cap, head, hit, stats);
-    else if (top == 341) k_trace_any4q<COUNT, 341><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, cap, head, hit, stats);
-    else if (!COUNT && g_timed_tag) k_trace_any4q<false, 0, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, cap, head, hit, stats);
-    else k_trace_any4q<COUNT, 0><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, cap, head, hit, stats);
-}
+// One launch of the shadow-ray kernel and the one place that picks its instantiation k_trace_any4q<COUNT, TOPN, TIMED, SRC>.
+// TOPN: MIRRES_TOPQ, on trees that have 341 full 4-wide nodes' worth of internal nodes; the 341-node prefix only for plain ray queues under the plain name.
+// TIMED = 1, the second name of the production kernel (`timed`: mirres_ctx_set_instrument bit 1), exists for the 0- and 85-node forms of ray and pixel-pair queues.
+struct AnyLaunch {
+    const mirres_bvh* bvh; const Ray* rays; const uint32_t* d_count; size_t capacity; uint32_t* heads; int32_t* hit; unsigned long long* stats; hipStream_t s;
+    RaySrc src = RaySrc{nullptr, nullptr, 0.f, 0};
+    template <bool COUNT, int TOPN, int TIMED, int SRC> void go() const {
+        k_trace_any4q<COUNT, TOPN, TIMED, SRC><<<persist_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, heads, hit, stats, src);
+    }
+    template <bool COUNT, int TOPN, int SRC, bool FRONT> void tagged(bool timed) const {
+        if constexpr (!COUNT && !FRONT) { if (timed) return go<false, TOPN, 1, SRC>(); }
+        go<COUNT, TOPN, FRONT ? 2 : 0, SRC>();
+    }
+    template <bool COUNT, int SRC = 0, bool FRONT = false> void launch(bool timed = false) const {
+        const int top = (bvh->T - 1 >= 341 * 4) ? any_top() : 0;
+        if constexpr (SRC == 0 && !FRONT) { if (top == 341) return go<COUNT, 341, 0, 0>(); }
+        if (top == 85) tagged<COUNT, 85, SRC, FRONT>(timed); else tagged<COUNT, 0, SRC, FRONT>(timed);
+    }
+};
 static int closest_mode() {   // 4 (default): ordered compressed 4-wide fast path + reference-order redo of the flagged rays; MIRRES_CLOSEST=2: reference order for all
     static int m = -1;
     if (m < 0) { const char* e = getenv("MIRRES_CLOSEST"); m = (e && e[0] == '2') ? 2 : 4; }
@@ -1092,47 +1068,36 @@ static int any_top() {
     static const int topq = [] { const char* e = getenv("MIRRES_TOPQ"); const int v = e ? atoi(e) : 0; return (v == 85 || v == 341) ? v : 0; }();
     return topq;
 }
-// the spatial pass's queue of (origin pixel, light pixel) pairs: same kernel, rays formed at the refill (head set of lane 0 ... 4 as below)
+// the spatial pass's queue of (origin pixel, light pixel) pairs: same kernel, rays formed at the refill. head_set: a unit of the band pipeline (HS_CHAIN_ANY, HS_BAND1,
+// HS_BAND2); < 0: the lane's own
 int trace_any_items_queue(const mirres_bvh* bvh, const uint2* items, const RaySrc& src, const uint32_t* d_count, size_t capacity, int32_t* hit,
                           unsigned long long* stats, hipStream_t s, int lane, int timed, bool heads_clean, int head_set) {
-    static const int set_of_lane[5] = {0, 7, 9, 11, 15};
-    uint32_t* const heads = bvh->work + (head_set >= 0 ? head_set : set_of_lane[lane]) * MR_WSET;      // head_set: a unit of the band pipeline (sets 0, 17, 18)
+    uint32_t* const heads = heads_of(bvh, head_set >= 0 ? head_set : lane_sets[lane].any);
     if (!heads_clean) MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
-    const Ray* q = reinterpret_cast<const Ray*>(items);
-    const int grid = persist_grid(capacity); const uint32_t cap = (uint32_t)capacity;
-    const int top = (bvh->T - 1 >= 341 * 4 && any_top() == 85) ? 85 : 0;
-    if (top == 85 && timed) k_trace_any4q<false, 85, 1, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), q, d_count, cap, heads, hit, stats, src);
-    else if (top == 85) k_trace_any4q<false, 85, 0, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), q, d_count, cap, heads, hit, stats, src);
-    else if (timed) k_trace_any4q<false, 0, 1, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), q, d_count, cap, heads, hit, stats, src);
-    else k_trace_any4q<false, 0, 0, 1><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), q, d_count, cap, heads, hit, stats, src);
+    AnyLaunch{bvh, reinterpret_cast<const Ray*>(items), d_count, capacity, heads, hit, stats, s, src}.launch<false, 1>(timed != 0);
     MR_LAUNCH_CHECK("trace_any_items_queue");
     return 0;
 }
 int trace_any_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, int32_t* hit,
                     unsigned long long* stats, hipStream_t s, int lane, int timed, bool heads_clean) {
-    g_timed_tag = timed;
-    static const int set_of_lane[5] = {0, 7, 9, 11, 15};                    // launches that may overlap on different streams use different head sets
-    uint32_t* const heads = bvh->work + set_of_lane[lane] * MR_WSET;
+    uint32_t* const heads = heads_of(bvh, lane_sets[lane].any);
     if (!heads_clean) MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));   // heads_clean: the previous consumer zeroed them (k_spatial_resolve in mirres_render's chain)
-    launch_any4q<false>(bvh, persist_grid(capacity), rays, d_count, (uint32_t)capacity, heads, hit, stats, s);
+    AnyLaunch{bvh, rays, d_count, capacity, heads, hit, stats, s}.launch<false>(timed != 0);
     MR_LAUNCH_CHECK("trace_any_queue");
     return 0;
 }
-// occlusion with hits in front of the origin only (API head set 2): render_dump.py's batch_intersector
+// occlusion with hits in front of the origin only: render_dump.py's batch_intersector
 int trace_any_front_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, int32_t* hit, hipStream_t s) {
-    uint32_t* const heads = bvh->work + 2 * MR_WSET;
+    uint32_t* const heads = heads_of(bvh, HS_API_ANY);
     MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
-    const int grid = persist_grid(capacity);
-    if (bvh->T - 1 >= 341 * 4 && any_top() == 85) k_trace_any4q<false, 85, 2><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, heads, hit, nullptr);
-    else k_trace_any4q<false, 0, 2><<<grid, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, heads, hit, nullptr);
+    AnyLaunch{bvh, rays, d_count, capacity, heads, hit, nullptr, s}.launch<false, 0, true>();
     MR_LAUNCH_CHECK("trace_any_front_queue");
     return 0;
 }
 int trace_closest_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
                         unsigned long long* stats, hipStream_t s, int lane, int32_t* prim) {
     if (closest_mode() == 4) return closest_fast<false>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, prim, stats, s, lane);
-    static const int set_of_lane[5] = {1, 8, 10, 10, 16};
-    uint32_t* const heads = bvh->work + set_of_lane[lane] * MR_WSET;
+    uint32_t* const heads = heads_of(bvh, lane_sets[lane].closest);
     MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
     k_trace_persist<false><<<persist_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, heads, nullptr, out,
                                                                              nullptr, nullptr, nullptr, prim, stats);
@@ -1142,20 +1107,21 @@ int trace_closest_queue(const mirres_bvh* bvh, const Ray* rays, const uint32_t* 
 int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, int32_t* hit,
                             unsigned long long* stats, hipStream_t s, int reference_order) {
     if (reference_order) {   // visit counts of the reference's own traversal (bvh_hit order, no early exit) on the same rays — SURVEY §8d's accounting basis
-        k_trace_any<true><<<trace_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, hit, nullptr, stats);
+        k_trace_any<<<trace_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, hit, nullptr, stats);
         MR_LAUNCH_CHECK("trace_any_queue_counted(ref)");
         return 0;
     }
-    MR_HIP(hipMemsetAsync(bvh->work, 0, MR_WSET * sizeof(uint32_t), s));
-    launch_any4q<true>(bvh, persist_grid(capacity), rays, d_count, (uint32_t)capacity, bvh->work, hit, stats, s);
+    uint32_t* const heads = heads_of(bvh, HS_CHAIN_ANY);
+    MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
+    AnyLaunch{bvh, rays, d_count, capacity, heads, hit, stats, s}.launch<true>();
     MR_LAUNCH_CHECK("trace_any_queue_counted");
     return 0;
 }
 int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32_t* d_count, size_t capacity, HitRec* out,
                                 unsigned long long* stats, hipStream_t s, int32_t* prim) {
     if (closest_mode() == 4) return closest_fast<true>(const_cast<mirres_bvh*>(bvh), rays, d_count, capacity, out, nullptr, nullptr, nullptr, nullptr, prim, stats, s);
-    k_trace_closest<true><<<trace_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, out, nullptr, nullptr,
-                                                                           nullptr, nullptr, prim, nullptr, stats);
+    k_trace_closest<<<trace_grid(capacity), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), rays, d_count, (uint32_t)capacity, out, nullptr, nullptr,
+                                                                    nullptr, nullptr, prim, nullptr, stats);
     MR_LAUNCH_CHECK("trace_closest_queue_counted");
     return 0;
 }
@@ -1178,28 +1144,22 @@ extern "C" int mirres_bvh_trace(mirres_bvh_t* bvh, const float* rays, int n, int
         if (!hit) { set_error("mirres_bvh_trace: occlusion needs hit[]"); return MIRRES_E_ARG; }
         return trace_any_front_queue(bvh, r, nullptr, (size_t)n, hit, s);
     }
-    if (mode == 4) {
-        if (counters) { set_error("mirres_bvh_trace: mode 4 has no per-ray counters"); return MIRRES_E_ARG; }
-        MR_HIP(hipMemsetAsync(bvh->work + 3 * MR_WSET, 0, MR_WSET * sizeof(uint32_t), s));
-        k_trace_persist<false, true><<<persist_grid((size_t)n), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, bvh->work + 3 * MR_WSET, hit, nullptr, t, pos, normal,
-                                                                                       prim, nullptr);
-        MR_LAUNCH_CHECK("mirres_bvh_trace");
-        return MIRRES_OK;
-    }
+    if (mode == 4 && counters) { set_error("mirres_bvh_trace: mode 4 has no per-ray counters"); return MIRRES_E_ARG; }
     if (mode == 0) {
         if (!hit) { set_error("mirres_bvh_trace: any-hit needs hit[]"); return MIRRES_E_ARG; }
-        if (counters) k_trace_any<true><<<g, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, hit, counters, nullptr);
+        if (counters) k_trace_any<<<g, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, hit, counters, nullptr);
         else {
-            MR_HIP(hipMemsetAsync(bvh->work + 2 * MR_WSET, 0, MR_WSET * sizeof(uint32_t), s));
-            launch_any4q<false>(bvh, persist_grid((size_t)n), r, nullptr, (uint32_t)n, bvh->work + 2 * MR_WSET, hit, nullptr, s);
+            uint32_t* const heads = heads_of(bvh, HS_API_ANY);
+            MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
+            AnyLaunch{bvh, r, nullptr, (size_t)n, heads, hit, nullptr, s}.launch<false>();   // always under the plain (untimed) name
         }
-    } else {
-        if (counters) k_trace_closest<true><<<g, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, nullptr, hit, t, pos, normal, prim, counters, nullptr);
-        else {
-            MR_HIP(hipMemsetAsync(bvh->work + 3 * MR_WSET, 0, MR_WSET * sizeof(uint32_t), s));
-            k_trace_persist<false><<<persist_grid((size_t)n), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, bvh->work + 3 * MR_WSET, hit, nullptr, t, pos, normal,
-                                                                                    prim, nullptr);
-        }
+    // what remains: mode 1 with per-ray counters (the simple reference-order kernel), then mode 1 without and mode 4 (never with counters: rejected above)
+    } else if (mode == 1 && counters) k_trace_closest<<<g, MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, nullptr, hit, t, pos, normal, prim, counters, nullptr);
+    else {   // modes 1 and 4: the reference order from the queue; mode 4 counts hits in (t_min, t_max] only
+        uint32_t* const heads = heads_of(bvh, HS_API_CLOSEST);
+        MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
+        if (mode == 4) k_trace_persist<true><<<persist_grid((size_t)n), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, heads, hit, nullptr, t, pos, normal, prim, nullptr);
+        else k_trace_persist<false><<<persist_grid((size_t)n), MR_TRACE_BLOCK, 0, s>>>(bvh->view(), r, nullptr, (uint32_t)n, heads, hit, nullptr, t, pos, normal, prim, nullptr);
     }
     MR_LAUNCH_CHECK("mirres_bvh_trace");
     return MIRRES_OK;
@@ -1213,8 +1173,9 @@ extern "C" int mirres_debug_any_stats(mirres_bvh_t* bvh, const float* rays, int 
     unsigned long long* d = nullptr;
     MR_HIP(hipMalloc(&d, 12 * sizeof(unsigned long long)));
     MR_HIP(hipMemsetAsync(d, 0, 12 * sizeof(unsigned long long), s));
-    MR_HIP(hipMemsetAsync(bvh->work + 2 * MR_WSET, 0, MR_WSET * sizeof(uint32_t), s));
-    launch_any4q<true>(bvh, persist_grid((size_t)n), reinterpret_cast<const Ray*>(rays), nullptr, (uint32_t)n, bvh->work + 2 * MR_WSET, hit, d, s);
+    uint32_t* const heads = heads_of(bvh, HS_API_ANY);
+    MR_HIP(hipMemsetAsync(heads, 0, MR_WSET * sizeof(uint32_t), s));
+    AnyLaunch{bvh, reinterpret_cast<const Ray*>(rays), nullptr, (size_t)n, heads, hit, d, s}.launch<true>();
     MR_HIP(hipStreamSynchronize(s));
     MR_HIP(hipMemcpy(h_stats, d, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     MR_HIP(hipFree(d));

@@ -10,6 +10,19 @@
 #define MR_QSTRIDE 32
 #define MR_WSET ((MR_NQ + 1) * MR_QSTRIDE)   // + one more line: word MR_NQ * MR_QSTRIDE = bit mask of the sub-queues found empty (grab_chunk)
 #define MR_WSETS 19
+// The head sets of mirres_bvh::work by user. Launches that may be in flight together use different sets (bvh_trace.hip lane_sets: which stream of mirres_render uses which).
+enum HeadSet {
+    HS_CHAIN_ANY = 0, HS_CHAIN_CLOSEST = 1,       // the chain stream (and every single-stream caller)
+    HS_API_ANY = 2, HS_API_CLOSEST = 3,           // mirres_bvh_trace / mirres_debug_any_stats
+    HS_FAST = 4,                                  // 4-6: ordered closest hit: fast heads, redo count, redo heads
+    HS_BULK_ANY = 7, HS_BULK_CLOSEST = 8,         // bulk stream
+    HS_PT_ANY = 9, HS_PT_CLOSEST = 10,            // path-tracing stream
+    HS_FIN_ANY = 11,                              // final-stage stream
+    HS_FAST2 = 12,                                // 12-14: ordered closest hit of the second path-tracing stream
+    HS_PT2_ANY = 15, HS_PT2_CLOSEST = 16,         // second path-tracing stream
+    HS_BAND1 = 17, HS_BAND2 = 18                  // the second / third chain stream of the band pipeline (render.hip)
+};
+static_assert(HS_BAND2 < MR_WSETS && HS_FAST2 + 2 < HS_PT2_ANY && HS_FAST + 2 < HS_BULK_ANY, "every head set lies inside mirres_bvh::work and the three-set groups do not overlap their neighbours");
 // Binned-SAH top of the private steering hierarchy (bvh_build.hip): clusters = maximal subtrees whose leaves share MR_SAH_PREFIX key bits (of 38), at most
 // MR_SAH_LEVELS levels rebuilt above them. The shadow-ray kernel's private stack (bvh_trace.hip MR_ANY_STACK) is sized from these two.
 #define MR_SAH_PREFIX 24
@@ -99,9 +112,7 @@ struct mirres_bvh {
     uint32_t *p_keys = nullptr, *p_vals = nullptr, *p_range = nullptr; unsigned long long* p_key64 = nullptr; int32_t* p_info = nullptr; float* p_aabb = nullptr;
     int32_t* p_parent = nullptr; void *sah_state = nullptr, *sah_nodes = nullptr, *sah_bins = nullptr; int32_t *sah_iref = nullptr, *sah_inode = nullptr, *sah_top = nullptr;   // SAH top over prefix clusters (k_sah_*)
     float* root_box = nullptr;      // [6]
-    uint32_t* work = nullptr;       // [MR_WSETS * MR_WSET] head sets of the persistent traversal kernels: 0/1 chain, 2/3 API, 4-6 ordered closest + redo, 7/8 bulk stream, 9/10 path-tracing stream,
-                                    // 11 final-stage stream, 12-14 ordered closest + redo and 15/16 any / closest of the second path-tracing stream, 17/18 the second / third
-                                    // chain stream of the band pipeline (render.hip)
+    uint32_t* work = nullptr;       // [MR_WSETS * MR_WSET] head sets of the persistent traversal kernels (HeadSet above)
     unsigned long long* dbg = nullptr;   // see BvhView::dbg
     uint32_t* err = nullptr;             // see BvhView::err (hipHostMalloc, mapped: the host reads it without a copy)
     char* dump_pool = nullptr; size_t dump_pool_bytes = 0;   // mirres_dump_render: shadow rays / results / slots of one pixel chunk
@@ -110,10 +121,10 @@ struct mirres_bvh {
 };
 
 // One unit of the band pipeline (round 6, render.hip): the spatial pass of one sample restricted to a band of rows, on queue resources of its own so that units of
-// consecutive samples can be in flight on different streams. set 0 = the context's own buffers and head set 0.
+// consecutive samples can be in flight on different streams. set 0 = the context's own buffers and head set HS_CHAIN_ANY.
 struct ChainSet {
     mr::Ray* q = nullptr; int32_t* hit = nullptr; uint32_t* counter = nullptr; int32_t* slot = nullptr; uint32_t* mask = nullptr;
-    int head_set = 0; bool clean = false;      // clean: the set's last resolve left the ray counter and the work heads zeroed
+    int head_set = HS_CHAIN_ANY; bool clean = false;      // clean: the set's last resolve left the ray counter and the work heads zeroed
 };
 struct SpatialBand { int y0, y1, gen_y1; ChainSet* set; };   // the resolve covers rows [y0, y1), the generator [y0, gen_y1) (one more row: the fused temporal merge of the
                                                              // band's last row may recompute the spatial merge of the pixel below, whose rays must be in THIS unit's queue)

@@ -902,7 +902,7 @@ int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, co
     // a unit of the band pipeline (render.hip) works on rows [y0, y1) with the queue, hit bits, per-pixel slots and work heads of its chain stream's set
     Ray* const q_rays = band ? band->set->q : ctx->any_rays; int32_t* const q_hit = band ? band->set->hit : ctx->any_hit; uint32_t* const q_count = band ? band->set->counter : &ctx->counters[0];
     int32_t* const px_slot = band ? band->set->slot : ctx->slot_a; uint32_t* const px_mask = band ? band->set->mask : ctx->mask_a;
-    const int head_set = band ? band->set->head_set : 0;
+    const int head_set = band ? band->set->head_set : HS_CHAIN_ANY;
     bool& clean = band ? band->set->clean : ctx->chain_clean;
     const int by0 = band ? band->y0 : 0, gen_rows = band ? band->gen_y1 - band->y0 : ctx->fy, res_rows = band ? band->y1 - band->y0 : ctx->fy;
     if (!(fold && clean)) MR_HIP(hipMemsetAsync(q_count, 0, sizeof(uint32_t), s));

@@ -346,7 +346,7 @@ static int band_count(const mirres_ctx* ctx, bool allowed) {   // MIRRES_BANDS: 
 static int chain_stream_count() { const char* e = getenv("MIRRES_CHAIN_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 3 ? 3 : n); }
 static int ensure_chain_sets(mirres_ctx* ctx, int S) {
     ChainSet& c0 = ctx->chain_sets[0];
-    c0.q = ctx->any_rays; c0.hit = ctx->any_hit; c0.counter = &ctx->counters[0]; c0.slot = ctx->slot_a; c0.mask = ctx->mask_a; c0.head_set = 0;
+    c0.q = ctx->any_rays; c0.hit = ctx->any_hit; c0.counter = &ctx->counters[0]; c0.slot = ctx->slot_a; c0.mask = ctx->mask_a; c0.head_set = HS_CHAIN_ANY;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t N = ctx->N, pairs = ctx->any_cap / 2;
     for (int t = 1; t < S; t++) {
@@ -358,7 +358,7 @@ static int ensure_chain_sets(mirres_ctx* ctx, int S) {
             ChainSet& c = ctx->chain_sets[t];
             c.q = reinterpret_cast<Ray*>(p); p += al(8 * pairs); c.hit = reinterpret_cast<int32_t*>(p); p += al(4 * ctx->any_cap);
             c.slot = reinterpret_cast<int32_t*>(p); p += al(4 * N); c.mask = reinterpret_cast<uint32_t*>(p); p += al(4 * N); c.counter = reinterpret_cast<uint32_t*>(p);
-            c.head_set = 16 + t;
+            c.head_set = HS_BAND1 + (t - 1);
         }
     }
     for (int t = 0; t < 3; t++) ctx->chain_sets[t].clean = false;

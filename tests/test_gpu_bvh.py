@@ -340,3 +340,62 @@ def test_deep_tree_private_stack_and_reference_stack(torch_cuda, oracle):
         open(os.path.join(rep, "deep_tree_stack.txt"), "w").write(
             "adversarial chain mesh T=%d: LBVH depth %d; reference stack deepest %d of 64; shadow-ray kernel's private stack deepest %d (bound 3 x (54 + ceil(log2 T)) = %d, capacity 256); overflows %d; "
             "64-byte records per ray %.1f\n" % (len(t), depth, deepest_ref, st[8], bound, st[11], st[3] / n))
+
+
+_TOPQ341_CHILD = r"""
+import ctypes as C, os, sys
+import numpy as np, torch
+import mirres_restir_nerf_mesh_amd as M
+from mirres_restir_nerf_mesh_amd.renderer_restir import restirbvhWorker
+from mirres_restir_nerf_mesh_amd._lib import lib, check
+from oracle import oracle
+assert os.environ["MIRRES_TOPQ"] == "341"
+v, t = M.scene.make_mesh(3, 16)
+assert len(t) - 1 >= 1364, len(t)                      # the staged top is only used when the tree has 341 full 4-wide nodes' worth of internal nodes
+w = restirbvhWorker(torch.from_numpy(v).cuda(), torch.from_numpy(t).cuda()); w.update_mesh(w.vrt, w.v_ind)
+info, aabb, _, _ = oracle.bvh_build(v, t)
+hw = 96; n = hw * hw
+eye, rd = M.scene.camera_rays(hw, hw)
+primary = oracle.make_rays(np.repeat(eye[None], n, 0), rd)
+prim = oracle.trace(info, aabb, v, t, primary, True)
+rng = np.random.default_rng(7)
+d2 = rng.normal(size=(n, 3)).astype(np.float32)
+d2[::17, 0] = 0.0
+o2 = (prim["pos"] + 0.01 * d2).astype(np.float32)
+secondary = oracle.make_rays(o2[prim["hit"] > 0], d2[prim["hit"] > 0])
+if len(secondary) % 64 == 0: secondary = secondary[:-1]
+assert len(primary) % 64 == 0 and len(secondary) % 64 != 0 and len(secondary) > 64, (len(primary), len(secondary))   # one full set, one with a ragged last chunk
+L = lib(); L.mirres_debug_any_stats.argtypes = [C.c_void_p] * 6; L.mirres_debug_any_stats.restype = C.c_int
+for name, rays in (("primary", primary), ("secondary", secondary)):
+    k = len(rays)
+    ref = oracle.trace(info, aabb, v, t, rays, True)["hit"]
+    front = oracle.occluded_front(info, aabb, v, t, rays)
+    assert (ref > 0).any() and (ref == 0).any(), name          # hits and misses
+    dr = torch.from_numpy(rays).cuda()
+    def trace(mode, counters=False):
+        hit = torch.full((k,), -1, dtype=torch.int32, device="cuda"); cnt = torch.zeros((k, 4), dtype=torch.int32, device="cuda")
+        check(lib().mirres_bvh_trace(w.h, dr.data_ptr(), k, mode, hit.data_ptr(), None, None, None, None, cnt.data_ptr() if counters else None, None), name)
+        torch.cuda.synchronize()
+        return hit.cpu().numpy()
+    assert np.array_equal(trace(0), ref), name + " mode 0"
+    assert np.array_equal(trace(3), front), name + " mode 3"
+    assert np.array_equal(trace(0, True), ref), name + " mode 0, reference order"
+    st = (C.c_uint64 * 12)(); hit = torch.full((k,), -1, dtype=torch.int32, device="cuda")
+    check(L.mirres_debug_any_stats(w.h, dr.data_ptr(), k, hit.data_ptr(), st, None), "any stats")
+    assert np.array_equal(hit.cpu().numpy(), ref) and st[0] == k and st[11] == 0, name + " counting build"
+print("topq341 ok", len(primary), len(secondary))
+"""
+
+
+def test_shadow_rays_with_341_top_nodes_staged_in_lds(torch_cuda):
+    """MIRRES_TOPQ=341 makes the shadow-ray kernel read the compressed tree's first five levels from LDS (k_trace_any4q<., 341>); the knob is read once per
+    process, so one fresh child process builds test_trace_bit_exact's (subdiv 3, ground 16) mesh (T - 1 >= 1364, asserted there: below it the staged top is
+    not used) and traces the 96 x 96 primary rays and their secondary rays (a count that is no multiple of 64: a ragged last chunk) with mode 0, mode 3, mode 0
+    with per-ray counters (the reference-order kernel) and the counting build: mode 0 equals the oracle's hit, mode 3 the oracle's front-only answer.
+    This checks that the answers are right with the knob set; staging is result-neutral, so it cannot show that the 341-node form was the one launched."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MIRRES_TOPQ="341", PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", _TOPQ341_CHILD], env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    assert r.stdout.strip().splitlines()[-1].startswith("topq341 ok"), r.stdout[-1000:]
