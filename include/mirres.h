@@ -456,6 +456,44 @@ int mirres_mesh_compact(const float* verts, int V, const int32_t* tris, int T, c
 int mirres_mesh_components(const unsigned long long* sorted_keys, const int32_t* key_face, long long n_keys, int T, int32_t* label, int32_t* changed_flag,
                            int max_rounds, int* h_rounds, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------------------------------------------
+ * Quadric-error edge collapse (decimate.hip): decimate_mesh, meshutils.py:64-97, called by export_stage0 at nerf/renderer.py:566-567 — MeshLab's
+ * meshing_decimation_quadric_edge_collapse(targetfacenum, optimalplacement) as deterministic rounds of independent collapses (Garland & Heckbert 1997; DESIGN.md
+ * section 5.10).  One round is the five calls below in this order (mirres_dec_quadrics in the first round only) plus mirres_mesh_compact; the caller does the
+ * sorts between them.  Shared inputs, all device memory, indices in range (the caller checks): verts f32[V,3]; tris i32[T,3]; quadrics f64[V,10], the symmetric
+ * 4 x 4 matrix of a vertex as a00 a01 a02 a03 a11 a12 a13 a22 a23 a33; edge_keys u64[E] = the distinct undirected edge keys (min << 32 | max) of all face corners
+ * in ascending order — an edge's position in this list is its id — and edge_mult i32[E] how many corners carry each; corner_edge i32[3T] = the edge id of
+ * corner 3 f + k, the edge (v_k, v_k+1) of face f; vstart i32[V+1] / vcorner i32[3T] = the corners sorted by their vertex, STABLY (a vertex's corners ascend).
+ * Nothing here is a floating-point atomic: equal inputs give equal bytes.
+ * mirres_dec_vertex_flags (meshutils.py:64-97): vflag i32[V], bit 0 = on an edge with one face (boundary), bit 1 = on an edge with more than two faces.      */
+int mirres_dec_vertex_flags(const unsigned long long* edge_keys, const int32_t* edge_mult, int E, int V, int32_t* vflag, void* stream);
+/* mirres_dec_quadrics (meshutils.py:64-97): quadrics[v] = sum over v's corners in CSR order of the face's plane quadric (unit normal, weight = area; a face with
+ * a zero cross product adds nothing) followed by, for the face's edges k and k + 2 at that corner where edge_mult == 1, the plane through the edge perpendicular
+ * to the face, weight = 1.0 * squared edge length.  fp64 on the fp32 positions.                                                                            */
+int mirres_dec_quadrics(const float* verts, int V, const int32_t* tris, int T, const int32_t* vstart, const int32_t* vcorner, const int32_t* corner_edge,
+                        const int32_t* edge_mult, int E, double* quadrics, void* stream);
+/* mirres_dec_edge (meshutils.py:64-97; optimalplacement as MeshLab's flag): per edge (a, b), Q = Q[a] + Q[b]; position f32[E,3] = the solution of the 3 x 3 system
+ * by cofactors rounded to fp32 (optimalplacement and |det| > 1e-9 * max|entry|^3 and finite), else the cheapest of p_a, p_b, fp32(midpoint), ties in that order;
+ * cost f64[E] = max(v^T Q v, 0) at that fp32 position; flags i32[E], 0 = valid: 1 multiplicity not 1 or 2, or an end point on an edge with more than two faces;
+ * 2 link condition (distinct common neighbours != multiplicity, or both (a, c0, c1) and (b, c0, c1) are faces); 4 interior edge between two boundary vertices;
+ * 8 a face around a or b (not both) would turn its normal by acos(0.2) or more or lose its area; 16 cost (as fp32) or position not finite.
+ * keys u64[E] = (bits of (float)cost) << 32 | edge id for a valid edge, 0x7FFFFFFFFFFFFFFF otherwise.                                                       */
+int mirres_dec_edge(const float* verts, const double* quadrics, int V, const int32_t* tris, int T, const int32_t* vstart, const int32_t* vcorner,
+                    const unsigned long long* edge_keys, const int32_t* edge_mult, const int32_t* vflag, int E, int optimalplacement, double* cost,
+                    float* position, int32_t* flags, unsigned long long* keys, void* stream);
+/* mirres_dec_select (meshutils.py:64-97): cand i32[n_cand] edge ids (the caller's cut: the smallest valid keys).  Every candidate takes the 64-bit atomicMin of
+ * its key into vkey u64[V] (scratch, set inside) over its region = a, b and every vertex of a face around a or b; selected u8[n_cand] = 1 where the whole region
+ * still holds the candidate's key.  Selected regions are pairwise disjoint and the smallest candidate is always selected.  d_count i32[1] (device) = their number. */
+int mirres_dec_select(const int32_t* tris, int T, int V, const int32_t* vstart, const int32_t* vcorner, const unsigned long long* edge_keys, int E,
+                      const unsigned long long* keys, const int32_t* cand, int n_cand, unsigned long long* vkey, uint8_t* selected, int32_t* d_count, void* stream);
+/* mirres_dec_apply (meshutils.py:64-97), IN PLACE: per selected edge verts[a] = position, quadrics[a] += quadrics[b] (one addition per component), remap[b] = a
+ * (remap i32[V], scratch, identity otherwise); per face the indices go through remap; keep_face u8[T] = 0 for a face with a repeated index (its indices are left),
+ * used_vertex u8[V] = 1 for the vertices of the kept faces.  The caller compacts with mirres_mesh_compact(keep_face) and the quadrics by used_vertex.
+ * h_selected = the count mirres_dec_select left in d_count; BLOCKS until it is on the host.                                                                 */
+int mirres_dec_apply(float* verts, double* quadrics, int V, int32_t* tris, int T, const unsigned long long* edge_keys, int E, const float* position,
+                     const int32_t* cand, const uint8_t* selected, int n_cand, int32_t* remap, uint8_t* keep_face, uint8_t* used_vertex, const int32_t* d_count,
+                     int* h_selected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,7 +143,12 @@ SIGNATURES = {
     "mirres_mesh_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "mirres_mesh_compact": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
     "mirres_mesh_components": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int), vp]),
-    "mirres_ctx_reserve": (C.c_int, [vp, C.c_int]),
+    "mirres_dec_vertex_flags": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "mirres_dec_quadrics": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]),
+    "mirres_dec_edge": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "mirres_dec_select": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "mirres_dec_apply": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+    "mirres_ctx_reserve":(C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mirres_render_finish": (C.c_int, [vp, PARGS, C.POINTER(vp), vp]),

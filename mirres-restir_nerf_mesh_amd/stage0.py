@@ -7,10 +7,13 @@ nvdiffrast behind it.
     unseen = mark_unseen_triangles(v, t, mvps, H, W)       # :1400-1434 on raster.rasterize
     v, t = remove_masked_trigs(v, t, unseen, dilation=5)   # meshutils.py:100-130
     v, t = clean_mesh(v, t, min_f=8, min_d=5)              # meshutils.py:183-225 (repair=True, remesh=False)
+    v, t = decimate_mesh(v, t, 3e5)                        # meshutils.py:64-97 (:566-567): quadric edge collapse in deterministic rounds, csrc/decimate.hip
     export_stage0(save_path, ckpt=..., cameras=(mvps, H, W))
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
-when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair, remeshing and decimation are not built.
+when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
+collapses independent sets of edges round by round instead of one edge at a time from a global heap, without MeshLab's quality / normal / planar extras, and may
+end one face below the target.
 Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
 import ctypes as C
 import os
@@ -22,7 +25,7 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
-           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "index_to_world", "synthetic_volume", "export_stage0"]
+           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "export_stage0"]
 
 
 def _dev():
@@ -233,6 +236,106 @@ def clean_mesh(vertices, triangles, min_f=8, min_d=5, max_rounds=0, log=None):
         log("[INFO] mesh cleaning: %s --> %s, %s --> %s" % (tuple(v0.shape), tuple(v.shape), tuple(t0.shape), tuple(t.shape)))
     return v, t
 
+DEC_MAX_ROUNDS = 4096                        # decimate_mesh's cap on rounds (max_rounds = 0)
+DEC_KEY_NONE = 0x7FFFFFFFFFFFFFFF            # the key of an edge that may not be collapsed
+DEC_FLAGS = {"multiplicity": 1, "link": 2, "boundary": 4, "flip": 8, "finite": 16}      # bits of decimate_round's per-edge flags (include/mirres.h)
+
+
+def _dec_topology(t, V):
+    """The sorts of one decimation round: the distinct undirected edges in key order with their multiplicity, every corner's edge, and the vertex -> corner CSR
+    (stable sort: a vertex's corners 3 f + k ascend)."""
+    t64 = t.to(torch.int64)
+    a = t64.reshape(-1); b = t64[:, [1, 2, 0]].reshape(-1)                        # corner 3 f + k: edge (v_k, v_k+1) of face f
+    ekeys, corner_edge, emult = torch.unique((torch.minimum(a, b) << 32) | torch.maximum(a, b), sorted=True, return_inverse=True, return_counts=True)
+    vcorner = torch.sort(a, stable=True).indices.to(torch.int32).contiguous()
+    vstart = torch.zeros(V + 1, dtype=torch.int32, device=t.device)
+    vstart[1:] = torch.cumsum(torch.bincount(a, minlength=V), 0)
+    return dict(ekeys=ekeys.contiguous(), emult=emult.to(torch.int32).contiguous(), corner_edge=corner_edge.to(torch.int32).contiguous(), vcorner=vcorner, vstart=vstart,
+                E=int(ekeys.shape[0]))
+
+
+def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True, mark=None):
+    """One round of decimate_mesh on device tensors whose indices are in range (vertices f32 [V, 3], quadrics f64 [V, 10] or None before the first round, triangles
+    i32 [T, 3], T > target) -> (vertices, quadrics, triangles, info); the inputs are left as they are.  info: the round's edge list and CSR (`ekeys`, `emult`,
+    `corner_edge`, `vcorner`, `vstart`, `E`), `vflag`, the quadrics the round started from (`quadrics`), per edge `cost` f64, `position` f32 [E, 3], `flags` i32
+    (DEC_FLAGS; 0 = valid) and `keys` i64, the candidates `cand` (edge ids, cheapest first), `sel` u8 per candidate, and `selected`, their number (0: nothing could
+    be collapsed, the mesh comes back as it was).  `mark(name)` is called after each stage ("edges", "k_dec_edge", "select", "apply") for timing."""
+    L = lib(); s = stream_ptr
+    mark = mark or (lambda name: None)
+    v, t = vertices.clone(), triangles.clone()
+    V, T = int(v.shape[0]), int(t.shape[0]); dev = v.device
+    tp = _dec_topology(t, V); E = tp["E"]
+    vflag = torch.empty(V, dtype=torch.int32, device=dev)
+    check(L.mirres_dec_vertex_flags(ptr(tp["ekeys"]), ptr(tp["emult"]), E, V, ptr(vflag), s()), "mirres_dec_vertex_flags")
+    if quadrics is None:
+        q = torch.empty((V, 10), dtype=torch.float64, device=dev)
+        check(L.mirres_dec_quadrics(ptr(v), V, ptr(t), T, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["corner_edge"]), ptr(tp["emult"]), E, ptr(q), s()), "mirres_dec_quadrics")
+        q0 = q.clone()
+    else:
+        q0 = quadrics; q = quadrics.clone()
+    mark("edges")
+    cost = torch.empty(E, dtype=torch.float64, device=dev); pos = torch.empty((E, 3), dtype=torch.float32, device=dev)
+    flags = torch.empty(E, dtype=torch.int32, device=dev); keys = torch.empty(E, dtype=torch.int64, device=dev)
+    check(L.mirres_dec_edge(ptr(v), ptr(q), V, ptr(t), T, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["ekeys"]), ptr(tp["emult"]), ptr(vflag), E, 1 if optimalplacement else 0,
+                            ptr(cost), ptr(pos), ptr(flags), ptr(keys), s()), "mirres_dec_edge")
+    mark("k_dec_edge")
+    skeys = torch.sort(keys).values
+    n_cand = min((T - int(target) + 1) // 2, int((skeys != DEC_KEY_NONE).sum()))      # only the cheapest ceil((T - target) / 2) valid edges stand this round
+    info = dict(tp, vflag=vflag, quadrics=q0, cost=cost, position=pos, flags=flags, keys=keys, cand=skeys[:0].to(torch.int32), sel=torch.empty(0, dtype=torch.uint8, device=dev), selected=0)
+    if n_cand <= 0:
+        return v, q, t, info
+    cand = (skeys[:n_cand] & 0xFFFFFFFF).to(torch.int32).contiguous()
+    vkey = torch.empty(V, dtype=torch.int64, device=dev); sel = torch.empty(n_cand, dtype=torch.uint8, device=dev); cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    check(L.mirres_dec_select(ptr(t), T, V, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["ekeys"]), E, ptr(keys), ptr(cand), n_cand, ptr(vkey), ptr(sel), ptr(cnt), s()), "mirres_dec_select")
+    mark("select")
+    remap = torch.empty(V, dtype=torch.int32, device=dev); keep = torch.empty(T, dtype=torch.uint8, device=dev); used = torch.empty(V, dtype=torch.uint8, device=dev)
+    h = C.c_int(0)
+    check(L.mirres_dec_apply(ptr(v), ptr(q), V, ptr(t), T, ptr(tp["ekeys"]), E, ptr(pos), ptr(cand), ptr(sel), n_cand, ptr(remap), ptr(keep), ptr(used), ptr(cnt), C.byref(h), s()),
+          "mirres_dec_apply")
+    scratch = torch.empty(int(L.mirres_mesh_scratch_bytes(V, T)), dtype=torch.uint8, device=dev)
+    ov = torch.empty_like(v); ot = torch.empty_like(t); counts = (C.c_int * 2)()
+    check(L.mirres_mesh_compact(ptr(v), V, ptr(t), T, ptr(keep), ptr(ov), ptr(ot), ptr(scratch), counts, s()), "mirres_mesh_compact")
+    q = q[used != 0].contiguous()                                                     # the vertices the kept faces use, in their old order: what the compaction keeps
+    if q.shape[0] != counts[0]:
+        raise _lib.MirresError("decimate_round: %d quadrics for %d compacted vertices" % (q.shape[0], counts[0]))
+    mark("apply")
+    info.update(cand=cand, sel=sel, selected=int(h.value), remap=remap, keep=keep)
+    return ov[: counts[0]].contiguous(), q, ot[: counts[1]].contiguous(), info
+
+
+def decimate_mesh(vertices, triangles, target, optimalplacement=True, max_rounds=0, log=None):
+    """decimate_mesh (meshutils.py:64-97; nerf/renderer.py:566-567) -> (vertices f32 [V', 3], triangles i32 [T', 3]) with target - 1 <= T' <= target: quadric-error
+    edge collapse (Garland & Heckbert 1997) in rounds, every round collapsing an independent set of the cheapest valid edges (decimate_round; csrc/decimate.hip,
+    DESIGN.md section 5.10).  Surviving vertices and faces keep their order; equal inputs give equal bytes.  `optimalplacement`: the new vertex minimises the summed
+    quadric where the system can be solved, else (and always without it) it is the cheapest of the two end points and their midpoint.  target >= T (or T == 0)
+    returns the input.  A round without a valid edge (stall) or `max_rounds` rounds (0: DEC_MAX_ROUNDS) end the run early with one [WARN] line."""
+    v, t = _verts(vertices), _tris(triangles)
+    V, T0 = int(v.shape[0]), int(t.shape[0]); target = int(target)
+    if T0 == 0 or target >= T0:
+        return v, t
+    if target < 0:
+        raise ValueError("decimate_mesh: target %d" % target)
+    if not bool(torch.isfinite(v).all()):
+        raise ValueError("decimate_mesh: non-finite vertex positions")
+    if int(t.min()) < 0 or int(t.max()) >= V:
+        raise ValueError("decimate_mesh: face index out of range")
+    if T0 > 0x7FFFFFFF // 3:
+        raise ValueError("decimate_mesh: %d faces do not fit 32-bit corner indices" % T0)
+    cap = DEC_MAX_ROUNDS if int(max_rounds) <= 0 else min(int(max_rounds), DEC_MAX_ROUNDS)
+    ov, ot, q, rounds, why = v, t, None, 0, None
+    while ot.shape[0] > target:
+        if rounds >= cap:
+            why = "%d rounds done (max_rounds)" % rounds; break
+        ov, q, ot, info = decimate_round(ov, q, ot, target, optimalplacement)
+        if info["selected"] == 0:
+            why = "no edge can be collapsed after %d rounds (stall)" % rounds; break
+        rounds += 1
+    if why:
+        (log or print)("[WARN] mesh decimation stopped at %d faces, target %d: %s" % (ot.shape[0], target, why))
+    if log:
+        log("[INFO] mesh decimation: %s --> %s, %s --> %s" % (tuple(v.shape), tuple(ov.shape), tuple(t.shape), tuple(ot.shape)))
+    return ov, ot
+
 
 def synthetic_volume(resolution=64, sdf=False):
     """An analytic density (or signed distance) of a unit-free scene for smoke runs and timings: a ball with a dent (radius 0.6 at the default threshold) and a small floater far from it
@@ -249,14 +352,15 @@ def synthetic_volume(resolution=64, sdf=False):
 
 
 def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, density_thresh=10.0, mesh=None, cameras=None, dilation=5, min_f=8, min_d=5,
-                  decimate_target=3e5, overwrite=False, log=print):
+                  decimate_target=3e5, optimalplacement=True, overwrite=False, log=print):
     """NeRFRenderer.export_stage0 (nerf/renderer.py:498-570) -> path of the written mesh_0.ply.
     Exactly one geometry source, or a volume together with the checkpoint that masks it:
       ckpt    a stage-0 checkpoint dict (top-level `mean_density`, `model` -> `density_grid` [cascade, S^3]): cascade 0 at the grid's own resolution (:511-515),
               iso = min(mean_density, density_thresh) (:506);
       volume  a dense [R, R, R] sigma volume (iso as for ckpt when one is given, else `iso` or density_thresh; with ckpt and not sdf it is masked by the grid,
               :532-539) or, with sdf, a signed distance extracted as (-volume, 0) (:549);
-      mesh    (vertices, triangles) of a foreign mesh in world space: cull and clean only.
+      mesh    (vertices, triangles) of a foreign mesh in world space: cull, clean and decimate only.
+    Above decimate_target (> 0) triangles the cleaned mesh is decimated to it (:566-567, decimate_mesh).
     cameras = (mvps [B, 4, 4], H, W) switches the visibility cull on (:557-560)."""
     from . import checkpoint as CK
     if mesh is not None and (ckpt is not None or volume is not None):
@@ -303,7 +407,7 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
         v, t = remove_masked_trigs(v, t, unseen, dilation=dilation, log=log)
     v, t = clean_mesh(v, t, min_f=min_f, min_d=min_d, log=log)
     if decimate_target > 0 and t.shape[0] > decimate_target:
-        log("[WARN] %d triangles exceed --decimate_target %d: quadric decimation is not built, the mesh is kept as it is" % (t.shape[0], int(decimate_target)))
+        v, t = decimate_mesh(v, t, int(decimate_target), optimalplacement=optimalplacement, log=log)
     if t.shape[0] == 0:
         raise RuntimeError("export_stage0: the mesh is empty after cleaning")
     os.makedirs(save_path, exist_ok=True)

@@ -3,7 +3,9 @@
     python scripts/dev_stage0_time.py [--sizes 128 512] [--repeat 5] [--out profiles/stage0_time.txt]
 
 Per size: marching cubes count (classification + both scans + the blocking read of the totals), emit, and the whole call; the six-camera visibility cull
-at 800 x 800; cleaning.  Every figure is the median of `--repeat` runs after one warm-up run, bracketed by events on the work's own stream; next to the
+at 800 x 800; cleaning; quadric decimation of the cleaned mesh (to --decimate_target, or to a fifth of its faces when it has fewer than that: one run, per round
+the faces, the collapses and the device time of the edge build (the torch sorts, vertex flags, in round 1 the quadrics), k_dec_edge, the candidate cut with
+claim / select, and apply with compaction).  Every other figure is the median of `--repeat` runs after one warm-up run, bracketed by events on the work's own stream; next to the
 marching-cubes times stands the volume traffic they imply (4 bytes per grid point and pass, two passes) in GB/s.  No speed gate reads this file."""
 import argparse, ctypes as C, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -21,8 +23,26 @@ def timed(fn, repeat):
     return statistics.median(ms), min(ms), max(ms), out
 
 
+def decimate_timed(v, t, target):
+    """stage0.decimate_mesh's loop with events between the stages of every round -> (v, t, rows of (faces before, collapses, {stage: ms}))."""
+    rows, q = [], None
+    while t.shape[0] > target and len(rows) < stage0.DEC_MAX_ROUNDS:
+        ev = [("start", torch.cuda.Event(enable_timing=True))]; ev[0][1].record()
+
+        def mark(name):
+            e = torch.cuda.Event(enable_timing=True); e.record(); ev.append((name, e))
+        T0 = t.shape[0]
+        v, q, t, info = stage0.decimate_round(v, q, t, target, True, mark)
+        torch.cuda.synchronize()
+        rows.append((T0, info["selected"], {ev[i][0]: ev[i - 1][1].elapsed_time(ev[i][1]) for i in range(1, len(ev))}))
+        if info["selected"] == 0:
+            break
+    return v, t, rows
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--decimate_target", type=float, default=3e5)
     p.add_argument("--sizes", type=int, nargs="+", default=[128, 512]); p.add_argument("--repeat", type=int, default=5)
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "stage0_time.txt"))
     a = p.parse_args()
@@ -59,6 +79,19 @@ def main():
         lines.append("  mark unseen, 6 x 800^2 %9.3f ms (%.3f .. %.3f)   BVH build + 6 rasterised views; %d of %d unseen" % (m_s[0], m_s[1], m_s[2], int(unseen.sum()), T))
         lines.append("  dilate 5 + remove      %9.3f ms (%.3f .. %.3f)   -> V %d, T %d" % (m_r[0], m_r[1], m_r[2], v2.shape[0], t2.shape[0]))
         lines.append("  clean_mesh             %9.3f ms (%.3f .. %.3f)   -> V %d, T %d" % (m_k[0], m_k[1], m_k[2], m_k[3][0].shape[0], m_k[3][1].shape[0]))
+        vk, tk = m_k[3]
+        target = int(a.decimate_target) if tk.shape[0] > a.decimate_target else tk.shape[0] // 5
+        stage0.decimate_mesh(vk, tk, target); torch.cuda.synchronize()                       # warm-up
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); vd, td, rows = decimate_timed(vk, tk, target); e1.record(); torch.cuda.synchronize()
+        tot = {k: sum(r[2].get(k, 0.0) for r in rows) for k in ("edges", "k_dec_edge", "select", "apply")}
+        lines.append("  decimate_mesh          %9.3f ms (one run)             T %d -> %d (target %d), V -> %d; %d rounds, collapses first %d, last %d" % (
+            e0.elapsed_time(e1), tk.shape[0], td.shape[0], target, vd.shape[0], len(rows), rows[0][1] if rows else 0, rows[-1][1] if rows else 0))
+        lines.append("    all rounds: edge build (sorts) %.3f ms, k_dec_edge %.3f ms, cut + claim + select %.3f ms, apply + compact %.3f ms" % (tot["edges"], tot["k_dec_edge"], tot["select"], tot["apply"]))
+        for i, (T0, nsel, ms) in enumerate(rows):
+            if i < 3 or i >= len(rows) - 2:
+                lines.append("    round %3d: T %8d, %7d collapses; edge build %.3f, k_dec_edge %.3f, select %.3f, apply %.3f ms" % (
+                    i + 1, T0, nsel, ms.get("edges", 0.0), ms.get("k_dec_edge", 0.0), ms.get("select", 0.0), ms.get("apply", 0.0)))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -3,14 +3,16 @@ file train_stage1.py, evaluate.py, export_stage1.py and albedo_eval.py start fro
 
     python scripts/export_stage0.py --workspace <ws> [--ckpt <ws>/checkpoints/ngp_stage0_epXXXX.pth] [--density_thresh 10]        # the S^3 density grid (S = 128)
     python scripts/export_stage0.py --workspace <ws> --volume sigma_512.npy [--ckpt ...] [--iso v] [--sdf]                         # a denser dumped volume
-    python scripts/export_stage0.py --workspace <ws> --mesh foreign.ply --transforms <data>/transforms_train.json                  # cull and clean only
+    python scripts/export_stage0.py --workspace <ws> --mesh foreign.ply --transforms <data>/transforms_train.json                  # cull, clean and decimate only
     python scripts/export_stage0.py --synthetic [--workspace <ws>]                                                                 # analytic volume, smoke run
 
 Exactly one geometry source: the checkpoint's grid (default: the latest stage-0 checkpoint of the workspace), `--volume` (a [R, R, R] float .npy the user dumps
 from the reference's density network; with `--ckpt` and without `--sdf` it is masked by the checkpoint's grid and cut at min(mean_density, density_thresh),
 otherwise at `--iso` / `--density_thresh`; `--sdf`: a signed distance, extracted as (-volume, 0)), or `--mesh`.  `--transforms` (with --H/--W/--downscale/--scale/
 --offset as in evaluate.py) gives the training cameras of the visibility cull (--mesh_visibility_culling, which -O switches on); without it nothing is culled.
-Quadric decimation is not built: above `--decimate_target` triangles one warning is printed and the mesh is kept."""
+Above `--decimate_target` triangles (default 3e5 as in the reference's main.py; 0 switches it off) the cleaned mesh is decimated to it by quadric edge collapse
+(stage0.decimate_mesh: deterministic rounds of independent collapses, the result has the target's face count or one less; `--no_optimal_placement` places a
+collapsed vertex at the cheapest of the two end points and their midpoint instead of the quadric's minimum).  This holds for `--mesh` as well."""
 import argparse, glob, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,11 +21,12 @@ def build_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--workspace"); p.add_argument("--ckpt", default=None); p.add_argument("--density_thresh", type=float, default=10.0)
     p.add_argument("--volume", default=None); p.add_argument("--iso", type=float, default=None); p.add_argument("--sdf", action="store_true")
-    p.add_argument("--mesh", default=None, help="a foreign mesh (PLY): visibility cull and cleaning only")
+    p.add_argument("--mesh", default=None, help="a foreign mesh (PLY): visibility cull, cleaning and decimation only")
     p.add_argument("--transforms", default=None); p.add_argument("--H", type=int, default=800); p.add_argument("--W", type=int, default=800)
     p.add_argument("--downscale", type=int, default=1); p.add_argument("--scale", type=float, default=1.0); p.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0])
     p.add_argument("--visibility_mask_dilation", type=int, default=5); p.add_argument("--clean_min_f", type=int, default=8); p.add_argument("--clean_min_d", type=float, default=5)
-    p.add_argument("--decimate_target", type=float, default=3e5)
+    p.add_argument("--decimate_target", type=float, default=3e5, help="decimate the cleaned mesh to this many triangles when it has more (0: never)")
+    p.add_argument("--no_optimal_placement", action="store_true", help="decimation: the cheapest of the end points and the midpoint instead of the quadric's minimum")
     p.add_argument("--out", default=None); p.add_argument("--overwrite", action="store_true"); p.add_argument("--synthetic", action="store_true")
     p.add_argument("--resolution", type=int, default=64, help="--synthetic: the analytic volume's resolution")
     return p
@@ -85,7 +88,7 @@ def main(argv=None):
     torch.cuda.set_device(0)
     log = lambda m: print(m, flush=True)
     kw = dict(density_thresh=a.density_thresh, iso=a.iso, sdf=a.sdf, dilation=a.visibility_mask_dilation, min_f=a.clean_min_f, min_d=a.clean_min_d,
-              decimate_target=a.decimate_target, overwrite=a.overwrite, log=log)
+              decimate_target=a.decimate_target, optimalplacement=not a.no_optimal_placement, overwrite=a.overwrite, log=log)
     if a.synthetic:
         kw["volume"] = stage0.synthetic_volume(a.resolution, sdf=a.sdf)
     elif a.mesh:
