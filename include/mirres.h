@@ -494,6 +494,36 @@ int mirres_dec_apply(float* verts, double* quadrics, int V, int32_t* tris, int T
                      const int32_t* cand, const uint8_t* selected, int n_cand, int32_t* remap, uint8_t* keep_face, uint8_t* used_vertex, const int32_t* d_count,
                      int* h_selected, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------------------------------------------
+ * The stage-0 density network (density.hip): what NeRFRenderer.export_stage0 evaluates on its --mcubes_reso lattice (nerf/renderer.py:516-539) — self.density()
+ * = torch-ngp's GridEncoder forward (gridencoder/src/gridencoder.cu:87-196: 'hash', align_corners False, linear, D = 3, C = 2) -> the bias-free sigma_net
+ * 32 -> 64 (ReLU) -> 16, of which density needs output 0 only -> trunc_exp (activation.py:8-10: exp).  Table and weights fp32 (the reference runs this query under
+ * fp16 autocast; DESIGN.md sections 5.11 and 8).  Feature 2 l + c is channel c of level l.  The encoder's operation order is fixed and restated in DESIGN.md section
+ * 5.11; sigma is mrf_exp of a k-ascending fmaf chain per neuron.  A point with a coordinate outside [-bound, bound] (or not finite) has 32 zero features and sigma 1. */
+#define MIRRES_DENSITY_MAX_LEVELS 16
+typedef struct {
+    int num_levels;                                   /* 1 .. 16 */
+    int offsets[MIRRES_DENSITY_MAX_LEVELS + 1];       /* first table entry of every level, offsets[num_levels] = all entries (grid.py:124-135)                 */
+    int resolution[MIRRES_DENSITY_MAX_LEVELS];        /* the KERNEL's resolution, ceil(scale) + 1 (gridencoder.cu:139)                                         */
+    int hashed[MIRRES_DENSITY_MAX_LEVELS];            /* 1: get_grid_index's final stride exceeds the level's size, the index is the hash (gridencoder.cu:79)  */
+    float scale[MIRRES_DENSITY_MAX_LEVELS];           /* gridencoder.cu:138, computed once on the host                                                         */
+    const float* table;                               /* device f32 [entries, 2]: encoder.embeddings                                                           */
+    const float* w0;                                  /* device f32 [64, 32]: sigma_net.0.weight                                                               */
+    const float* w1;                                  /* device f32 [64]: row 0 of sigma_net.1.weight                                                          */
+} mirres_density_t;
+/* GridEncoder.__init__ (gridencoder/grid.py:104-135) and gridencoder.cu:137-139 on the host: fills num_levels, offsets, resolution, hashed and scale of `net` (the
+ * pointers are left alone) and returns the number of table entries, or a negative error.  per_level_scale = exp2(log2(desired / base) / (L - 1)) in double; the level's
+ * size = min(2^log2_hashmap_size, (ceil(base pls^l) + 1)^3) rounded up to a multiple of 8; scale[l] = float(exp2(double(float(l) * float(log2 pls)))) * float(base) - 1.0f,
+ * the product and the difference rounded to fp32 — gridencoder.cu:138's expression with a correctly rounded exp2f.                                                  */
+long long mirres_density_layout(int num_levels, int base_resolution, double desired_resolution, int log2_hashmap_size, mirres_density_t* net);
+/* self.density(pts) (nerf/renderer.py:527-530, one chunk): pos f32[n,3] -> sigma_out f32[n] and, when feat_out is not NULL, the encoder's output f32[n,32].       */
+int mirres_density_points(const mirres_density_t* net, const float* pos, long long n, float bound, float* sigma_out, float* feat_out, void* stream);
+/* nerf/renderer.py:516-541 in one launch: out f32[nx][ny][nz] = sigma at (xs[i], ys[j], zs[k]) — the axes are read, never recomputed (renderer.py:518-520 builds them
+ * with torch.linspace).  With grid_vol f32[S][S][S] (cubic; NULL: no mask) a lattice point whose nearest cell — F.interpolate(mode='nearest')'s index per axis, as in
+ * mirres_mc_mask_nearest — does not pass > thresh is exactly 0 and costs no table read: sigmas * mask, then nan_to_num(., 0) (renderer.py:532-541).                  */
+int mirres_density_volume(const mirres_density_t* net, const float* xs, int nx, const float* ys, int ny, const float* zs, int nz, float bound,
+                          const float* grid_vol, int S, float thresh, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

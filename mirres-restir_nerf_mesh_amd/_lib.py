@@ -62,6 +62,11 @@ class RenderArgs(C.Structure):
                 ("halo_recv1", C.c_int * 2), ("halo_time_stride", C.c_int), ("tex", C.POINTER(TexMat))]
 
 
+class DensityNet(C.Structure):
+    _fields_ = [("num_levels", C.c_int), ("offsets", C.c_int * 17), ("resolution", C.c_int * 16), ("hashed", C.c_int * 16), ("scale", C.c_float * 16),
+                ("table", vp), ("w0", vp), ("w1", vp)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int, vp)   # int halo(void* user, float* records, int sample, void* stream)
 
 
@@ -148,6 +153,9 @@ SIGNATURES = {
     "mirres_dec_edge": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "mirres_dec_select": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "mirres_dec_apply": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+    "mirres_density_layout": (C.c_longlong, [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(DensityNet)]),
+    "mirres_density_points": (C.c_int, [C.POINTER(DensityNet), vp, C.c_longlong, f32, vp, vp, vp]),
+    "mirres_density_volume": (C.c_int, [C.POINTER(DensityNet), vp, C.c_int, vp, C.c_int, vp, C.c_int, f32, vp, C.c_int, f32, vp, vp]),
     "mirres_ctx_reserve":(C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

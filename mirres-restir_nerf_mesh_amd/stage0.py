@@ -8,12 +8,14 @@ nvdiffrast behind it.
     v, t = remove_masked_trigs(v, t, unseen, dilation=5)   # meshutils.py:100-130
     v, t = clean_mesh(v, t, min_f=8, min_d=5)              # meshutils.py:183-225 (repair=True, remesh=False)
     v, t = decimate_mesh(v, t, 3e5)                        # meshutils.py:64-97 (:566-567): quadric edge collapse in deterministic rounds, csrc/decimate.hip
-    export_stage0(save_path, ckpt=..., cameras=(mvps, H, W))
+    field = DensityField.from_checkpoint(ck, bound=1.0)    # self.density (nerf/network.py:177-192): hash-grid encoder + sigma_net + exp, csrc/density.hip
+    vol = field.volume(512, grid_vol, thresh)              # :516-541: the --mcubes_reso lattice, masked by the density grid
+    export_stage0(save_path, ckpt=..., cameras=(mvps, H, W), resolution=512)
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
 when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
 collapses independent sets of edges round by round instead of one edge at a time from a global heap, without MeshLab's quality / normal / planar extras, and may
-end one face below the target.
+end one face below the target; the density network is evaluated in fp32 (the reference: fp16 autocast), unfused, and a NaN coordinate counts as out of bounds.
 Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
 import ctypes as C
 import os
@@ -25,7 +27,8 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
-           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "export_stage0"]
+           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "density_layout",
+           "synthetic_checkpoint", "export_stage0"]
 
 
 def _dev():
@@ -351,12 +354,150 @@ def synthetic_volume(resolution=64, sdf=False):
     return sd.contiguous() if sdf else torch.clamp(-40.0 * sd, min=0.0).contiguous()
 
 
+# the reference's hash-grid configuration (nerf/network.py:77 -> encoding.get_encoder -> GridEncoder defaults): 16 levels of 2 features, base 16, 2^19 entries,
+# desired_resolution = 2048 * bound
+DENSITY_LEVELS, DENSITY_BASE, DENSITY_LOG2_T, DENSITY_FINEST = 16, 16, 19, 2048
+
+
+def density_layout(bound=1.0, num_levels=DENSITY_LEVELS, base_resolution=DENSITY_BASE, log2_hashmap_size=DENSITY_LOG2_T, desired_resolution=None):
+    """GridEncoder.__init__'s level table (gridencoder/grid.py:104-135) and the kernel's per-level quantities (gridencoder.cu:137-139) -> (_lib.DensityNet with the
+    levels filled in and no pointers, total entries).  desired_resolution defaults to 2048 * bound (nerf/network.py:77).  No device is touched."""
+    net = _lib.DensityNet()
+    desired = float(DENSITY_FINEST * float(bound) if desired_resolution is None else desired_resolution)
+    total = int(lib().mirres_density_layout(int(num_levels), int(base_resolution), desired, int(log2_hashmap_size), C.byref(net)))
+    if total < 0:
+        check(total, "mirres_density_layout")
+    return net, total
+
+
+class DensityField:
+    """The stage-0 density network on the device (csrc/density.hip): sigma = exp(sigma_net(encoder(x))[..., 0]) as NeRFNetwork.density computes it
+    (nerf/network.py:177-192), table and weights in fp32.
+    table f32 [entries, 2] (encoder.embeddings), w0 f32 [64, 32] (sigma_net.0.weight), w1 f32 [16, 64] or its row 0 [64] (sigma_net.1.weight)."""
+
+    def __init__(self, table, w0, w1, bound=1.0, num_levels=DENSITY_LEVELS, base_resolution=DENSITY_BASE, log2_hashmap_size=DENSITY_LOG2_T, desired_resolution=None):
+        self.bound = float(bound)
+        if not (self.bound > 0 and np.isfinite(self.bound)):
+            raise ValueError("DensityField: bound %r" % (bound,))
+        self.net, self.entries = density_layout(self.bound, num_levels, base_resolution, log2_hashmap_size, desired_resolution)
+        table, w0, w1 = torch.as_tensor(table), torch.as_tensor(w0), torch.as_tensor(w1)
+        if table.dim() != 2 or tuple(table.shape) != (self.entries, 2):
+            raise ValueError("DensityField: a table of %s, the layout of bound %g has [%d, 2] (a checkpoint trained with another --bound?)" % (tuple(table.shape), self.bound, self.entries))
+        if tuple(w0.shape) != (64, 2 * DENSITY_LEVELS):
+            raise ValueError("DensityField: sigma_net.0.weight of %s, expected [64, 32]" % (tuple(w0.shape),))
+        if w1.dim() == 2:
+            if w1.shape[0] < 1 or w1.shape[1] != 64:
+                raise ValueError("DensityField: sigma_net.1.weight of %s, expected [16, 64]" % (tuple(w1.shape),))
+            w1 = w1[0]
+        if tuple(w1.shape) != (64,):
+            raise ValueError("DensityField: row 0 of sigma_net.1.weight of %s, expected [64]" % (tuple(w1.shape),))
+        dev = _dev()
+        self.table = table.detach().to(dev, torch.float32).contiguous()
+        self.w0 = w0.detach().to(dev, torch.float32).contiguous()
+        self.w1 = w1.detach().to(dev, torch.float32).contiguous()
+        self.net.table, self.net.w0, self.net.w1 = self.table.data_ptr(), self.w0.data_ptr(), self.w1.data_ptr()
+
+    @classmethod
+    def from_checkpoint(cls, ckpt, bound=1.0, **layout):
+        """A torch-ngp stage-0 checkpoint dict (or its `model` state dict): encoder.embeddings [N, 2], encoder.offsets [17], sigma_net.0.weight [64, 32],
+        sigma_net.1.weight [16, 64].  per_level_scale is not stored in a checkpoint, so the layout is recomputed from `bound` and compared with the stored offsets."""
+        model = ckpt["model"] if "model" in ckpt else ckpt
+        if any(k.startswith("encoder.encoder.") for k in model):
+            raise NotImplementedError("this checkpoint's encoder is tiny-cuda-nn's (encoder.encoder.params, --tcnn): not supported, only torch-ngp's GridEncoder "
+                                      "(encoder.embeddings / encoder.offsets) is")
+        for k in ("encoder.embeddings", "encoder.offsets", "sigma_net.0.weight", "sigma_net.1.weight"):
+            if k not in model:
+                raise KeyError("checkpoint has no %s: not a stage-0 density network" % k)
+        net, total = density_layout(bound, **layout)
+        want = [int(net.offsets[i]) for i in range(net.num_levels + 1)]
+        have = [int(o) for o in torch.as_tensor(model["encoder.offsets"]).reshape(-1).tolist()]
+        if have != want:
+            raise ValueError("the checkpoint's encoder.offsets (%d levels, %d entries) do not fit the hash-grid layout of --bound %g (%d levels, %d entries): "
+                             "pass the --bound the checkpoint was trained with" % (len(have) - 1, have[-1] if have else 0, float(bound), net.num_levels, total))
+        w0, w1 = torch.as_tensor(model["sigma_net.0.weight"]), torch.as_tensor(model["sigma_net.1.weight"])
+        if tuple(w0.shape) != (64, 32) or tuple(w1.shape) != (16, 64):
+            raise ValueError("sigma_net weights of %s and %s: the stage-0 density head is 32 -> 64 -> 16 without biases" % (tuple(w0.shape), tuple(w1.shape)))
+        if any(k in model for k in ("sigma_net.0.bias", "sigma_net.1.bias")):
+            raise ValueError("sigma_net has biases: the stage-0 density head is bias-free")
+        return cls(model["encoder.embeddings"], w0, w1, bound=bound, **layout)
+
+    def _points(self, x, want_feat):
+        x = torch.as_tensor(x).to(_dev(), torch.float32)
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError("DensityField: positions of %s, expected [n, 3]" % (tuple(x.shape),))
+        x = x.contiguous(); n = int(x.shape[0])
+        sigma = torch.empty(n, dtype=torch.float32, device=x.device)
+        feat = torch.empty((n, 2 * DENSITY_LEVELS), dtype=torch.float32, device=x.device) if want_feat else None
+        check(lib().mirres_density_points(C.byref(self.net), ptr(x) if n else None, n, self.bound, ptr(sigma) if n else None, ptr(feat) if (want_feat and n) else None,
+                                          stream_ptr()), "mirres_density_points")
+        return sigma, feat
+
+    def encode(self, x):
+        """x [n, 3] -> the encoder's output f32 [n, 32] (feature 2 l + c: channel c of level l); all zero for a point outside [-bound, bound]^3."""
+        return self._points(x, True)[1]
+
+    def density(self, x):
+        """x [n, 3] -> sigma f32 [n]."""
+        return self._points(x, False)[0]
+
+    def volume(self, resolution, grid_vol=None, thresh=None):
+        """sigma on the lattice torch.linspace(-1, 1, R) per axis (nerf/renderer.py:516-530; `resolution` one int or three) -> f32 [Rx, Ry, Rz].  With grid_vol
+        [S, S, S] and thresh: lattice points whose nearest grid cell does not pass > thresh are exactly 0 and are not evaluated (:532-541)."""
+        res = [int(resolution)] * 3 if np.ndim(resolution) == 0 else [int(r) for r in resolution]
+        if len(res) != 3 or min(res) < 1:
+            raise ValueError("DensityField.volume: resolution %r" % (resolution,))
+        dev = _dev()
+        axes = [torch.linspace(-1, 1, r).to(dev).contiguous() for r in res]      # built on the host and copied, as the reference does (:518-528)
+        g, S = None, 0
+        if grid_vol is not None:
+            if thresh is None:
+                raise ValueError("DensityField.volume: a grid_vol needs a thresh")
+            g = torch.as_tensor(grid_vol).to(dev, torch.float32).contiguous()
+            if g.dim() != 3 or len(set(g.shape)) != 1:
+                raise ValueError("DensityField.volume: a cubic grid_vol expected, got %s" % (tuple(g.shape),))
+            S = int(g.shape[0])
+        out = torch.empty(res, dtype=torch.float32, device=dev)
+        check(lib().mirres_density_volume(C.byref(self.net), ptr(axes[0]), res[0], ptr(axes[1]), res[1], ptr(axes[2]), res[2], self.bound, ptr(g), S,
+                                          float(thresh) if g is not None else 0.0, ptr(out), stream_ptr()), "mirres_density_volume")
+        return out
+
+
+def synthetic_checkpoint(S=16, radius=0.6):
+    """A stage-0 checkpoint dict (bound 1, the reference's hash-grid configuration) whose network encodes a ball, for tests and smoke runs: feature 0 of level 0
+    holds 2 - |x| at the level's vertices (vertex i of an axis sits at u = (i - 0.5) / 15), every other table entry is 0, W0[0, 0] = c = 1.5, W1[0, 0] = 1 and all
+    other weights are 0, so sigma = exp(1.5 * trilinear(2 - |x|)): it falls with the radius everywhere in the cube and passes mean_density = exp(1.5 * (2 - radius))
+    (8.17 at the default, below the default density_thresh) at |x| = radius up to level 0's interpolation error (< 0.01).  density_grid [1, S^3] (Morton order)
+    holds, per cell, the density a full cell diagonal nearer to the centre than the cell's own centre: an upper bound over the cell and its neighbours, as a trained
+    grid's running maximum is, so masking by it removes nothing the iso level would keep."""
+    S = int(S); c, A = 1.5, 2.0
+    net, total = density_layout(1.0)
+    table = torch.zeros((total, 2), dtype=torch.float32)
+    s1 = int(net.resolution[0]) + 1
+    i = np.arange(s1, dtype=np.float64)
+    ax = ((i - 0.5) / float(net.scale[0])) * 2.0 - 1.0
+    x, y, z = np.meshgrid(ax, ax, ax, indexing="ij")
+    idx = (np.arange(s1)[:, None, None] + np.arange(s1)[None, :, None] * s1 + np.arange(s1)[None, None, :] * s1 * s1).reshape(-1)
+    table[torch.from_numpy(idx), 0] = torch.from_numpy((A - np.sqrt(x * x + y * y + z * z)).reshape(-1).astype(np.float32))
+    w0 = torch.zeros((64, 32), dtype=torch.float32); w0[0, 0] = c
+    w1 = torch.zeros((16, 64), dtype=torch.float32); w1[0, 0] = 1.0
+    cc = (np.arange(S, dtype=np.float64) + 0.5) / S * 2.0 - 1.0
+    gx, gy, gz = np.meshgrid(cc, cc, cc, indexing="ij")
+    r = np.maximum(np.sqrt(gx * gx + gy * gy + gz * gz) - np.sqrt(3.0) * 2.0 / S, 0.0)
+    grid = np.zeros(S ** 3, np.float32)
+    grid[morton_indices(S).reshape(-1)] = np.exp(c * (A - r)).reshape(-1).astype(np.float32)
+    offsets = torch.tensor([int(net.offsets[k]) for k in range(net.num_levels + 1)], dtype=torch.int32)
+    return {"mean_density": float(np.exp(c * (A - float(radius)))),
+            "model": {"encoder.embeddings": table, "encoder.offsets": offsets, "sigma_net.0.weight": w0, "sigma_net.1.weight": w1,
+                      "density_grid": torch.from_numpy(grid)[None]}}
+
+
 def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, density_thresh=10.0, mesh=None, cameras=None, dilation=5, min_f=8, min_d=5,
-                  decimate_target=3e5, optimalplacement=True, overwrite=False, log=print):
+                  decimate_target=3e5, optimalplacement=True, overwrite=False, log=print, resolution=None, bound=1.0):
     """NeRFRenderer.export_stage0 (nerf/renderer.py:498-570) -> path of the written mesh_0.ply.
     Exactly one geometry source, or a volume together with the checkpoint that masks it:
       ckpt    a stage-0 checkpoint dict (top-level `mean_density`, `model` -> `density_grid` [cascade, S^3]): cascade 0 at the grid's own resolution (:511-515),
-              iso = min(mean_density, density_thresh) (:506);
+              iso = min(mean_density, density_thresh) (:506); with `resolution` (the reference's --mcubes_reso) given and different from the grid's S, the
+              checkpoint's density network (DensityField.from_checkpoint(ckpt, bound)) is evaluated on the resolution^3 lattice and masked by the grid (:516-541);
       volume  a dense [R, R, R] sigma volume (iso as for ckpt when one is given, else `iso` or density_thresh; with ckpt and not sdf it is masked by the grid,
               :532-539) or, with sdf, a signed distance extracted as (-volume, 0) (:549);
       mesh    (vertices, triangles) of a foreign mesh in world space: cull, clean and decimate only.
@@ -369,6 +510,8 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
         raise ValueError("export_stage0: nothing to extract from (ckpt, volume or mesh)")
     if sdf and volume is None:
         raise ValueError("export_stage0: sdf needs a volume")
+    if resolution is not None and (ckpt is None or volume is not None):
+        raise ValueError("export_stage0: resolution queries a checkpoint's density network: it needs ckpt and excludes a volume and a mesh")
     out = os.path.join(save_path, "mesh_0.ply")
     if os.path.exists(out) and not overwrite:
         raise FileExistsError("%s exists (pass overwrite to replace it)" % out)
@@ -394,6 +537,8 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
                 vol = mask_by_density_grid(vol, grid_vol, thresh)
             else:
                 thresh = float(iso) if iso is not None else float(density_thresh)
+        elif resolution is not None and int(resolution) != int(grid_vol.shape[0]):
+            vol = DensityField.from_checkpoint(ckpt, bound).volume(int(resolution), grid_vol, thresh)
         else:
             vol = grid_vol
         if iso is not None and not sdf:

@@ -2,12 +2,18 @@
 file train_stage1.py, evaluate.py, export_stage1.py and albedo_eval.py start from.
 
     python scripts/export_stage0.py --workspace <ws> [--ckpt <ws>/checkpoints/ngp_stage0_epXXXX.pth] [--density_thresh 10]        # the S^3 density grid (S = 128)
-    python scripts/export_stage0.py --workspace <ws> --volume sigma_512.npy [--ckpt ...] [--iso v] [--sdf]                         # a denser dumped volume
+    python scripts/export_stage0.py --workspace <ws> [--ckpt ...] --mcubes_reso 512 [--bound 1]                                    # the checkpoint's density network, as the reference
+    python scripts/export_stage0.py --workspace <ws> --volume sigma_512.npy [--ckpt ...] [--iso v] [--sdf]                         # a dense volume from elsewhere
     python scripts/export_stage0.py --workspace <ws> --mesh foreign.ply --transforms <data>/transforms_train.json                  # cull, clean and decimate only
     python scripts/export_stage0.py --synthetic [--workspace <ws>]                                                                 # analytic volume, smoke run
+    python scripts/export_stage0.py --synthetic --network [--mcubes_reso 48]                                                       # a synthetic checkpoint's network, end to end
 
-Exactly one geometry source: the checkpoint's grid (default: the latest stage-0 checkpoint of the workspace), `--volume` (a [R, R, R] float .npy the user dumps
-from the reference's density network; with `--ckpt` and without `--sdf` it is masked by the checkpoint's grid and cut at min(mean_density, density_thresh),
+Exactly one geometry source.  The checkpoint (default: the latest stage-0 checkpoint of the workspace): its density grid, or with `--mcubes_reso R` (the
+reference's flag, 512 in its main.py; unset: the grid) its density network evaluated on the R^3 lattice of [-1, 1]^3 on the HIP path (stage0.DensityField: torch-ngp
+hash-grid encoder + sigma_net + exp in fp32), masked by the grid and cut at min(mean_density, density_thresh).  `--bound` (default 1) is the --bound the checkpoint
+was trained with: it fixes the hash-grid layout and is checked against the checkpoint's offsets; tiny-cuda-nn checkpoints are not supported.  Or `--volume` (a
+[R, R, R] float .npy from elsewhere, e.g. a signed distance, which the density network cannot give; with `--ckpt` and without `--sdf` it is masked by the
+checkpoint's grid and cut at min(mean_density, density_thresh),
 otherwise at `--iso` / `--density_thresh`; `--sdf`: a signed distance, extracted as (-volume, 0)), or `--mesh`.  `--transforms` (with --H/--W/--downscale/--scale/
 --offset as in evaluate.py) gives the training cameras of the visibility cull (--mesh_visibility_culling, which -O switches on); without it nothing is culled.
 Above `--decimate_target` triangles (default 3e5 as in the reference's main.py; 0 switches it off) the cleaned mesh is decimated to it by quadric edge collapse
@@ -29,6 +35,9 @@ def build_parser():
     p.add_argument("--no_optimal_placement", action="store_true", help="decimation: the cheapest of the end points and the midpoint instead of the quadric's minimum")
     p.add_argument("--out", default=None); p.add_argument("--overwrite", action="store_true"); p.add_argument("--synthetic", action="store_true")
     p.add_argument("--resolution", type=int, default=64, help="--synthetic: the analytic volume's resolution")
+    p.add_argument("--mcubes_reso", type=int, default=None, help="evaluate the checkpoint's density network on this lattice (the reference's flag; unset: the density grid)")
+    p.add_argument("--bound", type=float, default=1.0, help="the --bound the checkpoint was trained with (fixes the hash-grid layout)")
+    p.add_argument("--network", action="store_true", help="--synthetic: a synthetic checkpoint's density network instead of the analytic volume")
     return p
 
 
@@ -41,6 +50,17 @@ def parse_args(argv=None):
     """Validates what can be validated without a device: conflicting sources, missing inputs, an existing mesh_0.ply without --overwrite."""
     p = build_parser()
     a = p.parse_args(argv)
+    if a.mcubes_reso is not None:
+        if a.mesh or a.volume or a.sdf:
+            p.error("--mcubes_reso queries the checkpoint's density network: it conflicts with --mesh, --volume and --sdf (a density is no signed distance)")
+        if a.mcubes_reso < 2:
+            p.error("--mcubes_reso %d: at least 2" % a.mcubes_reso)
+        if a.synthetic and not a.network:
+            p.error("--mcubes_reso with --synthetic needs --network (the analytic volume's size is --resolution)")
+    if a.network and not a.synthetic:
+        p.error("--network belongs to --synthetic")
+    if not (a.bound > 0):
+        p.error("--bound %g: a positive number" % a.bound)
     if a.synthetic:
         if a.mesh or a.volume or a.ckpt:
             p.error("--synthetic is a geometry source of its own: drop --mesh / --volume / --ckpt")
@@ -89,13 +109,17 @@ def main(argv=None):
     log = lambda m: print(m, flush=True)
     kw = dict(density_thresh=a.density_thresh, iso=a.iso, sdf=a.sdf, dilation=a.visibility_mask_dilation, min_f=a.clean_min_f, min_d=a.clean_min_d,
               decimate_target=a.decimate_target, optimalplacement=not a.no_optimal_placement, overwrite=a.overwrite, log=log)
-    if a.synthetic:
+    if a.synthetic and a.network:
+        kw["ckpt"] = stage0.synthetic_checkpoint(); kw["resolution"] = a.mcubes_reso if a.mcubes_reso is not None else 48
+    elif a.synthetic:
         kw["volume"] = stage0.synthetic_volume(a.resolution, sdf=a.sdf)
     elif a.mesh:
         kw["mesh"] = CK.read_ply(a.mesh)
     else:
         if a.ckpt:
             kw["ckpt"] = torch.load(a.ckpt, map_location="cpu", weights_only=False)
+            if a.mcubes_reso is not None:
+                kw["resolution"] = a.mcubes_reso; kw["bound"] = a.bound
         if a.volume:
             kw["volume"] = np.load(a.volume)
     if a.transforms:
