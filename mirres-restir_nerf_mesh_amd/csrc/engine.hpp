@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <vector>
 #include "../../include/mirres.h"
 
@@ -126,8 +127,15 @@ struct ChainSet {
     mr::Ray* q = nullptr; int32_t* hit = nullptr; uint32_t* counter = nullptr; int32_t* slot = nullptr; uint32_t* mask = nullptr;
     int head_set = HS_CHAIN_ANY; bool clean = false;      // clean: the set's last resolve left the ray counter and the work heads zeroed
 };
-struct SpatialBand { int y0, y1, gen_y1; ChainSet* set; };   // the resolve covers rows [y0, y1), the generator [y0, gen_y1) (one more row: the fused temporal merge of the
-                                                             // band's last row may recompute the spatial merge of the pixel below, whose rays must be in THIS unit's queue)
+struct SpatialBand { int y0, y1, gen_y1; };   // the resolve covers rows [y0, y1), the generator [y0, gen_y1) (one more row: the fused temporal merge of the band's
+                                              // last row may recompute the spatial merge of the pixel below, whose rays must be in THIS unit's queue); {0, fy, fy}: the frame
+struct FrameView {   // what is constant for one mirres_render call and its launches need, passed to them as an argument; the stepwise ABI passes a default-constructed one
+    int y_off = 0;                  // strip sharding: global row of local row 0 (the seeds follow global pixel coordinates)
+    const float* occ_own = nullptr; // strip sharding: occupancy with the halo rows zeroed (own-pixel tests of the spatial pass); NULL otherwise
+    const float* grec = nullptr;    // packed 64-byte G records for the neighbour gathers of k_spatial_resolve and the pixel-pair queue; NULL: the separate arrays
+    bool fold = false;              // the chain has its own stream and work heads: k_spatial_resolve leaves its queue set's ray counter and heads zeroed (ChainSet::clean)
+};
+namespace mr { struct RowSet { int a, b, mode; }; }   // spatial pass restricted to local rows. mode 0: every row; 1: rows in [a, b); 2: rows outside [a, b)  (the interior / border parts of a strip's spatial pass)
 
 struct mirres_ctx {
     int fx = 0, fy = 0; size_t N = 0;
@@ -153,18 +161,14 @@ struct mirres_ctx {
     float* pool = nullptr; size_t pool_floats = 0;
     // K-sample batch of the path-tracing stages (mirres_render): queues + per-slot state for K * N sample slots
     char* ptb = nullptr; size_t ptb_bytes = 0; int ptb_kcap = 0, ptb_kcap_age = 0, ptb_retry_wait = 64;   // ptb_kcap: largest batch the device could hold when an allocation last fell back (0 = never); clamped frames between speculative retries
-    int y_off = 0, full_fy = 0;     // strip sharding (mirres_render): global row of local row 0 and the global height; full_fy == 0: the frame is the whole image
-    int row_a = 0, row_b = 0, row_mode = 0;   // spatial pass restricted to local rows: 0 all, 1 inside [row_a, row_b), 2 outside (mirres_render's strip_overlap)
     hipStream_t halo_stream = nullptr; hipEvent_t ev_halo[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_halo_t; size_t ev_halo_t_used = 0;   // event pairs around the sampled native halo exchanges of the last frame (mirres_ctx_halo_time)
-    const float* occ_own = nullptr; // strip sharding: occupancy with the halo rows zeroed (own-pixel tests of the spatial pass); NULL otherwise
-    const float* grec = nullptr;    // set by mirres_render for the duration of a frame: packed 64-byte G records for the neighbour gathers of k_spatial_resolve
-    bool chain_reset = false, chain_clean = false;   // mirres_render's chain: k_spatial_resolve leaves the ray counter and the lane-0 work heads zeroed for the next sample
     hipStream_t aux_stream = nullptr, pt_stream = nullptr, pt_stream2 = nullptr, fin_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join_pt = nullptr, ev_join_pt2 = nullptr, ev_join_fin = nullptr;
     std::vector<hipEvent_t> ev_pt;   // k_pt_reduce hand-over between the two path-tracing streams
     std::vector<hipEvent_t> ev_sync; // cross-stream hand-offs of the batch pipeline (mirres_render)
-    // band pipeline of the per-sample chain (render.hip): up to two more chain streams with their own queue sets, one event per unit of a batch
+    // queue sets of the spatial pass: [0] = the buffers above (mirres_ctx_create); [1], [2] = the further chain streams of the band pipeline (render.hip), with one
+    // event per unit of a batch. `clean` is never set here: a frame works on copies of its own, so nothing it learns outlives it
     ChainSet chain_sets[3]; void* chain_mem[2] = {nullptr, nullptr}; hipStream_t chain_streams[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_band;
     // per-ray triangle ids of the continuation rays (PtQueues::cl_prim): allocated on the first textured frame or mirres_path_t::new_prim request, never for a material field
@@ -190,6 +194,27 @@ inline int ensure_ray_prim(mirres_ctx* ctx, size_t n) {
     return MIRRES_OK;
 }
 
+inline int ensure_events(std::vector<hipEvent_t>& v, size_t n, unsigned flags) {   // grows an event vector to n events created with `flags`
+    while (v.size() < n) { hipEvent_t e; MR_HIP(hipEventCreateWithFlags(&e, flags)); v.push_back(e); }
+    return MIRRES_OK;
+}
+// ---- Environment knobs of the frame loop. Each is parsed here and nowhere else; the profile named is the one that decided the default.
+// Read at every call (tests switch them inside a process; mirres_render reads each once per frame):
+inline int knob_pt_batch() { const char* e = getenv("MIRRES_PT_BATCH"); const int k = e ? atoi(e) : 64; return k < 1 ? 1 : (k > 64 ? 64 : k); }   // samples per batch, 1..64: 64 (profiles/r06_ab_pt_batch.txt)
+inline int knob_streams() { const char* e = getenv("MIRRES_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 5 ? 5 : n); }   // streams of a frame, 1..5: 2 (profiles/r04_ab_gs_bits.txt)
+inline int knob_bands() { const char* e = getenv("MIRRES_BANDS"); return e ? atoi(e) : 1; }   // bands of the chain's band pipeline: 1 = off (profiles/r06_ab_bands.txt)
+inline int knob_chain_streams() { const char* e = getenv("MIRRES_CHAIN_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 3 ? 3 : n); }   // chain streams of the band pipeline, 1..3: 2 (profiles/r06_ab_bands.txt)
+inline size_t knob_pool_limit() { const char* e = getenv("MIRRES_POOL_LIMIT_MB"); return e ? (size_t)atoll(e) << 20 : 0; }   // largest batch pool in bytes, 0 = no limit (a test switch: no profile)
+inline int knob_min_batches() { const char* e = getenv("MIRRES_MIN_BATCHES"); return e ? (atoi(e) > 0 ? atoi(e) : 1) : 0; }   // batches per frame at least; 0 = unset, choose_k's rule (profiles/r06_ab_train_batch.txt)
+inline bool knob_dbg_sum() { return getenv("MIRRES_DBG_SUM") != nullptr; }   // per-stage checksums on stderr (development aid: no profile)
+inline bool knob_matnet_vector() { const char* e = getenv("MIRRES_MATNET"); return e && e[0] == 'v'; }   // material net on the VALU path: off (profiles/r03_mlp_ab.txt)
+// Latched at first use, once per process:
+inline bool knob_fuse_temporal() { static const bool v = [] { const char* e = getenv("MIRRES_FUSE_TEMPORAL"); return !(e && e[0] == '0'); }(); return v; }   // next sample's temporal merge inside the resolve: on (profiles/r04_ab_fuse_temporal.txt)
+inline bool knob_spatial_rays() { static const bool v = [] { const char* e = getenv("MIRRES_SPATIAL_RAYS"); return e && e[0] == '1'; }(); return v; }   // 32-byte rays instead of pixel pairs in the spatial queue: off (profiles/r03_bench_variants.txt)
+inline bool knob_skip_dead() { static const bool v = [] { const char* e = getenv("MIRRES_SKIP_DEAD"); return !(e && e[0] == '0'); }(); return v; }   // RaySrc::skip_dead: on (profiles/r04_ab_skip_dead.txt)
+inline bool knob_tile_compact() { static const bool v = [] { const char* e = getenv("MIRRES_TILE_COMPACT"); return !(e && e[0] == '0'); }(); return v; }   // compact light-tile records: on (profiles/r05_ab_tile_compact.txt)
+inline bool knob_bulk_prio_low() { static const bool v = [] { const char* e = getenv("MIRRES_BULK_PRIO"); return e && e[0] == 'l'; }(); return v; }   // bulk stream at the lowest priority: off (profiles/r05_strip_streams.txt)
+
 // queue tracing (bvh_trace.hip). count is read on the device; capacity bounds the grid-stride loop.
 int trace_any_items_queue(const mirres_bvh* bvh, const uint2* items, const RaySrc& src, const uint32_t* d_count, size_t capacity, int32_t* hit,
                           unsigned long long* stats, hipStream_t s, int lane, int timed, bool heads_clean, int head_set = -1);
@@ -209,6 +234,7 @@ struct PtQueues {
     uint32_t* counters;                 // [0] shadow rays, [1] continuation rays, [2] material-net list
     int32_t* slot_a; uint32_t* mask_a; int32_t* slot_c; float* pend;
     int N, NV;                          // pixels, sample slots (K * N)
+    FrameView frame;                    // y_off for the seeds of the path-tracing stages
     int lane;                           // stream of mirres_render the queue is worked on (0 chain, 1 bulk, 2 / 4 path tracing, 3 final stages): own traversal head sets
     int first_sample_is_zero;           // sample 0 of the frame has one pass fewer before the path-tracing stages (no temporal pass)
     // Live-slot lists of the batched path-tracing stages (mirres_render; NULL = every slot, the stepwise ABI): the slots whose path is still going after a
@@ -221,13 +247,17 @@ struct PtQueues {
     int32_t* cl_prim = nullptr;
 };
 int launch_initial_batch(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res, float* tile_data,
-                         float* tile_pdf, float* tile_aux, uint32_t frame0, int K, const PtQueues* q, hipStream_t s);
+                         float* tile_pdf, float* tile_aux, uint32_t frame0, int K, const PtQueues* q, const FrameView& fv, hipStream_t s);
 int launch_final_batch(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const float* occ, const float* pos, const float* normal, const float* ray_dir,
                        const float* kd, const float* rm, const mirres_res_t* res, int K, const PtQueues* q, float* color, float* diff, float* spec, float* tape, hipStream_t s);
-int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res,
-                   const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s, const mirres_res_t* next_res, uint32_t next_frame, const SpatialBand* band = nullptr);
+int launch_temporal(mirres_ctx* ctx, const FrameView& fv, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_gbuf_t* prev_g, const mirres_res_t* res,
+                    const mirres_res_t* prev_res, const float* motion, uint32_t frameIndex, hipStream_t s);
+// the spatial pass of rows `band` (further restricted by `rows`) on the queue set `set`
+int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainSet& set, const SpatialBand& band, const RowSet& rows, const mirres_env_t* env,
+                   const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res, const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s,
+                   const mirres_res_t* next_res, uint32_t next_frame);
 int comm_exchange_halos(void* comm, float* rec, int fx, int n, const int* peer, const int* s0, const int* s1, const int* r0, const int* r1, hipStream_t s);   // comm.hip
-int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane = 0);
+int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane = 0, bool heads_clean = false);   // heads_clean: ChainSet::clean of the set the launch works on, never guessed
 int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane = 0, int32_t* prim = nullptr);
 // texmat.hip
 int launch_texmat_live(const mirres_texmat_t* t, const float* occ, const float* pos, int nv, float* kd, float* rm, int use_scale, const float* scale3, const int32_t* live,

@@ -463,7 +463,6 @@ MR_DEV int tile_pixel_v(int fx, int fy, int tw, int N, int vt) {   // tile_pixel
 // ITEMS (mirres_render's chain: packed pixel records and reservoirs exist): the queue receives one (canonical pixel, neighbour pixel) pair per accepted
 // neighbour — 8 bytes instead of two 32-byte rays — and k_trace_any4q<.., SRC = 1> forms the rays (engine.hpp RaySrc). Forming and writing the rays was 135 of
 // this kernel's 214 us per sample (five position / light gathers per pixel, 290 MB of ray records per launch).
-struct RowSet { int a, b, mode; };    // mode 0: every row; 1: rows in [a, b); 2: rows outside [a, b)  (the interior / border parts of a strip's spatial pass)
 MR_DEV bool row_in(const RowSet& r, int pi, int fx) { if (r.mode == 0) return true; const int y = pi / fx; const bool in = y >= r.a && y < r.b; return r.mode == 1 ? in : !in; }
 template <int MR_MAX_NB, bool ITEMS = false>   // 5 (the reference's neighbour count) or 8: bounds the unrolled gathers, i.e. the registers held
 __global__ void __launch_bounds__(MR_SGEN_BLOCK / MR_SGEN_PX) k_spatial_gen(mirres_config_t C, GBufD G, ResD PR, const float* __restrict__ noff, uint32_t frameIndex,
@@ -821,35 +820,27 @@ int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const ui
                                 unsigned long long* stats, hipStream_t s, int32_t* prim = nullptr);
 
 static int ev_pair(std::vector<hipEvent_t>& pool, size_t& used, hipEvent_t** a, hipEvent_t** b) {
-    if (used + 2 > pool.size()) {
-        size_t old = pool.size(); pool.resize(old + 512);
-        for (size_t i = old; i < pool.size(); i++) MR_HIP(hipEventCreate(&pool[i]));
-    }
+    if (used + 2 > pool.size()) { int rc = ensure_events(pool, pool.size() + 512, hipEventDefault); if (rc) return rc; }
     *a = &pool[used]; *b = &pool[used + 1]; used += 2;
     return 0;
 }
-int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane) {
+int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane, bool heads_clean) {
     hipEvent_t *e0 = nullptr, *e1 = nullptr;
     if (ctx->instrument & 2) { int rc = ev_pair(ctx->ev_any, ctx->ev_any_used, &e0, &e1); if (rc) return rc; MR_HIP(hipEventRecord(*e0, s)); }
     int rc = (ctx->instrument & 1) ? trace_any_queue_counted(bvh, rays, count, cap, hit, ctx->stats, s, (ctx->instrument & 4) != 0)
-                                   : trace_any_queue(bvh, rays, count, cap, hit, ctx->stats, s, lane, (ctx->instrument & 2) != 0, lane == 0 && ctx->chain_reset && ctx->chain_clean);
+                                   : trace_any_queue(bvh, rays, count, cap, hit, ctx->stats, s, lane, (ctx->instrument & 2) != 0, heads_clean);
     if (e1) MR_HIP(hipEventRecord(*e1, s));
     return rc;
 }
 // queue of (origin pixel, light pixel) pairs instead of rays (engine.hpp RaySrc); never in the counting mode (callers fall back to rays there).
 // Only the spatial pass uses it: the initial pass's ray must follow the candidate's direction even when its reservoir is stored empty (non-finite weight), and
 // one ray per pixel is a small part of that kernel anyway.
-int trace_any_items_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* queue, const RaySrc& src, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane) {
+static int trace_any_items_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* queue, const RaySrc& src, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, bool heads_clean, int head_set) {
     hipEvent_t *e0 = nullptr, *e1 = nullptr;
     if (ctx->instrument & 2) { int rc = ev_pair(ctx->ev_any, ctx->ev_any_used, &e0, &e1); if (rc) return rc; MR_HIP(hipEventRecord(*e0, s)); }
-    int rc = trace_any_items_queue(bvh, reinterpret_cast<const uint2*>(queue), src, count, cap, hit, ctx->stats, s, lane, (ctx->instrument & 2) != 0,
-                                   lane == 0 && ctx->chain_reset && ctx->chain_clean);
+    int rc = trace_any_items_queue(bvh, reinterpret_cast<const uint2*>(queue), src, count, cap, hit, ctx->stats, s, 0, (ctx->instrument & 2) != 0, heads_clean, head_set);
     if (e1) MR_HIP(hipEventRecord(*e1, s));
     return rc;
-}
-static bool ray_items_allowed(const mirres_ctx* ctx) {
-    static const bool force_rays = [] { const char* e = getenv("MIRRES_SPATIAL_RAYS"); return e && e[0] == '1'; }();   // A/B: 32-byte rays everywhere, as before
-    return ctx->grec && !(ctx->instrument & 1) && !force_rays;
 }
 int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane, int32_t* prim) {
     hipEvent_t *e0 = nullptr, *e1 = nullptr;
@@ -866,16 +857,16 @@ int trace_closest(mirres_ctx* ctx, mirres_bvh* bvh, size_t cap, hipStream_t s) {
 // visibility / evaluation / shading of a sample feeds only the frame totals, so K samples go through each of them in one set of launches
 // (K * N slots, like the path-tracing stages); only temporal + spatial reuse stay sample by sample.
 int launch_initial_batch(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res, float* tile_data,
-                         float* tile_pdf, float* tile_aux, uint32_t frame0, int K, const PtQueues* q, hipStream_t s) {
+                         float* tile_pdf, float* tile_aux, uint32_t frame0, int K, const PtQueues* q, const FrameView& fv, hipStream_t s) {
     const int N = (int)ctx->N, NV = K * N;
     const int TS = ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
     MR_HIP(hipMemsetAsync(&q->counters[0], 0, sizeof(uint32_t), s));
     k_light_tiles<<<grid_for((size_t)K * TS, MR_BLOCK), MR_BLOCK, 0, s>>>(envh(env), frame0, K * TS, TS, tile_data, nullptr, tile_pdf);       // pass 0 (+1 inside)
-    static const bool compact = [] { const char* e = getenv("MIRRES_TILE_COMPACT"); return !(e && e[0] == '0'); }();
+    const bool compact = knob_tile_compact();
     if (compact) k_tile_aux<true><<<grid_for((size_t)K * TS, MR_BLOCK), MR_BLOCK, 0, s>>>(envh(env), K * TS, tile_data, tile_pdf, reinterpret_cast<float4*>(tile_aux));
     else k_tile_aux<false><<<grid_for((size_t)K * TS, MR_BLOCK), MR_BLOCK, 0, s>>>(envh(env), K * TS, tile_data, tile_pdf, reinterpret_cast<float4*>(tile_aux));
     (compact ? k_initial_gen<true> : k_initial_gen<false>)<<<grid_for(NV, MR_IGEN_BLOCK), MR_IGEN_BLOCK, 0, s>>>(ctx->cfg, envh(env), gbufd(g), resd(res), tile_data, tile_pdf, reinterpret_cast<const float4*>(tile_aux),
-                                                                       frame0 + 2, ctx->fx, N, NV, TS, ctx->y_off, q->any_rays, &q->counters[0], q->slot_a);       // pass 2
+                                                                       frame0 + 2, ctx->fx, N, NV, TS, fv.y_off, q->any_rays, &q->counters[0], q->slot_a);       // pass 2
     int rc = trace_any_q(ctx, bvh, q->any_rays, &q->counters[0], (size_t)NV, q->any_hit, s, q->lane); if (rc) return rc;
     k_initial_resolve<<<grid_for(NV, MR_BLOCK), MR_BLOCK, 0, s>>>(resd(res), NV, q->slot_a, q->any_hit);
     MR_LAUNCH_CHECK("initial_batch");
@@ -892,64 +883,59 @@ int launch_final_batch(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env
     return 0;
 }
 
+// the temporal merge (mirres_restir_temporal; mirres_render's first sample of a batch, the others are fused into the spatial resolve)
+int launch_temporal(mirres_ctx* ctx, const FrameView& fv, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_gbuf_t* prev_g, const mirres_res_t* res,
+                    const mirres_res_t* prev_res, const float* motion, uint32_t frameIndex, hipStream_t s) {
+    const int N = (int)ctx->N;
+    k_temporal<<<grid_for(N, MR_BLOCK), MR_BLOCK, 0, s>>>(ctx->cfg, envh(env), gbufd(g), gbufd(prev_g), resd(res), resd(prev_res), motion, frameIndex, ctx->fx, ctx->fy, N, fv.y_off);
+    MR_LAUNCH_CHECK("restir_temporal");
+    return MIRRES_OK;
+}
+
 // spatial pass; next_res != NULL (mirres_render's chain, packed reservoirs): the temporal merge of the next sample is fused into the resolve kernel (k_spatial_resolve<., true>)
-int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res,
-                   const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s, const mirres_res_t* next_res, uint32_t next_frame, const SpatialBand* band) {
+int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainSet& set, const SpatialBand& band, const RowSet& rows, const mirres_env_t* env,
+                   const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res, const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s,
+                   const mirres_res_t* next_res, uint32_t next_frame) {
     if (!ctx || !bvh || !env || !g || !res || !prev_res) { set_error("mirres_restir_spatial: null"); return MIRRES_E_ARG; }
     const int N = (int)ctx->N;
     const float* noff = neighbor_offsets ? neighbor_offsets : ctx->noff;
-    const bool fold = ctx->chain_reset;                         // inside mirres_render's chain (its own stream, its own work heads)
-    // a unit of the band pipeline (render.hip) works on rows [y0, y1) with the queue, hit bits, per-pixel slots and work heads of its chain stream's set
-    Ray* const q_rays = band ? band->set->q : ctx->any_rays; int32_t* const q_hit = band ? band->set->hit : ctx->any_hit; uint32_t* const q_count = band ? band->set->counter : &ctx->counters[0];
-    int32_t* const px_slot = band ? band->set->slot : ctx->slot_a; uint32_t* const px_mask = band ? band->set->mask : ctx->mask_a;
-    const int head_set = band ? band->set->head_set : HS_CHAIN_ANY;
-    bool& clean = band ? band->set->clean : ctx->chain_clean;
-    const int by0 = band ? band->y0 : 0, gen_rows = band ? band->gen_y1 - band->y0 : ctx->fy, res_rows = band ? band->y1 - band->y0 : ctx->fy;
-    if (!(fold && clean)) MR_HIP(hipMemsetAsync(q_count, 0, sizeof(uint32_t), s));
-    uint32_t* const rc_ = fold ? q_count : nullptr; uint32_t* const rh_ = fold ? bvh->work + (size_t)head_set * MR_WSET : nullptr;
+    // the pass works on rows [y0, y1) with the queue, hit bits, per-pixel slots and work heads of `set` (a unit of the band pipeline, render.hip: its chain stream's set)
+    const int by0 = band.y0, gen_rows = band.gen_y1 - band.y0, res_rows = band.y1 - band.y0;
+    const bool clean = fv.fold && set.clean;                    // inside mirres_render's chain (its own stream, its own work heads): the set's last resolve zeroed them
+    if (!clean) MR_HIP(hipMemsetAsync(set.counter, 0, sizeof(uint32_t), s));
+    uint32_t* const rc_ = fv.fold ? set.counter : nullptr; uint32_t* const rh_ = fv.fold ? bvh->work + (size_t)set.head_set * MR_WSET : nullptr;
     const bool nb5 = ctx->cfg.neighbor_count <= 5;
-    const RowSet rows = {ctx->row_a, ctx->row_b, ctx->row_mode};
     // mirres_render's chain (packed pixel records + packed reservoirs, no per-ray counters wanted): the queue carries pixel pairs and the traversal kernel forms the rays
-    const bool items = ray_items_allowed(ctx) && resd(prev_res).rec;
+    const bool items = !knob_spatial_rays() && fv.grec && !(ctx->instrument & 1) && resd(prev_res).rec;      // the knob first: latched by the first spatial pass of any kind
     // rays whose answer the merge cannot see (engine.hpp RaySrc::skip_dead) are not traced; MIRRES_SKIP_DEAD=0: trace them as the reference does (A/B). In the counting
     // mode of the chain (32-byte rays, own counters) they are marked instead, so that the counters describe what production traces; never for the reference-order counts
-    static const int skip_dead = [] { const char* e = getenv("MIRRES_SKIP_DEAD"); return (e && e[0] == '0') ? 0 : 1; }();
-    unsigned long long* const mark_dead = (skip_dead && ctx->grec && resd(prev_res).rec && (ctx->instrument & 1) && !(ctx->instrument & 4)) ? &ctx->stats[12] : nullptr;
+    const int skip_dead = knob_skip_dead() ? 1 : 0;
+    unsigned long long* const mark_dead = (skip_dead && fv.grec && resd(prev_res).rec && (ctx->instrument & 1) && !(ctx->instrument & 4)) ? &ctx->stats[12] : nullptr;
     const dim3 sg_grid(tile_grid(ctx->fx, gen_rows, MR_SGEN_TILE)), sg_block(MR_SGEN_BLOCK / MR_SGEN_PX);
-#define MR_SGEN_ARGS ctx->cfg, gbufd(g), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, ctx->y_off, ctx->occ_own, q_rays, q_count, px_slot, px_mask, rows, mark_dead, by0, gen_rows
+#define MR_SGEN_ARGS ctx->cfg, gbufd(g), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, set.q, set.counter, set.slot, set.mask, rows, mark_dead, by0, gen_rows
     if (nb5 && items) k_spatial_gen<5, true><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else if (nb5) k_spatial_gen<5><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else if (items) k_spatial_gen<8, true><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else k_spatial_gen<8><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
 #undef MR_SGEN_ARGS
-    int rc;
-    if (items) {
-        const RaySrc src = {reinterpret_cast<const float4*>(ctx->grec), resd(prev_res).rec, ctx->cfg.vis_near, skip_dead};
-        // the launch is sized by what the rows can produce (two rays per accepted neighbour): a band of a small frame does not start eight thousand waves
-        const size_t cap = band ? std::min(ctx->any_cap, (size_t)gen_rows * ctx->fx * (size_t)(2 * (ctx->cfg.neighbor_count > 1 ? ctx->cfg.neighbor_count : 1))) : ctx->any_cap;
-        if (band) {
-            hipEvent_t *e0 = nullptr, *e1 = nullptr;
-            if (ctx->instrument & 2) { int rce = ev_pair(ctx->ev_any, ctx->ev_any_used, &e0, &e1); if (rce) return rce; MR_HIP(hipEventRecord(*e0, s)); }
-            rc = trace_any_items_queue(bvh, reinterpret_cast<const uint2*>(q_rays), src, q_count, cap, q_hit, ctx->stats, s, 0, (ctx->instrument & 2) != 0, fold && clean, head_set);
-            if (e1) MR_HIP(hipEventRecord(*e1, s));
-        } else rc = trace_any_items_q(ctx, bvh, ctx->any_rays, src, &ctx->counters[0], ctx->any_cap, ctx->any_hit, s, 0);
-    } else {
-        if (band) { set_error("mirres_render: the band pipeline needs the pixel-pair queue"); return MIRRES_E_STATE; }
-        rc = trace_any(ctx, bvh, ctx->any_cap, s);
-    }
+    // the launch is sized by what the rows can produce (two rays per accepted neighbour): a band of a small frame does not start eight thousand waves
+    const size_t cap = std::min(ctx->any_cap, (size_t)gen_rows * ctx->fx * (size_t)(2 * (ctx->cfg.neighbor_count > 1 ? ctx->cfg.neighbor_count : 1)));
+    if (!items && (set.head_set != HS_CHAIN_ANY || by0 != 0 || gen_rows != ctx->fy)) { set_error("mirres_render: the band pipeline needs the pixel-pair queue"); return MIRRES_E_STATE; }   // 32-byte rays: whole frames on lane 0's heads only
+    const RaySrc src = {reinterpret_cast<const float4*>(fv.grec), resd(prev_res).rec, ctx->cfg.vis_near, skip_dead};
+    int rc = items ? trace_any_items_q(ctx, bvh, set.q, src, set.counter, cap, set.hit, s, clean, set.head_set) : trace_any_q(ctx, bvh, set.q, set.counter, cap, set.hit, s, 0, clean);
     if (rc) return rc;
     GBufD gr = gbufd(g);
-    if (ctx->grec) gr.rec = reinterpret_cast<const float4*>(ctx->grec);   // mirres_render: same values, one 64-byte record per neighbour instead of three arrays
+    if (fv.grec) gr.rec = reinterpret_cast<const float4*>(fv.grec);   // mirres_render: same values, one 64-byte record per neighbour instead of three arrays
     const bool fuse = next_res && resd(next_res).rec && resd(res).rec && gr.rec;
     const ResD NR = fuse ? resd(next_res) : resd(res);
     const int rg = tile_grid(ctx->fx, res_rows, MR_SRES_TILE), rb = MR_SRES_TILE * MR_SRES_TILE;
-#define MR_SRES_ARGS ctx->cfg, envh(env), gr, resd(res), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, ctx->y_off, ctx->occ_own, px_slot, px_mask, q_hit, rc_, rh_, NR, next_frame, rows, by0, res_rows
+#define MR_SRES_ARGS ctx->cfg, envh(env), gr, resd(res), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, set.slot, set.mask, set.hit, rc_, rh_, NR, next_frame, rows, by0, res_rows
     if (nb5 && fuse) k_spatial_resolve<5, true><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
     else if (nb5) k_spatial_resolve<5, false><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
     else if (fuse) k_spatial_resolve<8, true><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
     else k_spatial_resolve<8, false><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
 #undef MR_SRES_ARGS
-    if (fold) clean = true;
+    if (fv.fold) set.clean = true;
     MR_LAUNCH_CHECK("restir_spatial");
     return MIRRES_OK;
 }
@@ -985,6 +971,7 @@ int mirres_ctx_create(mirres_ctx_t** out, int fx, int fy, const mirres_config_t*
     MR_HIP(hipMalloc(&c->pend, sizeof(float) * 18 * N));
     MR_HIP(hipMalloc(&c->noff, sizeof(float) * 2 * (size_t)c->cfg.neighbor_offset_count));
     MR_HIP(hipMalloc(&c->tile_aux, sizeof(float) * 8 * (size_t)c->cfg.light_tile_count * c->cfg.light_tile_size));
+    c->chain_sets[0].q = c->any_rays; c->chain_sets[0].hit = c->any_hit; c->chain_sets[0].counter = &c->counters[0]; c->chain_sets[0].slot = c->slot_a; c->chain_sets[0].mask = c->mask_a;
     k_neighbor_offsets<<<1, 64, 0, 0>>>(c->cfg.neighbor_offset_count, c->noff);
     MR_HIP(hipDeviceSynchronize());
     *out = c;
@@ -1081,16 +1068,13 @@ int mirres_restir_initial(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_env
 int mirres_restir_temporal(mirres_ctx_t* ctx, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_gbuf_t* prev_g,
                            const mirres_res_t* res, const mirres_res_t* prev_res, const float* motion, uint32_t frameIndex, void* stream) {
     if (!ctx || !env || !g || !prev_g || !res || !prev_res) { set_error("mirres_restir_temporal: null"); return MIRRES_E_ARG; }
-    const int N = (int)ctx->N;
-    k_temporal<<<grid_for(N, MR_BLOCK), MR_BLOCK, 0, (hipStream_t)stream>>>(ctx->cfg, envh(env), gbufd(g), gbufd(prev_g), resd(res), resd(prev_res), motion,
-                                                                            frameIndex, ctx->fx, ctx->fy, N, ctx->y_off);
-    MR_LAUNCH_CHECK("restir_temporal");
-    return MIRRES_OK;
+    return launch_temporal(ctx, FrameView(), env, g, prev_g, res, prev_res, motion, frameIndex, (hipStream_t)stream);
 }
 
 int mirres_restir_spatial(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_env_t* env, const mirres_gbuf_t* g, const mirres_res_t* res,
                           const mirres_res_t* prev_res, const float* neighbor_offsets, uint32_t frameIndex, void* stream) {
-    return mr::launch_spatial(ctx, bvh, env, g, res, prev_res, neighbor_offsets, frameIndex, (hipStream_t)stream, nullptr, 0u);
+    if (!ctx) { set_error("mirres_restir_spatial: null"); return MIRRES_E_ARG; }
+    return launch_spatial(ctx, bvh, FrameView(), ctx->chain_sets[0], {0, ctx->fy, ctx->fy}, {0, 0, 0}, env, g, res, prev_res, neighbor_offsets, frameIndex, (hipStream_t)stream, nullptr, 0u);
 }
 
 int mirres_restir_final_vis(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const float* pos, const mirres_res_t* res, float* vis_map, void* stream) {

@@ -199,24 +199,15 @@ static PtSet pt_set(const PtBatch& PB, int h, size_t cap, int nb) {
     S.cb = PB.cb + 9 * (size_t)nb * o; S.maskb = PB.maskb + (size_t)nb * o;
     return S;
 }
-static int pt_batch_size() {   // MIRRES_PT_BATCH = samples per batch (default 64 since the end of round 6: ~164 M slots, ~110 GB of pool at 1600^2 — the device has 288 GB, and
-                               // carve_batch halves the batch when it cannot have them; 32, the default of rounds 1-6: 512-spp frame -0.3 % / -1.2 %, profiles/r06_ab_pt_batch.txt;
-                               // 1 = sample by sample)
-    const char* e = getenv("MIRRES_PT_BATCH");   // read per frame (tests switch it)
-    int k = e ? atoi(e) : 64; if (k < 1) k = 1; if (k > 64) k = 64;
-    return k;
-}
 // The bulk stream at the LOWEST priority (MIRRES_BULK_PRIO=low): the sample-by-sample chain on the caller's stream is what bounds a small frame (a strip of a
 // multi-GPU frame: profiles/r05_strip_table.txt), and its small launches get the CUs first while the batched stages fill in behind them. Default: normal priority.
 static hipError_t create_side_stream(hipStream_t* out) {
-    static const int prio_mode = [] { const char* e = getenv("MIRRES_BULK_PRIO"); return (e && e[0] == 'l') ? 1 : 0; }();
-    if (prio_mode == 1) {
+    if (knob_bulk_prio_low()) {
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) return hipStreamCreateWithPriority(out, hipStreamNonBlocking, least);
     }
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
-static int stream_count() { const char* e = getenv("MIRRES_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 5 ? 5 : n); }   // 1: everything on the caller's stream; 2 (default since the end of round 4: equal on the icosphere, +0.7 % on the lego-like mesh, profiles/r04_ab_gs_bits.txt): + one bulk stream; 3 (rounds 1-4): + path tracing on its own; 4: + final stages on their own; 5: + a second path-tracing stream (4, 5: measured within noise of 3)
 static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS, PtBatch& PB) {
     if (K < 1) K = 1;
     while ((size_t)K * (size_t)N > 0x30000000ull && K > 1) K--;   // slot indices are 32-bit
@@ -236,14 +227,14 @@ static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS,
     // BESIDE the working pool (and under MIRRES_POOL_LIMIT_MB), the larger pool is allocated next to the working one, which is given up only once the
     // new one exists. A retry that fails anyway (fragmentation) doubles the wait (64, 128, ... 4096 frames), so a device that stays full costs one
     // failed hipMalloc per ever-longer interval, never a synchronisation, a free or a memset of the working pool.
-    const char* lim_s0 = getenv("MIRRES_POOL_LIMIT_MB"); const size_t lim0 = lim_s0 ? (size_t)atoll(lim_s0) << 20 : 0;
+    const size_t lim = knob_pool_limit();
     if (ctx->ptb_kcap > 0 && K > ctx->ptb_kcap) {
         const size_t want = bytes_for(K);
         bool grown = false;
         if (++ctx->ptb_kcap_age >= ctx->ptb_retry_wait) {
             ctx->ptb_kcap_age = 0;
             size_t fr = 0, tot = 0;
-            const bool roomy = !(lim0 && want > lim0) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > want + (1ull << 30);
+            const bool roomy = !(lim && want > lim) && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > want + (1ull << 30);
             char* fresh = nullptr;
             if (roomy && hipMalloc(&fresh, want) == hipSuccess) {
                 if (ctx->ptb) { MR_HIP(hipDeviceSynchronize()); MR_HIP(hipFree(ctx->ptb)); }
@@ -264,7 +255,6 @@ static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS,
         // spare the request at all (other tenants of the HBM), the batch is halved until it fits.
         char* fresh = nullptr;
         // MIRRES_POOL_LIMIT_MB: refuse larger pools as if the device were full (how the tests exercise the fall-back without filling 288 GB)
-        const char* lim_s = getenv("MIRRES_POOL_LIMIT_MB"); const size_t lim = lim_s ? (size_t)atoll(lim_s) << 20 : 0;
         auto pool_alloc = [&](char** p, size_t b) -> hipError_t { if (lim && b > lim) return hipErrorOutOfMemory; return hipMalloc(p, b); };
         hipError_t e = pool_alloc(&fresh, need);
         if (e != hipSuccess) {
@@ -337,16 +327,13 @@ static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS,
 // traversal kernel that takes band queues as they become ready — a different engine. MIRRES_BANDS = n switches the pipeline on.
 static int band_count(const mirres_ctx* ctx, bool allowed) {   // MIRRES_BANDS: unset / 0 / 1 = off (default), n = n bands (each at least 48 rows, boundaries at multiples of 16 rows)
     if (!allowed) return 1;
-    const char* e = getenv("MIRRES_BANDS"); int b = e ? atoi(e) : 1;
+    int b = knob_bands();
     if (b <= 0) b = 1;
     const int most = ctx->fy / 48;
     if (b > most) b = most; if (b > 16) b = 16; if (b < 1) b = 1;
     return b;
 }
-static int chain_stream_count() { const char* e = getenv("MIRRES_CHAIN_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 3 ? 3 : n); }
-static int ensure_chain_sets(mirres_ctx* ctx, int S) {
-    ChainSet& c0 = ctx->chain_sets[0];
-    c0.q = ctx->any_rays; c0.hit = ctx->any_hit; c0.counter = &ctx->counters[0]; c0.slot = ctx->slot_a; c0.mask = ctx->mask_a; c0.head_set = HS_CHAIN_ANY;
+static int ensure_chain_sets(mirres_ctx* ctx, int S) {   // the streams and queue sets of chain streams 1 .. S - 1 (set 0: mirres_ctx_create)
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t N = ctx->N, pairs = ctx->any_cap / 2;
     for (int t = 1; t < S; t++) {
@@ -361,7 +348,6 @@ static int ensure_chain_sets(mirres_ctx* ctx, int S) {
             c.head_set = HS_BAND1 + (t - 1);
         }
     }
-    for (int t = 0; t < 3; t++) ctx->chain_sets[t].clean = false;
     return 0;
 }
 
@@ -401,19 +387,8 @@ static int finish(mirres_ctx* ctx, const mirres_render_args_t* a, float* tot[6],
     return 0;
 }
 
-extern "C" {
-
-int mirres_ctx_reserve(mirres_ctx_t* ctx, int samples_per_batch) {
-    if (!ctx || samples_per_batch < 0) { set_error("mirres_ctx_reserve: bad argument"); return MIRRES_E_ARG; }
-    int K = samples_per_batch > 0 ? samples_per_batch : pt_batch_size();
-    if (K > 64) K = 64;
-    PtBatch PB;
-    const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
-    const int rc = carve_batch(ctx, ctx->fx * ctx->fy, K, ctx->cfg.max_bounce, TS, PB);
-    return rc ? rc : PB.K;
-}
-
-int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args_t* a, void* stream) {
+// ---- mirres_render = argument checks, frame set-up and Frame::run, whose stages (initial, chain_sample, final_batch, path_trace_batch) take what they need as arguments
+static int check_args(const mirres_ctx* ctx, const mirres_bvh* bvh, const mirres_render_args_t* a) {
     if (!ctx || !bvh || !a || !a->env_map || !a->occ || !a->normal || !a->depth || !a->kd || !a->rough_metal || !a->ray_dir || !a->pos || a->spp <= 0) {
         set_error("mirres_render: bad argument"); return MIRRES_E_ARG;
     }
@@ -421,312 +396,143 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
     if (a->tex && a->mat) { set_error("mirres_render: both a textured mesh (tex) and a material field (mat) given"); return MIRRES_E_ARG; }
     if (bvh->T < 2) { set_error("mirres_render: BVH not built"); return MIRRES_E_STATE; }
     if (int e = bvh_sticky_error(bvh, "mirres_render")) return e;
-    hipStream_t s = (hipStream_t)stream;
-    const int N = (int)ctx->N, fx = ctx->fx; const size_t n3 = 3 * (size_t)N;
-    const int Wc = a->Wc, Hc = a->Hc;
-    FrameBufs B; int rc = carve(ctx, Wc, Hc, B); if (rc) return rc;
-    const bool strip = a->strip_full_fy > 0;
+    if (a->strip_full_fy <= 0) return MIRRES_OK;
     // the local frame may extend below the image (rows the caller padded with background so that strips of different views share a context size);
     // the own rows must lie inside it
-    if (strip && !(a->own_y0 >= 0 && a->own_y0 < a->own_y1 && a->own_y1 <= ctx->fy && a->strip_y_off >= 0 && a->strip_y_off + a->own_y1 <= a->strip_full_fy)) {
+    if (!(a->own_y0 >= 0 && a->own_y0 < a->own_y1 && a->own_y1 <= ctx->fy && a->strip_y_off >= 0 && a->strip_y_off + a->own_y1 <= a->strip_full_fy)) {
         set_error("mirres_render: strip rows [%d,%d) of a %d-row local frame at global row %d of %d", a->own_y0, a->own_y1, ctx->fy, a->strip_y_off, a->strip_full_fy);
         return MIRRES_E_ARG;
     }
-    if (strip) {   // the halo must cover the spatial gather radius wherever the image continues beyond the own rows
-        const int r = (int)ctx->cfg.gather_radius;
-        const int above = a->strip_y_off + a->own_y0, below = a->strip_full_fy - (a->strip_y_off + a->own_y1);
-        if (a->own_y0 < (above < r ? above : r) || ctx->fy - a->own_y1 < (below < r ? below : r)) { set_error("mirres_render: strip halo narrower than the gather radius %d", r); return MIRRES_E_ARG; }
+    // the halo must cover the spatial gather radius wherever the image continues beyond the own rows
+    const int r = (int)ctx->cfg.gather_radius;
+    const int above = a->strip_y_off + a->own_y0, below = a->strip_full_fy - (a->strip_y_off + a->own_y1);
+    if (a->own_y0 < (above < r ? above : r) || ctx->fy - a->own_y1 < (below < r ? below : r)) { set_error("mirres_render: strip halo narrower than the gather radius %d", r); return MIRRES_E_ARG; }
+    return MIRRES_OK;
+}
+// K: the configured batch size (or the whole sample range when that is shorter). The path-tracing stages do not depend on the ReSTIR stages,
+// so even a single batch keeps several streams busy; larger batches mean fewer, larger launches (measured at 1600^2: 16 spp in one batch
+// of 16 instead of four of 4: 53.6 -> 50.5 ms; 128 spp in batches of 16 / 32 / 64: 375 / 370 / 367 ms)
+static int choose_k(int n, int N, int Kmax) {
+    // a frame whose samples fit ONE batch runs its stages strictly one after the other (initial resampling of all samples, then the whole chain, then the final
+    // stage); two batches let I(1) and F(0) run beside the chain. On a small frame (the 800 x 800 x 32 spp training frame) that is worth 1.3 % of the step
+    // (profiles/r06_ab_train_batch.txt: 16 per batch 25.9 ms, 32: 26.25, 11: 27.2, 8: 28.3); on the full-size frame short batches lose (r05_ab_batch_ramp.txt)
+    // A full-size frame of 33 ... 64 samples (a rank's slice of the 512-spp frame on eight GPUs) keeps the two batches of <= 32 it had while 32 was the batch size.
+    int K = Kmax, mb = knob_min_batches();
+    if (!mb) mb = (n >= 16 && n <= K && ((size_t)N <= (size_t)1024 * 1024 || n > 32)) ? 2 : 1;
+    if (n < mb * K) K = (n + mb - 1) / mb; if (K < 1) K = 1; if (K > Kmax) K = Kmax; if (K > n) K = n;
+    return K;
+}
+// Whatever way mirres_render returns, the caller's stream is ordered after every side stream that was forked from it (an error exit must not
+// leave work running on the side streams that the caller's next enqueue could race with), and the debug buffer is released.
+struct Join {
+    mirres_ctx* c = nullptr; hipStream_t s = nullptr; hipStream_t forked[4]; hipEvent_t joins[4]; int n = 0; unsigned long long* sums = nullptr;
+    // a side stream plus its join event, created on first use; it waits on the fork event
+    int fork(hipStream_t* slot, hipEvent_t* join, bool bulk, hipStream_t* out) {
+        if (!*slot) MR_HIP(bulk ? create_side_stream(slot) : hipStreamCreateWithFlags(slot, hipStreamNonBlocking));
+        if (!*join) MR_HIP(hipEventCreateWithFlags(join, hipEventDisableTiming));
+        MR_HIP(hipStreamWaitEvent(*slot, c->ev_fork, 0));
+        forked[n] = *slot; joins[n++] = *join; *out = *slot;
+        return 0;
     }
-    const bool partial = strip || !(a->spp_begin == 0 && a->spp_end == 0);
-    const bool sliced = !(a->spp_begin == 0 && a->spp_end == 0);
-    const int i0 = sliced ? a->spp_begin : 0, i1 = sliced ? a->spp_end : a->spp;
-    const int grd = grid_for(N, MR_BLOCK);
+    void run() { for (int k = 0; k < n; k++) { (void)hipEventRecord(joins[k], forked[k]); (void)hipStreamWaitEvent(s, joins[k], 0); } n = 0; }
+    ~Join() { run(); if (sums) { (void)hipStreamSynchronize(s); (void)hipFree(sums); } }
+};
 
-    k_prep<<<grd, MR_BLOCK, 0, s>>>(N, a->occ, a->ray_dir, a->normal, a->depth, a->kd, a->rough_metal, B.ray_dir, B.nd, B.brdf, a->pos, reinterpret_cast<float4*>(B.grec));
-    k_flip_env<<<grid_for((size_t)Wc * Hc, MR_BLOCK), MR_BLOCK, 0, s>>>(Wc, Hc, a->env_map, B.tex);
-    rc = mirres_env_make_sampleable(B.tex, Wc, Hc, B.pdf, B.cdf, B.mpdf, B.mcdf, s); if (rc) return rc;
-    // zero-initialised state of restir_di_with_pt (:252-302)
-    MR_HIP(hipMemsetAsync(B.tot[0], 0, sizeof(float) * (size_t)(B.c1 - B.tot[0]), s));       // the six running totals (the reservoirs and the path state live in the batch pool)
-    mirres_env_t E = {B.tex, Wc, Hc, B.pdf, B.cdf, B.mpdf, B.mcdf};
-    // strip sharding: `occ` (halo rows zeroed) selects the pixels this rank computes; the spatial pass tests neighbours against the true G-buffer
-    const float* occ = a->occ;
-    struct StripGuard { mirres_ctx* c; ~StripGuard() { c->y_off = 0; c->full_fy = 0; c->occ_own = nullptr; } } strip_guard{ctx};
-    if (strip) {
-        k_own_occ<<<grd, MR_BLOCK, 0, s>>>(N, fx, a->own_y0, a->own_y1, a->occ, B.occ_own);
-        occ = B.occ_own; ctx->y_off = a->strip_y_off; ctx->full_fy = a->strip_full_fy; ctx->occ_own = B.occ_own;
-    }
-    mirres_gbuf_t G = {occ, a->pos, B.nd, B.brdf, B.ray_dir};          // own-pixel stages (initial, temporal)
-    mirres_gbuf_t Gt = {a->occ, a->pos, B.nd, B.brdf, B.ray_dir};      // spatial reuse: neighbours in the halo rows are real pixels
-    struct GrecGuard { mirres_ctx* c; ~GrecGuard() { c->grec = nullptr; c->chain_reset = false; c->chain_clean = false; c->row_mode = 0; } } grec_guard{ctx};
-    ctx->grec = B.grec;   // packed copy for the neighbour gathers of the spatial merge; cleared when this call returns (the launches captured the pointer)
-    const uint32_t passes = 20;  // mTotalRISPasses (:242)
-    const int max_bounce = ctx->cfg.max_bounce;
+static const uint32_t kRisPasses = 20;  // mTotalRISPasses (:242)
+struct Frame {
+    mirres_ctx* ctx; mirres_bvh* bvh; const mirres_render_args_t* a; hipStream_t s;   // s: the caller's stream, which carries the chain
+    int N, i0, i1, nbatch = 0;                  // pixels, the sample range [i0, i1), its batches
+    FrameBufs B; PtBatch PB; FrameView fv; mirres_env_t E; mirres_gbuf_t G, Gt; const float* occ;
+    bool two_streams = false, dbg_sum = false, matnet_vector = false;
+    hipStream_t sp, st, sf, st2 = nullptr;      // sp: I stages, sf: F stages, st (and st2): path-tracing stages
+    ChainSet sets[3];                           // the frame's own copies of the context's queue sets: what `clean` says ends with the frame
+    bool merged = false;                        // this sample's temporal merge ran inside the previous sample's resolve
+    int n_sums = 0, pt_seq = 0;                 // checksums taken; running index of the path-tracing sub-batches
+    Join join;
 
-    // ---- K-sample batches. The ReSTIR stages of a sample need the previous sample's reservoirs (temporal reuse) and run one sample at a
-    // time; the path-tracing stages depend only on the G-buffer and the sample's RNG stream, so the K samples of a batch go through them
-    // together: K * N slots per launch. A traversal launch has a tail as long as its slowest rays (~0.1 ms) during which most CUs idle —
-    // a third of a 2.3 M-ray launch, a small fraction of a K-times larger one.
-    if (i1 > i0) {   // an empty slice of the sample range (spp sharding with more ranks than samples) leaves the zeroed totals
-    const int Kmax = pt_batch_size();
-    const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
-    // K: the configured batch size (or the whole sample range when that is shorter). The path-tracing stages do not depend on the ReSTIR stages,
-    // so even a single batch keeps several streams busy; larger batches mean fewer, larger launches (measured at 1600^2: 16 spp in one batch
-    // of 16 instead of four of 4: 53.6 -> 50.5 ms; 128 spp in batches of 16 / 32 / 64: 375 / 370 / 367 ms)
-    int Kuse = Kmax;
-    { const char* e = getenv("MIRRES_MIN_BATCHES");
-      const int n = i1 - i0;
-      // a frame whose samples fit ONE batch runs its stages strictly one after the other (initial resampling of all samples, then the whole chain, then the final
-      // stage); two batches let I(1) and F(0) run beside the chain. On a small frame (the 800 x 800 x 32 spp training frame) that is worth 1.3 % of the step
-      // (profiles/r06_ab_train_batch.txt: 16 per batch 25.9 ms, 32: 26.25, 11: 27.2, 8: 28.3); on the full-size frame short batches lose (r05_ab_batch_ramp.txt)
-      // A full-size frame of 33 ... 64 samples (a rank's slice of the 512-spp frame on eight GPUs) keeps the two batches of <= 32 it had while 32 was the batch size.
-      const int mb = e ? (atoi(e) > 0 ? atoi(e) : 1) : ((n >= 16 && n <= Kuse && ((size_t)N <= (size_t)1024 * 1024 || n > 32)) ? 2 : 1);
-      if (n < mb * Kuse) Kuse = (n + mb - 1) / mb; if (Kuse < 1) Kuse = 1; if (Kuse > Kmax) Kuse = Kmax; if (Kuse > n) Kuse = n; }
-    PtBatch PB; rc = carve_batch(ctx, N, Kuse, max_bounce, TS, PB); if (rc) return rc;
-    if (a->tex) { rc = ensure_ray_prim(ctx, (size_t)PB.K * (size_t)N); if (rc) return rc; }   // textured frames only: the batch pool of a material-field frame does not grow
-    // ---- schedule. Per batch b of K samples:
-    //   I(b)  initial resampling of the K samples (light tiles, candidates, shadow rays)              bulk stream, K * N slots per launch
-    //   C(b)  temporal + spatial reuse, one sample after the other (needs the previous sample)        caller's stream, N pixels per launch
-    //   F(b)  final visibility + evaluation + shading of the K samples -> totals 0..2                 bulk stream
-    //   PT(b) new direction + max_bounce indirect vertices of the K samples -> totals 3..5            path-tracing stream
-    // The branches share only read-only inputs (G-buffer, environment tables, BVH). The large launches of the bulk and path-tracing streams
-    // fill the CUs the small sample-by-sample launches of the chain leave idle (a 2.3 M-ray traversal launch idles a third of the chip in its
-    // tail), and the launch gaps and kernel tails of one stream are covered by the others. Reservoir sets alternate with the batch parity;
-    // hand-offs are events:
-    //   bulk:   wait C(b-1) | F(b-1) | I(b+1) | signal          chain:  wait signal(b-1) | C(b) | signal          path tracing: PT(0) PT(1) ...
-    // PT(b) reads nothing the ReSTIR stages write (its own rays, queues and totals 3..5), so only the frame's start and end order it against
-    // them. Every stream works on its own traversal head set (bvh_trace.hip) and no kernel accumulates across streams, so the frame is
-    // bit-identical for any stream count and batch size (tests/test_gpu_fullsize.py). MIRRES_STREAMS=2 puts PT(b) behind I(b+1) on the bulk
-    // stream; instrumented frames (counters / per-launch event timing) and MIRRES_STREAMS=1 run the same sequence on one stream.
-    hipStream_t sp = s, st = s, sf = s, st2 = nullptr;   // sp: I stages, sf: F stages, st (and st2): path-tracing stages
-    unsigned long long* d_sums = nullptr;
-    // Whatever way this call returns, the caller's stream is ordered after every side stream that was forked from it (an error exit must not
-    // leave work running on the side streams that the caller's next enqueue could race with), and the debug buffer is released.
-    struct Join {
-        mirres_ctx* c; hipStream_t s; hipStream_t *sp, *st, *sf, *st2; unsigned long long** sums; bool done;
-        void run() {
-            if (done) return; done = true;
-            if (*sp != s && c->ev_join) { (void)hipEventRecord(c->ev_join, *sp); (void)hipStreamWaitEvent(s, c->ev_join, 0); }
-            if (*st != *sp && c->ev_join_pt) { (void)hipEventRecord(c->ev_join_pt, *st); (void)hipStreamWaitEvent(s, c->ev_join_pt, 0); }
-            if (*sf != *sp && c->ev_join_fin) { (void)hipEventRecord(c->ev_join_fin, *sf); (void)hipStreamWaitEvent(s, c->ev_join_fin, 0); }
-            if (*st2 && c->ev_join_pt2) { (void)hipEventRecord(c->ev_join_pt2, *st2); (void)hipStreamWaitEvent(s, c->ev_join_pt2, 0); }
-        }
-        ~Join() { run(); if (*sums) { (void)hipStreamSynchronize(s); (void)hipFree(*sums); *sums = nullptr; } }
-    } join{ctx, s, &sp, &st, &sf, &st2, &d_sums, false};
-    const int nstreams = ctx->instrument == 0 ? stream_count() : 1;
-    const bool two_streams = nstreams >= 2;
-    const int nbatch = (i1 - i0 + PB.K - 1) / PB.K;
-    if (two_streams) {
-        if (!ctx->aux_stream) {
-            MR_HIP(create_side_stream(&ctx->aux_stream));
-            MR_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)); MR_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        while ((int)ctx->ev_sync.size() < 3 * (nbatch + 1)) { hipEvent_t e; MR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_sync.push_back(e); }
-        sp = st = sf = ctx->aux_stream;
-        MR_HIP(hipEventRecord(ctx->ev_fork, s)); MR_HIP(hipStreamWaitEvent(sp, ctx->ev_fork, 0));
-        PB.q.lane = PB.qf.lane = PB.qv.lane = 1;
-        if (nstreams >= 3) {   // the path-tracing stages read only the G-buffer: nothing orders them against the ReSTIR stages but the frame's start and end
-            if (!ctx->pt_stream) { MR_HIP(hipStreamCreateWithFlags(&ctx->pt_stream, hipStreamNonBlocking)); MR_HIP(hipEventCreateWithFlags(&ctx->ev_join_pt, hipEventDisableTiming)); }
-            st = ctx->pt_stream;
-            MR_HIP(hipStreamWaitEvent(st, ctx->ev_fork, 0));
-            PB.q.lane = 2;
-        }
-        if (nstreams >= 5 && PB.K >= 2) {   // two path-tracing streams, each advancing half-batches (+1 % at 128 spp, -4 % at 16 spp: not the default)
-            if (!ctx->pt_stream2) { MR_HIP(hipStreamCreateWithFlags(&ctx->pt_stream2, hipStreamNonBlocking)); MR_HIP(hipEventCreateWithFlags(&ctx->ev_join_pt2, hipEventDisableTiming)); }
-            st2 = ctx->pt_stream2;
-            MR_HIP(hipStreamWaitEvent(st2, ctx->ev_fork, 0));
-        }
-        if (nstreams >= 4) {
-            if (!ctx->fin_stream) { MR_HIP(hipStreamCreateWithFlags(&ctx->fin_stream, hipStreamNonBlocking)); MR_HIP(hipEventCreateWithFlags(&ctx->ev_join_fin, hipEventDisableTiming)); }
-            sf = ctx->fin_stream;
-            MR_HIP(hipStreamWaitEvent(sf, ctx->ev_fork, 0));
-            PB.qv.lane = 3;
-        }
-    }
-    ctx->chain_reset = two_streams; ctx->chain_clean = false;   // with the other stages on their own streams and work heads, the chain's spatial passes clean up after themselves
-    auto ev_bulk = [&](int b) { return ctx->ev_sync[3 * (b + 1)]; };       // bulk stream reached "I(b+1) done" in iteration b (b = -1: I(0))
-    auto ev_chain = [&](int b) { return ctx->ev_sync[3 * (b + 1) + 1]; };  // chain C(b) done
-    auto ev_fin = [&](int b) { return ctx->ev_sync[3 * (b + 1) + 2]; };    // F(b) done (only when the final stages have their own stream)
-    auto batch_k = [&](int b) { const int ib = i0 + b * PB.K; return (i1 - ib < PB.K) ? (i1 - ib) : PB.K; };
-    auto initial = [&](int b) -> int {
-        const int ib = i0 + b * PB.K;
-        PtQueues Q = PB.qf; Q.NV = batch_k(b) * N;
-        return launch_initial_batch(ctx, bvh, &E, &G, &PB.rinit[b & 1], PB.tile_data, PB.tile_pdf, PB.tile_aux, a->random_offset + passes * (uint32_t)ib, batch_k(b), &Q, sp);
-    };
-    const bool dbg_sum = getenv("MIRRES_DBG_SUM") != nullptr;
-    int n_sums = 0;
-    if (dbg_sum) { MR_HIP(hipMalloc(&d_sums, 8 * 4096)); MR_HIP(hipMemsetAsync(d_sums, 0, 8 * 4096, s)); }
-    auto csum = [&](const void* p, size_t words) { if (dbg_sum && n_sums < 4096) k_checksum<<<1024, MR_BLOCK, 0, s>>>((const uint32_t*)p, words, d_sums + n_sums++); };
-    int pt_seq = 0;   // running index of the path-tracing sub-batches
-    // band pipeline of the chain: only inside the streamed schedule (own work heads, packed reservoirs), not for strips (their per-sample halo exchange is a barrier over
-    // the whole local frame), not for the checksum / counting / event-timing modes
+    hipEvent_t ev_bulk(int b) const { return ctx->ev_sync[3 * (b + 1)]; }       // bulk stream reached "I(b+1) done" in iteration b (b = -1: I(0))
+    hipEvent_t ev_chain(int b) const { return ctx->ev_sync[3 * (b + 1) + 1]; }  // chain C(b) done
+    hipEvent_t ev_fin(int b) const { return ctx->ev_sync[3 * (b + 1) + 2]; }    // F(b) done (only when the final stages have their own stream)
+    int batch_k(int b) const { const int ib = i0 + b * PB.K; return (i1 - ib < PB.K) ? (i1 - ib) : PB.K; }
+    uint32_t frame_of(int i) const { return a->random_offset + kRisPasses * (uint32_t)i; }
+    void csum(const void* p, size_t words) { if (dbg_sum && n_sums < 4096) k_checksum<<<1024, MR_BLOCK, 0, s>>>((const uint32_t*)p, words, join.sums + n_sums++); }
+
     // the per-sample halo exchange of a strip: the library's own RCCL send / receive group (halo_comm) or the caller's callback
-    const bool has_halo = a->halo || a->halo_comm;
-    ctx->ev_halo_t_used = 0;
-    auto exchange = [&](float* records, int sample, hipStream_t hs) -> int {
+    int exchange(float* records, int sample, hipStream_t hs) {
         if (a->halo_comm) {
             if (a->halo_n < 0 || a->halo_n > 2) { set_error("mirres_render: halo_n = %d", a->halo_n); return MIRRES_E_ARG; }
             hipEvent_t *e0 = nullptr, *e1 = nullptr;
             if (a->halo_time_stride > 0 && sample % a->halo_time_stride == 0) {
-                if (ctx->ev_halo_t_used + 2 > ctx->ev_halo_t.size()) { const size_t old_n = ctx->ev_halo_t.size(); ctx->ev_halo_t.resize(old_n + 64); for (size_t q = old_n; q < ctx->ev_halo_t.size(); q++) MR_HIP(hipEventCreate(&ctx->ev_halo_t[q])); }
+                if (ctx->ev_halo_t_used + 2 > ctx->ev_halo_t.size()) { int rc = ensure_events(ctx->ev_halo_t, ctx->ev_halo_t.size() + 64, hipEventDefault); if (rc) return rc; }
                 e0 = &ctx->ev_halo_t[ctx->ev_halo_t_used]; e1 = &ctx->ev_halo_t[ctx->ev_halo_t_used + 1]; ctx->ev_halo_t_used += 2;
                 MR_HIP(hipEventRecord(*e0, hs));
             }
-            const int rce = comm_exchange_halos(a->halo_comm, records, fx, a->halo_n, a->halo_peer, a->halo_send0, a->halo_send1, a->halo_recv0, a->halo_recv1, hs);
+            const int rce = comm_exchange_halos(a->halo_comm, records, ctx->fx, a->halo_n, a->halo_peer, a->halo_send0, a->halo_send1, a->halo_recv0, a->halo_recv1, hs);
             if (e1) MR_HIP(hipEventRecord(*e1, hs));
             return rce;
         }
         if (a->halo(a->halo_user, records, sample, (void*)hs)) { set_error("mirres_render: halo exchange callback failed at sample %d", sample); return MIRRES_E_STATE; }
         return 0;
-    };
-    const int nbands = band_count(ctx, two_streams && !has_halo && !dbg_sum && ctx->instrument == 0 && !(getenv("MIRRES_FUSE_TEMPORAL") && getenv("MIRRES_FUSE_TEMPORAL")[0] == '0') &&
-                                       !(getenv("MIRRES_SPATIAL_RAYS") && getenv("MIRRES_SPATIAL_RAYS")[0] == '1'));
-    const int nchain = nbands > 1 ? chain_stream_count() : 1;
-    hipStream_t cstream[3] = {s, nullptr, nullptr};
-    int band_seq = 0; bool have_last_unit = false; hipEvent_t last_unit_ev = nullptr; hipStream_t last_unit_stream = s;
-    if (nbands > 1) {
-        rc = ensure_chain_sets(ctx, nchain); if (rc) return rc;
-        for (int t = 1; t < nchain; t++) { cstream[t] = ctx->chain_streams[t - 1]; MR_HIP(hipStreamWaitEvent(cstream[t], ctx->ev_fork, 0)); }
     }
-    if (st2) while (ctx->ev_pt.size() < 2) { hipEvent_t e; MR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_pt.push_back(e); }
-    rc = initial(0); if (rc) return rc;
-    if (two_streams) MR_HIP(hipEventRecord(ev_bulk(-1), sp));
-    for (int b = 0; b < nbatch; b++) {
-        const int ib = i0 + b * PB.K, kk = batch_k(b);
-        // ---- bulk stream(s): F(b-1), I(b+1)
-        if (b > 0) {
-            if (two_streams) { MR_HIP(hipStreamWaitEvent(sp, ev_chain(b - 1), 0)); if (sf != sp) MR_HIP(hipStreamWaitEvent(sf, ev_chain(b - 1), 0)); }
-            PtQueues Q = PB.qv; Q.NV = batch_k(b - 1) * N;
-            rc = launch_final_batch(ctx, bvh, &E, occ, a->pos, a->normal, B.ray_dir, a->kd, a->rough_metal, &PB.rspat[(b - 1) & 1], batch_k(b - 1), &Q, B.tot[0], B.tot[1], B.tot[2],
-                                    a->tape ? a->tape + 8 * (size_t)N * (size_t)((b - 1) * PB.K) : nullptr, sf);
-            if (rc) return rc;
-            if (sf != sp) MR_HIP(hipEventRecord(ev_fin(b - 1), sf));
+    int initial(int b) {          // I(b)
+        PtQueues Q = PB.qf; Q.NV = batch_k(b) * N;
+        return launch_initial_batch(ctx, bvh, &E, &G, &PB.rinit[b & 1], PB.tile_data, PB.tile_pdf, PB.tile_aux, frame_of(i0 + b * PB.K), batch_k(b), &Q, fv, sp);
+    }
+    int final_batch(int b) {      // F(b)
+        PtQueues Q = PB.qv; Q.NV = batch_k(b) * N;
+        return launch_final_batch(ctx, bvh, &E, occ, a->pos, a->normal, B.ray_dir, a->kd, a->rough_metal, &PB.rspat[b & 1], batch_k(b), &Q, B.tot[0], B.tot[1], B.tot[2],
+                                  a->tape ? a->tape + 8 * (size_t)N * (size_t)(b * PB.K) : nullptr, sf);
+    }
+    // One sample of C(b): sample k of batch b on stream cs with the queue set `set`: the pass numbering, the first-of-batch temporal merge, the choice of the fused
+    // next merge and the spatial launch(es). units(rt, i, spatial) is the caller's part: it calls spatial(band, rows) once per launch its schedule cuts the pass into,
+    // with what it enqueues around them (halo exchange, event waits). may_fuse = false where the pass is cut by a row restriction (the strip's interior / border parts).
+    template <class Units> int chain_sample(int b, int k, hipStream_t cs, ChainSet& set, bool may_fuse, Units&& units) {
+        const int i = i0 + b * PB.K + k;
+        const uint32_t base = frame_of(i);
+        uint32_t pass = 3;
+        mirres_res_t rt = res_slot(PB.rinit[b & 1], k, (size_t)N), rs = res_slot(PB.rspat[b & 1], k, (size_t)N);
+        if (!merged) csum(rt.light_data, 8 * (size_t)N);
+        if (i > 0) {
+            // prev_* G-buffers alias the current ones from the second sample on (:462-465); a rank that starts in the middle of the sample
+            // range (spp sharding) has no history yet and skips the merge but keeps the pass numbering
+            if (i > i0 && !merged) {
+                mirres_res_t rp = (k > 0) ? res_slot(PB.rspat[b & 1], k - 1, (size_t)N) : res_slot(PB.rspat[(b - 1) & 1], PB.K - 1, (size_t)N);
+                int rc = launch_temporal(ctx, fv, &E, &G, &G, &rt, &rp, nullptr, base + pass, cs); if (rc) return rc;
+            }
+            pass += 1;
         }
-        if (b + 1 < nbatch) { rc = initial(b + 1); if (rc) return rc; }
-        if (two_streams) MR_HIP(hipEventRecord(ev_bulk(b), sp));
-        // ---- chain: temporal + spatial reuse of samples ib .. ib+kk-1
-        if (two_streams) MR_HIP(hipStreamWaitEvent(s, ev_bulk(b - 1), 0));
-        if (sf != sp && b >= 2) MR_HIP(hipStreamWaitEvent(s, ev_fin(b - 2), 0));   // C(b) overwrites the spatial reservoirs F(b-2) evaluates
-        // The temporal merge of sample i + 1 is fused into the spatial resolve of sample i (k_spatial_resolve<., true>: same pixel, the spatial output still in
-        // registers) whenever sample i + 1 belongs to the same batch — its initial reservoirs are then complete (I(b) precedes C(b)). The first sample of a batch
-        // merges in a launch of its own (its initial reservoirs come from the bulk stream's I(b), which the previous batch's last resolve cannot wait for).
-        static const bool fuse_temporal = [] { const char* e = getenv("MIRRES_FUSE_TEMPORAL"); return !(e && e[0] == '0'); }();
-        // strip_overlap: interior rows = own rows at least gather_radius away from every strip edge that has a neighbouring rank behind it
-        int in_a = a->own_y0, in_b = a->own_y1; bool overlap = false;
-        if (strip && has_halo && a->strip_overlap) {
-            const int r = (int)ctx->cfg.gather_radius;
-            if (a->strip_y_off + a->own_y0 > 0) in_a += r;
-            if (a->strip_y_off + a->own_y1 < a->strip_full_fy) in_b -= r;
-            overlap = in_b > in_a;
-            if (overlap && !ctx->halo_stream) {
-                MR_HIP(hipStreamCreateWithFlags(&ctx->halo_stream, hipStreamNonBlocking));
-                MR_HIP(hipEventCreateWithFlags(&ctx->ev_halo[0], hipEventDisableTiming)); MR_HIP(hipEventCreateWithFlags(&ctx->ev_halo[1], hipEventDisableTiming));
-            }
-        }
-        bool merged_already = false;     // this sample's temporal merge ran inside the previous sample's resolve
-        if (nbands > 1) {
-            // ---- band pipeline (see band_count): the batch's samples alternate between the chain streams; unit (k, j) waits for unit (k - 1, j + 1)
-            const int NBv = nbands;
-            while ((int)ctx->ev_band.size() < PB.K * NBv) { hipEvent_t e; MR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ctx->ev_band.push_back(e); }
-            auto ev_unit = [&](int k, int j) { return ctx->ev_band[(size_t)k * NBv + j]; };
-            auto band_row = [&](int j) { return j >= NBv ? ctx->fy : (int)(((long long)ctx->fy * j / NBv + 8) / 16 * 16); };
-            for (int t = 1; t < nchain; t++) {      // the other chain streams enter the batch where the caller's stream does (I(b) done; F(b - 2) done with the reservoirs C(b) overwrites)
-                if (two_streams) MR_HIP(hipStreamWaitEvent(cstream[t], ev_bulk(b - 1), 0));
-                if (sf != sp && b >= 2) MR_HIP(hipStreamWaitEvent(cstream[t], ev_fin(b - 2), 0));
-            }
-            for (int k = 0; k < kk; k++) {
-                const int i = ib + k, t = band_seq % nchain; band_seq++;
-                hipStream_t cs = cstream[t];
-                const uint32_t base = a->random_offset + passes * (uint32_t)i;
-                uint32_t pass = 3;
-                mirres_res_t rt = res_slot(PB.rinit[b & 1], k, (size_t)N), rs = res_slot(PB.rspat[b & 1], k, (size_t)N);
-                if (i > 0) {
-                    if (k == 0 && i > i0) {
-                        // the batch's first sample merges in a launch of its own over the whole frame (its initial reservoirs come from the bulk stream): after EVERY unit of
-                        // the previous sample, i.e. after its last one (the units of a sample run in order)
-                        if (have_last_unit && last_unit_stream != cs) MR_HIP(hipStreamWaitEvent(cs, last_unit_ev, 0));
-                        mirres_res_t rp = res_slot(PB.rspat[(b - 1) & 1], PB.K - 1, (size_t)N);
-                        rc = mirres_restir_temporal(ctx, &E, &G, &G, &rt, &rp, nullptr, base + pass, cs); if (rc) return rc;
-                    }
-                    pass += 1;
-                }
-                const bool fuse_next = k + 1 < kk;
-                mirres_res_t rn = res_slot(PB.rinit[b & 1], fuse_next ? k + 1 : k, (size_t)N);
-                for (int j = 0; j < NBv; j++) {
-                    if (k > 0 && nchain > 1) MR_HIP(hipStreamWaitEvent(cs, ev_unit(k - 1, j + 1 < NBv ? j + 1 : NBv - 1), 0));
-                    const int y0 = band_row(j), y1 = band_row(j + 1);
-                    SpatialBand band = {y0, y1, (j + 1 < NBv) ? y1 + 1 : y1, &ctx->chain_sets[t]};
-                    rc = launch_spatial(ctx, bvh, &E, &Gt, &rs, &rt, nullptr, base + pass, cs, fuse_next ? &rn : nullptr, a->random_offset + passes * (uint32_t)(i + 1) + 3u, &band); if (rc) return rc;
-                    MR_HIP(hipEventRecord(ev_unit(k, j), cs));
-                }
-                have_last_unit = true; last_unit_ev = ev_unit(k, NBv - 1); last_unit_stream = cs;
-            }
-            // the batch's chain is done when its last unit is (every earlier unit is among that unit's predecessors): the caller's stream carries the hand-off event
-            if (last_unit_stream != s) MR_HIP(hipStreamWaitEvent(s, last_unit_ev, 0));
-        } else
-        for (int k = 0; k < kk; k++) {
-            const int i = ib + k;
-            const uint32_t base = a->random_offset + passes * (uint32_t)i;
-            uint32_t pass = 3;
-            mirres_res_t rt = res_slot(PB.rinit[b & 1], k, (size_t)N), rs = res_slot(PB.rspat[b & 1], k, (size_t)N);
-            if (!merged_already) csum(rt.light_data, 8 * (size_t)N);
-            if (i > 0) {
-                // prev_* G-buffers alias the current ones from the second sample on (:462-465); a rank that starts in the middle of the sample
-                // range (spp sharding) has no history yet and skips the merge but keeps the pass numbering
-                if (i > i0 && !merged_already) {
-                    mirres_res_t rp = (k > 0) ? res_slot(PB.rspat[b & 1], k - 1, (size_t)N) : res_slot(PB.rspat[(b - 1) & 1], PB.K - 1, (size_t)N);
-                    rc = mirres_restir_temporal(ctx, &E, &G, &G, &rt, &rp, nullptr, base + pass, s); if (rc) return rc;
-                }
-                pass += 1;
-            }
-            if (has_halo && overlap) {
-                // strip sharding with the exchange off the chain: the callback enqueues it on the side stream (after this sample's temporal output), the chain does the
-                // interior rows meanwhile, then waits and does the border rows
-                MR_HIP(hipEventRecord(ctx->ev_halo[0], s)); MR_HIP(hipStreamWaitEvent(ctx->halo_stream, ctx->ev_halo[0], 0));
-                rc = exchange(rt.light_data, i, ctx->halo_stream); if (rc) return rc;
-                MR_HIP(hipEventRecord(ctx->ev_halo[1], ctx->halo_stream));
-                ctx->row_a = in_a; ctx->row_b = in_b; ctx->row_mode = 1;
-                rc = launch_spatial(ctx, bvh, &E, &Gt, &rs, &rt, nullptr, base + pass, s, nullptr, 0u);
-                if (!rc) { MR_HIP(hipStreamWaitEvent(s, ctx->ev_halo[1], 0)); ctx->row_mode = 2; rc = launch_spatial(ctx, bvh, &E, &Gt, &rs, &rt, nullptr, base + pass, s, nullptr, 0u); }
-                ctx->row_mode = 0;
-                if (rc) return rc;
-                merged_already = false;
-                csum(rs.light_data, 8 * (size_t)N);
-                continue;
-            }
-            if (has_halo) {   // strip sharding: the neighbouring ranks' border rows of the temporal output -> this rank's halo rows (and vice versa)
-                rc = exchange(rt.light_data, i, s); if (rc) return rc;
-            }
-            const bool fuse_next = fuse_temporal && !dbg_sum && k + 1 < kk;      // (sample i + 1 > i0 >= 0: it always has a temporal pass)
-            mirres_res_t rn = res_slot(PB.rinit[b & 1], fuse_next ? k + 1 : k, (size_t)N);
-            rc = launch_spatial(ctx, bvh, &E, &Gt, &rs, &rt, nullptr, base + pass, s, fuse_next ? &rn : nullptr, a->random_offset + passes * (uint32_t)(i + 1) + 3u); if (rc) return rc;
-            merged_already = fuse_next;
-            csum(rs.light_data, 8 * (size_t)N);
-        }
-        if (two_streams) MR_HIP(hipEventRecord(ev_chain(b), s));
-        // ---- path-tracing stages of samples ib .. ib+kk-1 (new direction, then max_bounce indirect vertices), in sub-batches of Kp samples that
-        // alternate between the two halves of the per-slot state (and the two path-tracing streams, when there are two)
-        const int nbq = max_bounce > 0 ? max_bounce : 1;
-        const int Kp = st2 ? PB.K / 2 : PB.K;
+        const bool fuse_next = may_fuse && knob_fuse_temporal() && !dbg_sum && k + 1 < batch_k(b);      // (sample i + 1 > i0 >= 0: it always has a temporal pass)
+        mirres_res_t rn = res_slot(PB.rinit[b & 1], fuse_next ? k + 1 : k, (size_t)N);
+        auto spatial = [&](const SpatialBand& band, const RowSet& rows) { return launch_spatial(ctx, bvh, fv, set, band, rows, &E, &Gt, &rs, &rt, nullptr, base + pass, cs, fuse_next ? &rn : nullptr, frame_of(i + 1) + 3u); };
+        int rc = units(rt, i, spatial); if (rc) return rc;
+        merged = fuse_next;
+        csum(rs.light_data, 8 * (size_t)N);
+        return 0;
+    }
+    // PT(b): path-tracing stages of the batch's samples (new direction, then max_bounce indirect vertices), in sub-batches of Kp samples that
+    // alternate between the two halves of the per-slot state (and the two path-tracing streams, when there are two)
+    int path_trace_batch(int b) {
+        const int ib = i0 + b * PB.K, kk = batch_k(b), max_bounce = ctx->cfg.max_bounce; const size_t n3 = 3 * (size_t)N;
+        const int nbq = max_bounce > 0 ? max_bounce : 1, Kp = st2 ? PB.K / 2 : PB.K;
         for (int k0 = 0; k0 < kk; k0 += Kp, pt_seq++) {
             const int ks = (kk - k0 < Kp) ? (kk - k0) : Kp, is = ib + k0, h = st2 ? (pt_seq & 1) : 0;
             hipStream_t sq = h ? st2 : st;
             PtSet T = pt_set(PB, h, (size_t)Kp * (size_t)N, nbq);
             PtQueues Q = T.q; Q.NV = ks * N; Q.first_sample_is_zero = (is == 0); if (h) Q.lane = 4;
             if (a->tex) Q.cl_prim = ctx->ray_prim + (size_t)h * (size_t)Kp * (size_t)N;     // textured frame: the continuation rays' triangles (this half's rays)
-            uint32_t fi = a->random_offset + passes * (uint32_t)is + 5;   // pass number of new_dir for a sample with a temporal pass before it
+            uint32_t fi = frame_of(is) + 5;   // pass number of new_dir for a sample with a temporal pass before it
             mirres_path_t P0 = {occ, a->pos, a->normal, B.ray_dir, a->kd, a->rough_metal, T.prd, T.pos[0], T.rd[0], T.occ[0], T.n[0]};
             // the bounce kernels run over live-slot lists and leave the other slots alone: the per-bounce masks k_pt_reduce reads must say "nothing" there
             if (max_bounce > 0) MR_HIP(hipMemsetAsync(T.maskb, 0, sizeof(uint32_t) * (size_t)nbq * (size_t)Q.NV, sq));
             Q.live_cur = 0;
-            rc = launch_new_dir(ctx, bvh, &P0, fi, 0, sq, &Q); if (rc) return rc;
-            fi += 5;
-            int src = 0;
+            int rc = launch_new_dir(ctx, bvh, &P0, fi, 0, sq, &Q); if (rc) return rc;
+            fi += 5; int src = 0;
             for (int bo = 1; bo <= max_bounce; bo++) {
                 // material lookup at the new vertices: compacted slot list -> hash-grid gather -> MFMA MLP -> scatter (slot_c is free between passes);
                 // a textured mesh instead: the live slots' texels at the triangles their continuation rays hit (slot_c still maps a slot to its ray)
                 if (a->tex) rc = launch_texmat_live(a->tex, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur],
                                                     Q.slot_c, Q.cl_prim, sq);
-                else if (a->mat && !(getenv("MIRRES_MATNET") && getenv("MIRRES_MATNET")[0] == 'v')) rc = launch_matnet_scatter_mfma(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.slot_c, &Q.counters[2], sq, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur], &Q.gs);
+                else if (a->mat && !matnet_vector) rc = launch_matnet_scatter_mfma(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, Q.slot_c, &Q.counters[2], sq, Q.live[Q.live_cur], &Q.counters[3 + Q.live_cur], &Q.gs);
                 else rc = launch_matnet_scatter(a->mat, T.occ[src], T.pos[src], Q.NV, T.kd, T.rm, a->use_scale, a->scale, a->const_kd, a->const_rm, sq);
                 if (rc) return rc;
                 mirres_path_t Pb = {T.occ[src], T.pos[src], T.n[src], T.rd[src], T.kd, T.rm, T.prd, T.pos[src ^ 1], T.rd[src ^ 1], T.occ[src ^ 1], T.n[src ^ 1]};
@@ -743,21 +549,200 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
                 if (st2) MR_HIP(hipEventRecord(ctx->ev_pt[pt_seq & 1], sq));
             }
         }
+        return 0;
     }
-    {   // F(last)
-        if (two_streams) MR_HIP(hipStreamWaitEvent(sf, ev_chain(nbatch - 1), 0));
-        PtQueues Q = PB.qv; Q.NV = batch_k(nbatch - 1) * N;
-        rc = launch_final_batch(ctx, bvh, &E, occ, a->pos, a->normal, B.ray_dir, a->kd, a->rough_metal, &PB.rspat[(nbatch - 1) & 1], batch_k(nbatch - 1), &Q, B.tot[0], B.tot[1], B.tot[2],
-                                a->tape ? a->tape + 8 * (size_t)N * (size_t)((nbatch - 1) * PB.K) : nullptr, sf);
-        if (rc) return rc;
+    int fork_streams(int nstreams); int run();
+};
+
+// stream set-up: the streams the stages run on (Frame::sp, st, sf, st2) and the traversal head sets (lanes) of their queues
+int Frame::fork_streams(int nstreams) {
+    sp = st = sf = s; two_streams = nstreams >= 2; if (!two_streams) return 0;
+    if (!ctx->ev_fork) MR_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    int rc = ensure_events(ctx->ev_sync, 3 * (size_t)(nbatch + 1), hipEventDisableTiming); if (rc) return rc;
+    MR_HIP(hipEventRecord(ctx->ev_fork, s));
+    rc = join.fork(&ctx->aux_stream, &ctx->ev_join, true, &sp); if (rc) return rc;
+    st = sf = sp;
+    PB.q.lane = PB.qf.lane = PB.qv.lane = 1;
+    if (nstreams >= 3) {   // the path-tracing stages read only the G-buffer: nothing orders them against the ReSTIR stages but the frame's start and end
+        rc = join.fork(&ctx->pt_stream, &ctx->ev_join_pt, false, &st); if (rc) return rc;
+        PB.q.lane = 2;
     }
+    if (nstreams >= 4) {
+        rc = join.fork(&ctx->fin_stream, &ctx->ev_join_fin, false, &sf); if (rc) return rc;
+        PB.qv.lane = 3;
+    }
+    if (nstreams >= 5 && PB.K >= 2) {   // two path-tracing streams, each advancing half-batches (+1 % at 128 spp, -4 % at 16 spp: not the default)
+        rc = join.fork(&ctx->pt_stream2, &ctx->ev_join_pt2, false, &st2); if (rc) return rc;
+        rc = ensure_events(ctx->ev_pt, 2, hipEventDisableTiming); if (rc) return rc;   // k_pt_reduce hand-over between the two path-tracing streams
+    }
+    return 0;
+}
+
+// ---- K-sample batches. The ReSTIR stages of a sample need the previous sample's reservoirs (temporal reuse) and run one sample at a
+// time; the path-tracing stages depend only on the G-buffer and the sample's RNG stream, so the K samples of a batch go through them
+// together: K * N slots per launch. A traversal launch has a tail as long as its slowest rays (~0.1 ms) during which most CUs idle —
+// a third of a 2.3 M-ray launch, a small fraction of a K-times larger one.
+int Frame::run() {
+    const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
+    int rc = carve_batch(ctx, N, choose_k(i1 - i0, N, knob_pt_batch()), ctx->cfg.max_bounce, TS, PB); if (rc) return rc;
+    if (a->tex) { rc = ensure_ray_prim(ctx, (size_t)PB.K * (size_t)N); if (rc) return rc; }   // textured frames only: the batch pool of a material-field frame does not grow
+    PB.q.frame = PB.qf.frame = PB.qv.frame = fv;
+    // ---- schedule. Per batch b of K samples:
+    //   I(b)  initial resampling of the K samples (light tiles, candidates, shadow rays)              bulk stream, K * N slots per launch
+    //   C(b)  temporal + spatial reuse, one sample after the other (needs the previous sample)        caller's stream, N pixels per launch
+    //   F(b)  final visibility + evaluation + shading of the K samples -> totals 0..2                 bulk stream
+    //   PT(b) new direction + max_bounce indirect vertices of the K samples -> totals 3..5            path-tracing stream
+    // The branches share only read-only inputs (G-buffer, environment tables, BVH). The large launches of the bulk and path-tracing streams
+    // fill the CUs the small sample-by-sample launches of the chain leave idle (a 2.3 M-ray traversal launch idles a third of the chip in its
+    // tail), and the launch gaps and kernel tails of one stream are covered by the others. Reservoir sets alternate with the batch parity;
+    // hand-offs are events:
+    //   bulk:   wait C(b-1) | F(b-1) | I(b+1) | signal          chain:  wait signal(b-1) | C(b) | signal          path tracing: PT(0) PT(1) ...
+    // PT(b) reads nothing the ReSTIR stages write (its own rays, queues and totals 3..5), so only the frame's start and end order it against
+    // them. Every stream works on its own traversal head set (bvh_trace.hip) and no kernel accumulates across streams, so the frame is
+    // bit-identical for any stream count and batch size (tests/test_gpu_fullsize.py). MIRRES_STREAMS=2 puts PT(b) behind I(b+1) on the bulk
+    // stream; instrumented frames (counters / per-launch event timing) and MIRRES_STREAMS=1 run the same sequence on one stream.
+    join.c = ctx; join.s = s; nbatch = (i1 - i0 + PB.K - 1) / PB.K;
+    rc = fork_streams(ctx->instrument == 0 ? knob_streams() : 1); if (rc) return rc;
+    fv.fold = two_streams;   // with the other stages on their own streams and work heads, the chain's spatial passes clean up after themselves
+    dbg_sum = knob_dbg_sum(); matnet_vector = knob_matnet_vector();
+    if (dbg_sum) { MR_HIP(hipMalloc(&join.sums, 8 * 4096)); MR_HIP(hipMemsetAsync(join.sums, 0, 8 * 4096, s)); }
+    const bool has_halo = a->halo || a->halo_comm; ctx->ev_halo_t_used = 0;
+    // band pipeline of the chain: only inside the streamed schedule (own work heads, packed reservoirs), not for strips (their per-sample halo exchange is a barrier over
+    // the whole local frame), not for the checksum / counting / event-timing modes
+    const bool fused_pairs = knob_fuse_temporal() & !knob_spatial_rays();   // both evaluated (and so latched) in the process's first frame, whatever its schedule
+    const int nbands = band_count(ctx, two_streams && !has_halo && !dbg_sum && ctx->instrument == 0 && fused_pairs);
+    const int nchain = nbands > 1 ? knob_chain_streams() : 1;
+    hipStream_t cstream[3] = {s, nullptr, nullptr};
+    int band_seq = 0; hipEvent_t last_unit_ev = nullptr; hipStream_t last_unit_stream = s;
+    if (nbands > 1) {
+        rc = ensure_chain_sets(ctx, nchain); if (rc) return rc;
+        rc = ensure_events(ctx->ev_band, (size_t)PB.K * nbands, hipEventDisableTiming); if (rc) return rc;
+        for (int t = 1; t < nchain; t++) { cstream[t] = ctx->chain_streams[t - 1]; MR_HIP(hipStreamWaitEvent(cstream[t], ctx->ev_fork, 0)); }
+    }
+    for (int t = 0; t < 3; t++) sets[t] = ctx->chain_sets[t];
+    auto ev_unit = [&](int k, int j) { return ctx->ev_band[(size_t)k * nbands + j]; };
+    auto band_row = [&](int j) { return j >= nbands ? ctx->fy : (int)(((long long)ctx->fy * j / nbands + 8) / 16 * 16); };
+    const SpatialBand whole = {0, ctx->fy, ctx->fy}; const RowSet all_rows = {0, 0, 0};
+    // strip_overlap: interior rows = own rows at least gather_radius away from every strip edge that has a neighbouring rank behind it
+    int in_a = a->own_y0, in_b = a->own_y1; bool overlap = false;
+    if (a->strip_full_fy > 0 && has_halo && a->strip_overlap) {
+        const int r = (int)ctx->cfg.gather_radius;
+        if (a->strip_y_off + a->own_y0 > 0) in_a += r;
+        if (a->strip_y_off + a->own_y1 < a->strip_full_fy) in_b -= r;
+        overlap = in_b > in_a;
+        if (overlap && !ctx->halo_stream) MR_HIP(hipStreamCreateWithFlags(&ctx->halo_stream, hipStreamNonBlocking));
+        for (int k = 0; overlap && k < 2; k++) if (!ctx->ev_halo[k]) MR_HIP(hipEventCreateWithFlags(&ctx->ev_halo[k], hipEventDisableTiming));
+    }
+    rc = initial(0); if (rc) return rc;
+    if (two_streams) MR_HIP(hipEventRecord(ev_bulk(-1), sp));
+    for (int b = 0; b < nbatch; b++) {
+        // ---- bulk stream(s): F(b-1), I(b+1)
+        if (b > 0) {
+            if (two_streams) { MR_HIP(hipStreamWaitEvent(sp, ev_chain(b - 1), 0)); if (sf != sp) MR_HIP(hipStreamWaitEvent(sf, ev_chain(b - 1), 0)); }
+            rc = final_batch(b - 1); if (rc) return rc;
+            if (sf != sp) MR_HIP(hipEventRecord(ev_fin(b - 1), sf));
+        }
+        if (b + 1 < nbatch) { rc = initial(b + 1); if (rc) return rc; }
+        if (two_streams) MR_HIP(hipEventRecord(ev_bulk(b), sp));
+        // ---- chain: temporal + spatial reuse of samples ib .. ib+kk-1
+        // The temporal merge of sample i + 1 is fused into the spatial resolve of sample i (k_spatial_resolve<., true>: same pixel, the spatial output still in
+        // registers) whenever sample i + 1 belongs to the same batch — its initial reservoirs are then complete (I(b) precedes C(b)). The first sample of a batch
+        // merges in a launch of its own (its initial reservoirs come from the bulk stream's I(b), which the previous batch's last resolve cannot wait for).
+        for (int t = 0; t < nchain; t++) {      // the other chain streams enter the batch where the caller's stream does (I(b) done; F(b - 2) done with the reservoirs C(b) overwrites)
+            if (two_streams) MR_HIP(hipStreamWaitEvent(cstream[t], ev_bulk(b - 1), 0));
+            if (sf != sp && b >= 2) MR_HIP(hipStreamWaitEvent(cstream[t], ev_fin(b - 2), 0));   // C(b) overwrites the spatial reservoirs F(b-2) evaluates
+        }
+        merged = false;
+        for (int k = 0; k < batch_k(b); k++) {
+            if (nbands > 1) {
+                // ---- band pipeline (see band_count): the batch's samples alternate between the chain streams; unit (k, j) waits for unit (k - 1, j + 1)
+                const int t = band_seq++ % nchain; hipStream_t cs = cstream[t];
+                // the batch's first sample merges in a launch of its own over the whole frame (its initial reservoirs come from the bulk stream): after EVERY unit of
+                // the previous sample, i.e. after its last one (the units of a sample run in order)
+                if (k == 0 && b > 0 && last_unit_stream != cs) MR_HIP(hipStreamWaitEvent(cs, last_unit_ev, 0));
+                rc = chain_sample(b, k, cs, sets[t], true, [&](const mirres_res_t&, int, auto& spatial) -> int {
+                    for (int j = 0; j < nbands; j++) {
+                        if (k > 0 && nchain > 1) MR_HIP(hipStreamWaitEvent(cs, ev_unit(k - 1, j + 1 < nbands ? j + 1 : nbands - 1), 0));
+                        const int y0 = band_row(j), y1 = band_row(j + 1);
+                        if (int rcu = spatial({y0, y1, (j + 1 < nbands) ? y1 + 1 : y1}, all_rows)) return rcu;
+                        MR_HIP(hipEventRecord(ev_unit(k, j), cs));
+                    }
+                    return 0;
+                });
+                last_unit_ev = ev_unit(k, nbands - 1); last_unit_stream = cs;
+            } else if (overlap) {
+                // strip sharding with the exchange off the chain: the callback enqueues it on the side stream (after this sample's temporal output), the chain does the
+                // interior rows meanwhile, then waits and does the border rows
+                rc = chain_sample(b, k, s, sets[0], false, [&](const mirres_res_t& rt, int i, auto& spatial) -> int {
+                    MR_HIP(hipEventRecord(ctx->ev_halo[0], s)); MR_HIP(hipStreamWaitEvent(ctx->halo_stream, ctx->ev_halo[0], 0));
+                    if (int rce = exchange(rt.light_data, i, ctx->halo_stream)) return rce;
+                    MR_HIP(hipEventRecord(ctx->ev_halo[1], ctx->halo_stream));
+                    if (int rcu = spatial(whole, {in_a, in_b, 1})) return rcu;
+                    MR_HIP(hipStreamWaitEvent(s, ctx->ev_halo[1], 0));
+                    return spatial(whole, {in_a, in_b, 2});
+                });
+            } else {
+                rc = chain_sample(b, k, s, sets[0], true, [&](const mirres_res_t& rt, int i, auto& spatial) -> int {   // strip sharding: the neighbouring ranks' border rows of the temporal output -> this rank's halo rows (and vice versa)
+                    if (has_halo) { if (int rce = exchange(rt.light_data, i, s)) return rce; }
+                    return spatial(whole, all_rows);
+                });
+            }
+            if (rc) return rc;
+        }
+        // the batch's chain is done when its last unit is (every earlier unit is among that unit's predecessors): the caller's stream carries the hand-off event
+        if (last_unit_stream != s) MR_HIP(hipStreamWaitEvent(s, last_unit_ev, 0));
+        if (two_streams) MR_HIP(hipEventRecord(ev_chain(b), s));
+        rc = path_trace_batch(b); if (rc) return rc;
+    }
+    if (two_streams) MR_HIP(hipStreamWaitEvent(sf, ev_chain(nbatch - 1), 0));
+    rc = final_batch(nbatch - 1); if (rc) return rc;
     join.run();
     if (dbg_sum) {
         std::vector<unsigned long long> h(n_sums);
-        MR_HIP(hipStreamSynchronize(s)); MR_HIP(hipMemcpy(h.data(), d_sums, 8 * (size_t)n_sums, hipMemcpyDeviceToHost)); (void)hipFree(d_sums); d_sums = nullptr;
+        MR_HIP(hipStreamSynchronize(s)); MR_HIP(hipMemcpy(h.data(), join.sums, 8 * (size_t)n_sums, hipMemcpyDeviceToHost)); (void)hipFree(join.sums); join.sums = nullptr;
         for (int k = 0; k < n_sums; k++) fprintf(stderr, "[sum %d] %016llx\n", k, h[k]);
     }
+    return 0;
+}
+
+extern "C" {
+
+int mirres_ctx_reserve(mirres_ctx_t* ctx, int samples_per_batch) {
+    if (!ctx || samples_per_batch < 0) { set_error("mirres_ctx_reserve: bad argument"); return MIRRES_E_ARG; }
+    int K = samples_per_batch > 0 ? samples_per_batch : knob_pt_batch();
+    if (K > 64) K = 64;
+    PtBatch PB;
+    const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
+    const int rc = carve_batch(ctx, ctx->fx * ctx->fy, K, ctx->cfg.max_bounce, TS, PB);
+    return rc ? rc : PB.K;
+}
+
+int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args_t* a, void* stream) {
+    if (int e = check_args(ctx, bvh, a)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    const int N = (int)ctx->N, Wc = a->Wc, Hc = a->Hc; const size_t n3 = 3 * (size_t)N;
+    Frame F; F.ctx = ctx; F.bvh = bvh; F.a = a; F.s = s; F.N = N;
+    FrameBufs& B = F.B; int rc = carve(ctx, Wc, Hc, B); if (rc) return rc;
+    const bool strip = a->strip_full_fy > 0, sliced = !(a->spp_begin == 0 && a->spp_end == 0), partial = strip || sliced;
+    F.i0 = sliced ? a->spp_begin : 0; F.i1 = sliced ? a->spp_end : a->spp;
+    const int grd = grid_for(N, MR_BLOCK);
+    k_prep<<<grd, MR_BLOCK, 0, s>>>(N, a->occ, a->ray_dir, a->normal, a->depth, a->kd, a->rough_metal, B.ray_dir, B.nd, B.brdf, a->pos, reinterpret_cast<float4*>(B.grec));
+    k_flip_env<<<grid_for((size_t)Wc * Hc, MR_BLOCK), MR_BLOCK, 0, s>>>(Wc, Hc, a->env_map, B.tex);
+    rc = mirres_env_make_sampleable(B.tex, Wc, Hc, B.pdf, B.cdf, B.mpdf, B.mcdf, s); if (rc) return rc;
+    // zero-initialised state of restir_di_with_pt (:252-302)
+    MR_HIP(hipMemsetAsync(B.tot[0], 0, sizeof(float) * (size_t)(B.c1 - B.tot[0]), s));       // the six running totals (the reservoirs and the path state live in the batch pool)
+    F.E = {B.tex, Wc, Hc, B.pdf, B.cdf, B.mpdf, B.mcdf};
+    // strip sharding: `occ` (halo rows zeroed) selects the pixels this rank computes; the spatial pass tests neighbours against the true G-buffer
+    F.occ = a->occ;
+    if (strip) {
+        k_own_occ<<<grd, MR_BLOCK, 0, s>>>(N, ctx->fx, a->own_y0, a->own_y1, a->occ, B.occ_own);
+        F.occ = B.occ_own; F.fv.y_off = a->strip_y_off; F.fv.occ_own = B.occ_own;
     }
+    F.G = {F.occ, a->pos, B.nd, B.brdf, B.ray_dir};          // own-pixel stages (initial, temporal)
+    F.Gt = {a->occ, a->pos, B.nd, B.brdf, B.ray_dir};        // spatial reuse: neighbours in the halo rows are real pixels
+    F.fv.grec = B.grec;   // packed copy for the neighbour gathers of the spatial merge
+    // an empty slice of the sample range (spp sharding with more ranks than samples) leaves the zeroed totals
+    if (F.i1 > F.i0) { rc = F.run(); if (rc) return rc; }
     if (partial) {
         for (int k = 0; k < 6; k++) MR_HIP(hipMemcpyAsync(a->outs[k], B.tot[k], sizeof(float) * n3, hipMemcpyDeviceToDevice, s));
         return MIRRES_OK;

@@ -347,7 +347,7 @@ int launch_new_dir(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_path_t* p, uin
     const PtQueues Q = qq ? *qq : ctx_queues(ctx);
     const int NV = Q.NV, grd = grid_for(NV, MR_BLOCK);
     MR_HIP(hipMemsetAsync(&Q.counters[1], 0, sizeof(uint32_t), s));
-    k_new_dir_gen<<<grid_for(NV, MR_GEN_BLOCK), MR_GEN_BLOCK, 0, s>>>(*p, ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, ctx->y_off,
+    k_new_dir_gen<<<grid_for(NV, MR_GEN_BLOCK), MR_GEN_BLOCK, 0, s>>>(*p, ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, Q.frame.y_off,
                                                                        Q.cl_rays, &Q.counters[1], Q.slot_c);
     int32_t* cl_prim = Q.cl_prim;
     const bool want_prim = !qq && p->new_prim;       // stepwise ABI: the triangle of every next vertex (mirres_path_t::new_prim)
@@ -370,7 +370,7 @@ int launch_bounce(mirres_ctx* ctx, mirres_bvh* bvh, const mirres_env_t* env, con
     MR_HIP(hipMemsetAsync(&Q.counters[0], 0, 2 * sizeof(uint32_t), s));
     // list mode: 16 blocks per CU stride over the device-side list; otherwise one thread per slot
     const int ggen = lin ? min(grid_for(NV, MR_BGEN_BLOCK), 256 * 16) : grid_for(NV, MR_BGEN_BLOCK), gres = lin ? min(grd, 256 * 16) : grd;
-    k_bounce_gen<<<ggen, MR_BGEN_BLOCK, 0, s>>>(*p, envh(env), ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, ctx->y_off, qq ? 1 : 0,
+    k_bounce_gen<<<ggen, MR_BGEN_BLOCK, 0, s>>>(*p, envh(env), ctx->cfg.max_bounce, ctx->cfg.vis_near, frameIndex, bounce_count, ctx->fx, Q.N, NV, Q.first_sample_is_zero, Q.frame.y_off, qq ? 1 : 0,
                                                                       color, dc, sc, Q.any_rays, &Q.counters[0], Q.cl_rays, &Q.counters[1], Q.slot_a, Q.mask_a, Q.slot_c, Q.pend, lin, lin_n);
     int rc = trace_any_q(ctx, bvh, Q.any_rays, &Q.counters[0], 2 * (size_t)NV, Q.any_hit, s, Q.lane); if (rc) return rc;
     int32_t* cl_prim = Q.cl_prim;

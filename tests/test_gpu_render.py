@@ -665,3 +665,92 @@ def test_batch_pool_fallback_keeps_the_frame_and_is_remembered(oracle, scene_mod
     for x, y in zip(ref, c):
         assert torch.equal(x, y)
     _ops._CTX_CACHE.clear()
+
+
+def _scaled_mlp(scene_mod, torch):
+    from mirres_restir_nerf_mesh_amd.render_helper import MLPTexture3D
+    mn, mx = scene_mod.material_min_max()
+    mlp = MLPTexture3D(torch.tensor([-1, -1, -1, 1, 1, 1], dtype=torch.float32), channels=6, min_max=(torch.from_numpy(mn).cuda(), torch.from_numpy(mx).cuda()), seed=3)
+    with torch.no_grad():
+        mlp.encoder.params.mul_(1e3)
+    return mlp
+
+
+def test_schedule_does_not_change_a_small_frame(oracle, scene_mod, monkeypatch):
+    """Every schedule mirres_render can be switched to sends each sample through the same chain code (render.hip chain_sample) — on the caller's stream, or as
+    bands of rows on up to three chain streams — and the other stages through one to four side streams. 48 x 144 (the smallest height band_count cuts into three
+    bands of >= 48 rows), 7 samples in batches of 3, 3, 1: a first-of-batch temporal merge, fused merges and a ragged last batch. All six buffers, bit for bit,
+    against the frame of one stream and sample-by-sample batches."""
+    F, W, mods, RR, torch = _setup(oracle, scene_mod, fx=48, fy=144)
+    mlp = _scaled_mlp(scene_mod, torch)
+    def frame(streams, batch, bands=None, chain=None):
+        for k, v in (("MIRRES_STREAMS", streams), ("MIRRES_PT_BATCH", batch), ("MIRRES_BANDS", bands), ("MIRRES_CHAIN_STREAMS", chain)):
+            monkeypatch.delenv(k, raising=False) if v is None else monkeypatch.setenv(k, str(v))
+        return [torch.from_numpy(o) for o in _run(F, W, mods, RR, torch, 7, mlp)]
+    ref = frame(1, 1)
+    assert len(ref) == 6
+    for cfg in [(n, 3) for n in (2, 3, 4, 5)] + [(2, 3, 2, 1), (2, 3, 2, 2), (2, 3, 3, 3)]:
+        for k, (a, b) in enumerate(zip(ref, frame(*cfg))):
+            assert torch.equal(a, b), "streams / batch / bands / chain streams %r: buffer %d differs" % (cfg, k)
+
+
+def test_a_frame_leaves_nothing_behind_in_the_context(oracle, scene_mod, monkeypatch):
+    """What a frame needs beyond its arguments (strip offset, own-pixel occupancy, packed G records, row restriction, clean work heads) travels as arguments of
+    its launches, so neither a strip frame with strip_overlap nor a frame that fails can change what the stepwise ABI computes afterwards on the same context:
+    initial -> temporal -> spatial give the bits of a freshly created context. Rank 0 of the two-rank split of a 48 x 96 image (local frame: 78 rows)."""
+    import torch
+    from mirres_restir_nerf_mesh_amd import renderer_restir as RR, Resampling as RS, dist as D, _lib, _ops
+    F, W, mods, RR, torch = _setup(oracle, scene_mod, fx=48, fy=96)
+    fx, fy, spp = F.fx, F.fy, 2
+    mlp = _scaled_mlp(scene_mod, torch)
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    full = {"occ": cu(F.occ[:, None].copy()), "normal": cu(F.normal), "depth": cu(F.depth[:, None]), "kd": cu(F.kd), "rm": cu(F.rm), "ray_dir": cu(F.ray_dir_raw), "pos": cu(F.pos)}
+    env = cu(F.env)
+    def render(ctx, g, n, **kw):
+        outs, _, _ = RR.render_fused(ctx, W, mlp, False, (1, 1, 1), env, g["occ"].clone(), g["normal"], g["depth"], g["kd"], g["rm"], g["ray_dir"], g["pos"],
+                                     n, 2, 2, 2.0, 0.1, 0.001, 909, **kw)
+        torch.cuda.synchronize()
+        return [o.clone() for o in outs]
+    rec = {}
+    def recorder(user, records, sample, stream):
+        rec[sample] = D.device_view(records, (fy, fx, 8)).clone()
+        return 0
+    ref = render(_ops.Context(fx, fy), full, spp, strip=(fy, 0, 0, fy), halo=_lib.HALO_FN(recorder))
+    y0, y1, lo, hi = D.strip_rows(fy, 0, 2)
+    plan = D.halo_plan(fy, fx, 0, 2)
+    loc = {k: v[lo * fx:hi * fx].contiguous() for k, v in full.items()}
+    def replay_side(user, records, sample, stream):
+        with D.on_stream(stream):
+            view = D.device_view(records, (hi - lo, fx, 8))
+            for peer, send, (ra, rb) in plan:
+                view[ra:rb].copy_(rec[sample][lo + ra:lo + rb])
+        return 0
+    used, fresh = _ops.Context(fx, hi - lo), _ops.Context(fx, hi - lo)
+    got = render(used, loc, spp, strip=(fy, lo, y0 - lo, y1 - lo), halo=_lib.HALO_FN(replay_side), strip_overlap=True)
+    for a, b in zip(ref, got):
+        assert torch.equal(a[y0 * fx:y1 * fx], b[(y0 - lo) * fx:(y1 - lo) * fx])      # the strip frame was the real thing
+    monkeypatch.setenv("MIRRES_POOL_LIMIT_MB", "1")      # 8 samples need a larger batch pool than the strip frame left: refused, inside mirres_render
+    with pytest.raises(_lib.MirresError, match="batch pool"):
+        render(used, loc, 8)
+    monkeypatch.delenv("MIRRES_POOL_LIMIT_MB")
+    # the stepwise sequence of test_gpu_passes.py::test_reservoir_chain on a frame of the local size, on both contexts
+    S = SmallFrame(oracle, scene_mod, fx=fx, fy=hi - lo)
+    WS = RR.restirbvhWorker(cu(S.vert), cu(S.tri)); WS.update_mesh(WS.vrt, WS.v_ind)
+    T = dict(occ=cu(S.occ[:, None]), pos=cu(S.pos), nd=cu(S.normal_depth), brdf=cu(S.brdf), rd=cu(S.ray_dir), tex=cu(S.tex), noff=cu(S.noff))
+    pdf, cdf, mpdf, mcdf = (cu(t) for t in S.tables)
+    tile_ld, _, tile_pdf = oracle.light_tiles(S.frame, 1000)
+    tile_ld, tile_pdf = cu(tile_ld), cu(tile_pdf)
+    new_res = lambda: (torch.zeros((S.N, 3), device="cuda"), torch.zeros((S.N, 1), device="cuda"), torch.zeros((S.N, 1), dtype=torch.int32, device="cuda"), torch.zeros((S.N, 1), device="cuda"))
+    def stepwise(ctx):
+        m = _ops.Module("stepwise", ctx)
+        r0, r1, rs = new_res(), new_res(), new_res()
+        for r, frame in ((r0, 1002), (r1, 1022)):
+            WS.InitialResampling_(m, T["pos"], r, T["tex"], S.Wc, S.Hc, S.fx, S.fy, frame, T["occ"], T["nd"], T["brdf"], T["rd"], pdf, cdf, mpdf, mcdf, tile_ld, None, tile_pdf)
+        RS.TemporalResampling(m, r1, r0, T["tex"], S.Wc, S.Hc, S.fx, S.fy, 1023, T["occ"], T["nd"], T["brdf"], T["rd"], T["occ"], T["nd"], T["brdf"], T["rd"], None)
+        WS.SpatialResampling_(m, T["pos"], rs, r1, T["noff"], T["tex"], S.Wc, S.Hc, S.fx, S.fy, 1024, T["occ"], T["nd"], T["brdf"], T["rd"])
+        torch.cuda.synchronize()
+        return [t.clone() for r in (r0, r1, rs) for t in r]
+    a, b = stepwise(used), stepwise(fresh)
+    assert int(a[10].sum()) > 0                      # the spatial pass produced reservoirs (M of the spatial output)
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert torch.equal(x, y), "stepwise buffer %d differs after a strip frame and a failed frame on the same context" % k
