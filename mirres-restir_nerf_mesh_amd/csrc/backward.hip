@@ -178,7 +178,8 @@ __global__ void __launch_bounds__(MR_BLOCK) k_final_shading_bwd(int N, const flo
 // texel (open addressing, two probes; an LDS same-address add costs cycles, not a memory round trip) and flushes each occupied entry with one
 // global atomic per channel at the end; an insert that finds both probes taken by other texels goes to global memory directly.
 #define MR_DBW_SPLIT 8
-#define MR_DBW_TABLE 2048
+#define MR_DBW_TABLE_LOG2 11
+#define MR_DBW_TABLE (1 << MR_DBW_TABLE_LOG2)
 #define MR_DBW_LIST 2048
 // Round 6 (profiles/r06_pmc_train.txt, r06_atomic_rate.txt): the kernel ran at the memory side's atomic REQUEST rate — 65 M requests per launch at 17 G/s; MI355X takes
 // 21 G scattered fp32 atomic requests per second whatever the scope (every device-scope atomic leaves the XCD's L2: TCC_EA0_ATOMIC == TCC_ATOMIC), but the lanes of ONE
@@ -188,27 +189,41 @@ __global__ void __launch_bounds__(MR_BLOCK) k_final_shading_bwd(int N, const flo
 // lanes per entry (three channels + an idle lane) — a third of the requests. A workgroup (32 pixels) makes up to 32 x spp x 4 footprint updates (4096 at 32 spp,
 // 8192 at 64 spp), and every update whose two probes are taken by other texels takes a list entry. So the list can fill; the updates that find it full go to
 // global memory with direct atomics (tests/test_gpu_render_bwd.py reaches that path).
-struct EnvScatter { int* keys; float* vals; int* lkeys; float* lvals; int* lcount; };
-MR_DEV void env_grad_add(const EnvScatter& S, float* g_env, int texel, v3 g) {
-    uint32_t h = ((uint32_t)texel * 2654435761u) >> (32 - 11);
+// The LDS aggregation table of both scatters (environment texels here, hash-grid entries in k_matnet_bwd): 2^LOG2 keys (-1 = free) with NV values each, open
+// addressing with two probes. Adds v to key's entry, claiming a free one; false when both probes are taken by other keys — the caller has its own overflow path.
+template <int NV, int LOG2>
+MR_DEV bool lds_table_add(int* keys, float* vals, int key, const float (&v)[NV]) {
+    uint32_t h = ((uint32_t)key * 2654435761u) >> (32 - LOG2);
 #pragma unroll
     for (int probe = 0; probe < 2; probe++) {
-        const int old = atomicCAS(&S.keys[h], -1, texel);
-        if (old == -1 || old == texel) { atomicAdd(&S.vals[3 * h], g.x); atomicAdd(&S.vals[3 * h + 1], g.y); atomicAdd(&S.vals[3 * h + 2], g.z); return; }
-        h = (h + 1) & (MR_DBW_TABLE - 1);
+        const int old = atomicCAS(&keys[h], -1, key);
+        if (old == -1 || old == key) {
+#pragma unroll
+            for (int c = 0; c < NV; c++) atomicAdd(&vals[NV * h + c], v[c]);
+            return true;
+        }
+        h = (h + 1) & ((1u << LOG2) - 1u);
     }
+    return false;
+}
+// entries [0, n) of (keys, vals) -> dst[NV * key + c], LANES lanes per entry: lanes LANES e .. LANES e + NV - 1 add the NV values of one entry (NV consecutive
+// dwords: one sector) in ONE instruction. The caller's threads t = first, first + step, ... share the work.
+template <int LANES, int NV>
+MR_DEV void lds_table_flush(const int* keys, const float* vals, int n, float* dst, int first, int step) {
+    for (int j = first; j < LANES * n; j += step) {
+        const int e = (uint32_t)j / LANES, c = (uint32_t)j % LANES;
+        const int key = keys[e];
+        if (c < NV && key >= 0) atomicAdd(dst + NV * (size_t)key + c, vals[NV * e + c]);
+    }
+}
+struct EnvScatter { int* keys; float* vals; int* lkeys; float* lvals; int* lcount; };
+MR_DEV void env_grad_add(const EnvScatter& S, float* g_env, int texel, v3 g) {
+    const float v[3] = {g.x, g.y, g.z};
+    if (lds_table_add<3, MR_DBW_TABLE_LOG2>(S.keys, S.vals, texel, v)) return;
     const int at = atomicAdd(S.lcount, 1);
     if (at < MR_DBW_LIST) { S.lkeys[at] = texel; S.lvals[3 * at] = g.x; S.lvals[3 * at + 1] = g.y; S.lvals[3 * at + 2] = g.z; return; }
     float* dst = g_env + 3 * (size_t)texel;
     atomicAdd(dst, g.x); atomicAdd(dst + 1, g.y); atomicAdd(dst + 2, g.z);
-}
-// entries [0, n) of (keys, vals) -> global memory, four lanes per entry: lanes 4 e .. 4 e + 2 add the three channels of one texel in ONE instruction
-MR_DEV void env_grad_flush(const int* keys, const float* vals, int n, float* g_env) {
-    for (int j = threadIdx.x; j < 4 * n; j += MR_BLOCK) {
-        const int e = j >> 2, c = j & 3;
-        const int key = keys[e];
-        if (c < 3 && key >= 0) atomicAdd(g_env + 3 * (size_t)key + c, vals[3 * e + c]);
-    }
 }
 __global__ void __launch_bounds__(MR_BLOCK) k_direct_bwd(EnvD E, int N, int S, const float* __restrict__ occ, const float* __restrict__ normal,
                                                          const float* __restrict__ ray_dir_raw, const float* __restrict__ kd, const float* __restrict__ rm,
@@ -267,8 +282,9 @@ __global__ void __launch_bounds__(MR_BLOCK) k_direct_bwd(EnvD E, int N, int S, c
     }
     if (g_env) {
         __syncthreads();
-        env_grad_flush(s_keys, s_vals, MR_DBW_TABLE, g_env);
-        env_grad_flush(s_lkeys, s_lvals, s_lcount < MR_DBW_LIST ? s_lcount : MR_DBW_LIST, g_env);
+        // four lanes per texel: three channels + an idle lane
+        lds_table_flush<4, 3>(s_keys, s_vals, MR_DBW_TABLE, g_env, threadIdx.x, MR_BLOCK);
+        lds_table_flush<4, 3>(s_lkeys, s_lvals, s_lcount < MR_DBW_LIST ? s_lcount : MR_DBW_LIST, g_env, threadIdx.x, MR_BLOCK);
     }
     if (live && sub == 0) {
         if (g_normal) st3(g_normal, pi, V3(v[0], v[1], v[2]));
@@ -286,9 +302,7 @@ int launch_direct_bwd(const float* tex, int Wc, int Hc, int N, int S, const floa
     return 0;
 }
 
-// ---------------------------------------------------------------- material-field backward (level table and index arithmetic: device_grid.hpp)
-struct MatNetB { const __half2* grid; const float *w0, *w1, *w2; float aabb_min[3], aabb_max[3], mn[6], mx[6]; };
-
+// ---------------------------------------------------------------- material-field backward (the field's own device code: device_grid.hpp)
 // Weight gradients are outer-product sums over the points (gW1[o][k] = sum_p gh2_p[o] * h1_p[k], ...). The first version added every
 // product to LDS with an atomic — 2 240 LDS atomics per point onto 2 240 addresses shared by the whole workgroup, 15 of the kernel's 17.6 ms.
 // Now each wave stages its 64 points' two factor vectors in LDS and every lane accumulates a fixed set of matrix entries in registers over
@@ -299,22 +313,147 @@ struct MatNetB { const __half2* grid; const float *w0, *w1, *w2; float aabb_min[
 #define MR_BW_TABLE_LOG2 10
 #define MR_BW_TABLE (1 << MR_BW_TABLE_LOG2)   // per-wave aggregation table of the coarse grid levels: keys in U (4 KB of 8.4), values in V (8 KB of 8.4)
 #define MR_BW_COARSE 8
-typedef GridLevels GridLevelsB;
-static GridLevelsB host_levels_b() { return host_levels(nullptr); }
+
+// Round 6: a tile whose 64 points all carry a zero cotangent (the background pixels of a training view: 60 % of an image; the loss is taken over foreground
+// pixels) adds exact zeros to every gradient — skipped as a wave; its position gradient is the zero the full computation writes
+MR_DEV bool skip_zero_tile(const float* __restrict__ gout, float* __restrict__ g_pos, int i, bool live) {
+    bool nz = false;
+    if (live) {
+#pragma unroll
+        for (int o = 0; o < 6; o++) nz = nz || gout[6 * (size_t)i + o] != 0.f;
+    }
+    if (__ballot(nz)) return false;
+    if (g_pos && live) { g_pos[3 * (size_t)i] = 0.f; g_pos[3 * (size_t)i + 1] = 0.f; g_pos[3 * (size_t)i + 2] = 0.f; }
+    return true;
+}
+// forward recompute: the forward's encoder and layers (device_grid.hpp) -> features a0, hidden activations h1, h2, pre-sigmoid outputs z2
+MR_DEV void recompute_forward(const MatNetD& M, const GridLevels& L, const float* sw0, const float* sw1, const float* sw2, const float x[3],
+                              float a0[32], float h1[32], float h2[32], float z2[6]) {
+    for (int lv = 0; lv < MR_LEVELS; lv++) {
+        const __half2* g = M.grid + L.offset[lv];
+        uint32_t pg[3], ci[8]; float p[3];
+        level_cell(L.scale[lv], x, pg, p);
+        corner_indices(L.size[lv], L.res[lv], pg, ci);
+        __half2 cv[8];
+#pragma unroll
+        for (uint32_t idx = 0; idx < 8; idx++) cv[idx] = g[ci[idx]];
+        const __half2 r = interpolate_cell(p, cv);
+        a0[2 * lv] = __low2float(r); a0[2 * lv + 1] = __high2float(r);
+    }
+    dense_layer<32>(sw0, a0, h1, ActRelu());
+    dense_layer<32>(sw1, h1, h2, ActRelu());
+    dense_layer<6>(sw2, h2, z2, ActNone());
+}
+// Position gradient (the reference's sample() is differentiable in its argument: tcnn's HashGrid returns dL/dx, the x128 / /128 hooks of
+// render_helper.py:41,78-80 cancel on this route, and kd / ks losses reach `vertices_offsets` through dr.interpolate, nerf/renderer.py:1017-1018).
+// d enc[f] / d x_d = scale * sum_corners (+-1 along d) * (product of the other two weights) * table[corner][f]   (tcnn grid.h, dy_dx with
+// pos_derivative = 1 for linear interpolation; tcnn differences the fp16 entries and accumulates in fp16, here the sum is fp32);
+// d x / d pos = 1 / (aabb_max - aabb_min), torch.clamp passes the gradient on [0, 1] inclusive and blocks it outside.
+MR_DEV void position_gradient(const MatNetD& M, const GridLevels& L, const float x[3], const float xraw[3], const float ga0[32], float* __restrict__ g_pos, int i) {
+    float gx[3] = {0.f, 0.f, 0.f};
+    for (int lv = 0; lv < MR_LEVELS; lv++) {
+        const float g0 = ga0[2 * lv], g1 = ga0[2 * lv + 1];
+        if (g0 == 0.f && g1 == 0.f) continue;
+        const float scale = L.scale[lv];
+        const __half2* g = M.grid + L.offset[lv];
+        uint32_t pg[3], ci[8]; float p[3];
+        level_cell(scale, x, pg, p);
+        float lx[3] = {0.f, 0.f, 0.f};
+        corner_indices(L.size[lv], L.res[lv], pg, ci);
+#pragma unroll
+        for (uint32_t idx = 0; idx < 8; idx++) {
+            const __half2 v = g[ci[idx]];
+            const float sv = g0 * __low2float(v) + g1 * __high2float(v);
+            lx[0] += ((idx & 1u) ? sv : -sv) * (corner_factor(p, idx, 1) * corner_factor(p, idx, 2));
+            lx[1] += ((idx & 2u) ? sv : -sv) * (corner_factor(p, idx, 0) * corner_factor(p, idx, 2));
+            lx[2] += ((idx & 4u) ? sv : -sv) * (corner_factor(p, idx, 0) * corner_factor(p, idx, 1));
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) gx[d] += scale * lx[d];
+    }
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+        g_pos[3 * (size_t)i + d] = (xraw[d] >= 0.f && xraw[d] <= 1.f) ? gx[d] / (M.aabb_max[d] - M.aabb_min[d]) : 0.f;
+}
+// One staged outer-product sum over the wave's 64 points (wave-synchronous: a wave owns its U / V): gW[o][k] += u[o] * v[k] with 2 NJ rows o; lane owns the
+// entries e = lane + 64 j, j < NJ, i.e. [o = lane / 32 + 2 j][k = lane % 32]
+template <int NJ>
+MR_DEV void outer_accumulate(float* U, float* V, int lane, const float (&u)[2 * NJ], const float (&v)[32], float (&acc)[NJ]) {
+    for (int o = 0; o < 2 * NJ; o++) U[lane * MR_BW_LD + o] = u[o];
+    for (int k = 0; k < 32; k++) V[lane * MR_BW_LD + k] = v[k];
+    __builtin_amdgcn_wave_barrier();
+    for (int p = 0; p < 64; p++) {
+        const float vk = V[p * MR_BW_LD + (lane & 31)];
+#pragma unroll
+        for (int j = 0; j < NJ; j++) acc[j] = fmaf(U[p * MR_BW_LD + (lane >> 5) + 2 * j], vk, acc[j]);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+// hash-grid gradient: fp32 atomics into the master-precision gradient table (tcnn accumulates its grid gradient the same way). The 64
+// points of a wave are neighbouring pixels: on the coarse levels they fall into a handful of cells, and 164 M scattered global atomics
+// (with that contention) were what the kernel waited for. Levels < MR_BW_COARSE therefore go through a per-wave LDS table (the wave's
+// staging area, free after the outer products: lds_table_add, overflow straight to global memory), flushed per tile.
+// Round 6 (profiles/r06_atomic_rate.txt): the memory side takes 21 G scattered atomic REQUESTS per second, and the lanes of one instruction that fall into the
+// same 32-byte sector are one request. A table entry's two features are 8 consecutive bytes: every update is issued by a PAIR of lanes (even lane: feature 0,
+// odd lane: feature 1 of the same entry; first the even lane's entry, then the odd lane's) — half the requests for the same adds, in the same order per word.
+MR_DEV void grid_gradient_scatter(const GridLevels& L, const float x[3], const float ga0[32], bool live, int lane, float* U, float* V, float* __restrict__ g_params) {
+    int* const keys = reinterpret_cast<int*>(U); float* const vals = V;
+    for (int e = lane; e < MR_BW_TABLE; e += 64) { keys[e] = -1; vals[2 * e] = 0.f; vals[2 * e + 1] = 0.f; }
+    __builtin_amdgcn_wave_barrier();
+    const int odd = lane & 1;
+    for (int lv = 0; lv < MR_LEVELS; lv++) {      // every lane walks every level (a dead or gradient-free lane contributes nothing): the pairs must stay together
+        uint32_t pg[3], ci[8]; float p[3];
+        level_cell(L.scale[lv], x, pg, p);
+        const float g0 = ga0[2 * lv], g1 = ga0[2 * lv + 1];
+        const bool lvalid = live && !(g0 == 0.f && g1 == 0.f);
+        if (!__ballot(lvalid)) continue;
+        corner_indices(L.size[lv], L.res[lv], pg, ci);
+#pragma unroll
+        for (uint32_t idx = 0; idx < 8; idx++) {
+            const float w = corner_weight(p, idx);
+            const uint32_t e = L.offset[lv] + ci[idx];
+            const float v[2] = {w * g0, w * g1};
+            const bool direct = lvalid && !(lv < MR_BW_COARSE && lds_table_add<2, MR_BW_TABLE_LOG2>(keys, vals, (int)e, v));
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const int src = (lane & ~1) | r;
+                const uint32_t e_s = (uint32_t)__shfl((int)e, src, 64);
+                const int d_s = __shfl(direct ? 1 : 0, src, 64);
+                const float a_s = __shfl(v[0], src, 64), b_s = __shfl(v[1], src, 64);
+                if (d_s) atomicAdd(&g_params[2 * (size_t)e_s + odd], odd ? b_s : a_s);
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    lds_table_flush<2, 2>(keys, vals, MR_BW_TABLE, g_params, lane, 64);      // lane pairs again: entry j / 2, feature j % 2
+    __builtin_amdgcn_wave_barrier();
+}
+// reduce the four waves' register accumulators through LDS (entry e = lane + 64 j  <->  [o = e / 32][k = e % 32]), one global atomic per entry
+MR_DEV void reduce_weight_gradients(float* red, int lane, const float (&acc0)[16], const float (&acc1)[16], const float (&acc2)[3],
+                                    float* __restrict__ g_w0, float* __restrict__ g_w1, float* __restrict__ g_w2) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2240; i += blockDim.x) red[i] = 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 16; j++) { atomicAdd(&red[lane + 64 * j], acc0[j]); atomicAdd(&red[1024 + lane + 64 * j], acc1[j]); }
+#pragma unroll
+    for (int j = 0; j < 3; j++) atomicAdd(&red[2048 + lane + 64 * j], acc2[j]);
+    __syncthreads();
+    for (int k = threadIdx.x; k < 1024; k += blockDim.x) { if (g_w0 && red[k] != 0.f) atomicAdd(&g_w0[k], red[k]); if (g_w1 && red[1024 + k] != 0.f) atomicAdd(&g_w1[k], red[1024 + k]); }
+    for (int k = threadIdx.x; k < 192; k += blockDim.x) if (g_w2 && red[2048 + k] != 0.f) atomicAdd(&g_w2[k], red[2048 + k]);
+}
 // Two waves per SIMD (256 registers, the rest in scratch) instead of one (512 + AGPRs): -4 % on the kernel (profiles/r06_ab_matnet_bwd_builds.txt). Forming every layer's
 // weight-gradient outer product right after its adjoint (shorter live ranges in the source) was measured too: the compiler hoists the LDS loads of the fully unrolled
 // mat-vecs either way — +6 % slower with one wave, +-0 with two; not kept.
 #ifndef MR_BW_MINWAVES
 #define MR_BW_MINWAVES 2
 #endif
-__global__ void __launch_bounds__(MR_BLOCK, MR_BW_MINWAVES) k_matnet_bwd(MatNetB M, GridLevelsB L, const float* __restrict__ pos, int n, const float* __restrict__ gout,
+__global__ void __launch_bounds__(MR_BLOCK, MR_BW_MINWAVES) k_matnet_bwd(MatNetD M, GridLevels L, const float* __restrict__ pos, int n, const float* __restrict__ gout,
                                                          float* __restrict__ g_params, float* __restrict__ g_w0, float* __restrict__ g_w1, float* __restrict__ g_w2,
                                                          float* __restrict__ g_pos) {
     __shared__ float sw0[1024], sw1[1024], sw2[192];
     __shared__ float sU[MR_BW_WAVES][64 * MR_BW_LD], sV[MR_BW_WAVES][64 * MR_BW_LD];
-    for (int i = threadIdx.x; i < 1024; i += blockDim.x) { sw0[i] = M.w0[i]; sw1[i] = M.w1[i]; }
-    for (int i = threadIdx.x; i < 192; i += blockDim.x) sw2[i] = M.w2[i];
-    __syncthreads();
+    stage_weights(M, sw0, sw1, sw2);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* const U = sU[wave]; float* const V = sV[wave];
     float acc0[16], acc1[16], acc2[3];
@@ -327,190 +466,24 @@ __global__ void __launch_bounds__(MR_BLOCK, MR_BW_MINWAVES) k_matnet_bwd(MatNetB
         const bool live = i < n;
         float a0[32], h1[32], h2[32], gz2[6], gh2[32], gh1[32], ga0[32];
         float x[3] = {0.f, 0.f, 0.f}, xraw[3] = {0.f, 0.f, 0.f};
-        // Round 6: a tile whose 64 points all carry a zero cotangent (the background pixels of a training view: 60 % of an image; the loss is taken over foreground
-        // pixels) adds exact zeros to every gradient — skipped as a wave; its position gradient is the zero the full computation writes
-        {
-            bool nz = false;
-            if (live) {
-#pragma unroll
-                for (int o = 0; o < 6; o++) nz = nz || gout[6 * (size_t)i + o] != 0.f;
-            }
-            if (!__ballot(nz)) {
-                if (g_pos && live) { g_pos[3 * (size_t)i] = 0.f; g_pos[3 * (size_t)i + 1] = 0.f; g_pos[3 * (size_t)i + 2] = 0.f; }
-                continue;
-            }
-        }
-        if (live) {
-#pragma unroll
-            for (int d = 0; d < 3; d++) { xraw[d] = (pos[3 * (size_t)i + d] - M.aabb_min[d]) / (M.aabb_max[d] - M.aabb_min[d]); x[d] = fminf(fmaxf(xraw[d], 0.f), 1.f); }
-        }
-        // forward recompute
-        for (int lv = 0; lv < MR_LEVELS; lv++) {
-            const float scale = L.scale[lv]; const uint32_t res = L.res[lv], size = L.size[lv];
-            const __half2* g = M.grid + L.offset[lv];
-            float p[3]; uint32_t pg[3];
-#pragma unroll
-            for (int d = 0; d < 3; d++) { float q = fmaf(scale, x[d], 0.5f); float fl = floorf(q); pg[d] = (uint32_t)(int)fl; p[d] = q - fl; }
-            uint32_t ci[8]; corner_indices(size, res, pg, ci);
-            __half2 cv[8];
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) cv[idx] = g[ci[idx]];
-            __half2 r = __floats2half2_rn(0.f, 0.f);
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) {
-                float w = 1.f;
-#pragma unroll
-                for (int d = 0; d < 3; d++) w *= (idx & (1u << d)) == 0 ? 1 - p[d] : p[d];
-                r = __hadd2(r, weighted_half2(w, cv[idx]));
-            }
-            a0[2 * lv] = __low2float(r); a0[2 * lv + 1] = __high2float(r);
-        }
+        if (skip_zero_tile(gout, g_pos, i, live)) continue;
+        if (live) normalise_pos(M, pos, i, x, xraw);
         float z2[6];
-        for (int o = 0; o < 32; o++) { float acc = 0.f; for (int k = 0; k < 32; k++) acc = fmaf(a0[k], sw0[o * 32 + k], acc); h1[o] = fmaxf(acc, 0.f); }
-        for (int o = 0; o < 32; o++) { float acc = 0.f; for (int k = 0; k < 32; k++) acc = fmaf(h1[k], sw1[o * 32 + k], acc); h2[o] = fmaxf(acc, 0.f); }
-        for (int o = 0; o < 6; o++) { float acc = 0.f; for (int k = 0; k < 32; k++) acc = fmaf(h2[k], sw2[o * 32 + k], acc); z2[o] = acc; }
-        // backward through the MLP (a dead lane carries zeros)
+        recompute_forward(M, L, sw0, sw1, sw2, x, a0, h1, h2, z2);
+        // backward through the MLP (a dead lane carries zeros): cotangents of the pre-activations gz2, gh2, gh1 and of the features ga0. Written here and not as
+        // a function, with the arrays declared before the tile skip: the kernel sits at the register limit, and as a function this phase cost 3 % of the kernel's
+        // time (profiles/matnet_shared_time.txt)
         for (int o = 0; o < 6; o++) { float sg = mrf_sigmoid(z2[o]); gz2[o] = live ? gout[6 * (size_t)i + o] * (M.mx[o] - M.mn[o]) * sg * (1.f - sg) : 0.f; }
         for (int k = 0; k < 32; k++) { float acc = 0.f; for (int o = 0; o < 6; o++) acc += gz2[o] * sw2[o * 32 + k]; gh2[k] = h2[k] > 0.f ? acc : 0.f; }
         for (int k = 0; k < 32; k++) { float acc = 0.f; for (int o = 0; o < 32; o++) acc += gh2[o] * sw1[o * 32 + k]; gh1[k] = h1[k] > 0.f ? acc : 0.f; }
         for (int k = 0; k < 32; k++) { float acc = 0.f; for (int o = 0; o < 32; o++) acc += gh1[o] * sw0[o * 32 + k]; ga0[k] = acc; }
-        // Position gradient (the reference's sample() is differentiable in its argument: tcnn's HashGrid returns dL/dx, the x128 / /128 hooks of
-        // render_helper.py:41,78-80 cancel on this route, and kd / ks losses reach `vertices_offsets` through dr.interpolate, nerf/renderer.py:1017-1018).
-        // d enc[f] / d x_d = scale * sum_corners (+-1 along d) * (product of the other two weights) * table[corner][f]   (tcnn grid.h, dy_dx with
-        // pos_derivative = 1 for linear interpolation; tcnn differences the fp16 entries and accumulates in fp16, here the sum is fp32);
-        // d x / d pos = 1 / (aabb_max - aabb_min), torch.clamp passes the gradient on [0, 1] inclusive and blocks it outside.
-        if (g_pos && live) {
-            float gx[3] = {0.f, 0.f, 0.f};
-            for (int lv = 0; lv < MR_LEVELS; lv++) {
-                const float g0 = ga0[2 * lv], g1 = ga0[2 * lv + 1];
-                if (g0 == 0.f && g1 == 0.f) continue;
-                const float scale = L.scale[lv]; const uint32_t res = L.res[lv], size = L.size[lv];
-                const __half2* g = M.grid + L.offset[lv];
-                float p[3]; uint32_t pg[3];
-#pragma unroll
-                for (int d = 0; d < 3; d++) { float q = fmaf(scale, x[d], 0.5f); float fl = floorf(q); pg[d] = (uint32_t)(int)fl; p[d] = q - fl; }
-                float lx[3] = {0.f, 0.f, 0.f};
-                uint32_t ci[8]; corner_indices(size, res, pg, ci);
-#pragma unroll
-                for (uint32_t idx = 0; idx < 8; idx++) {
-                    float wd[3];
-#pragma unroll
-                    for (int d = 0; d < 3; d++) wd[d] = (idx & (1u << d)) == 0 ? 1 - p[d] : p[d];
-                    const __half2 v = g[ci[idx]];
-                    const float sv = g0 * __low2float(v) + g1 * __high2float(v);
-                    lx[0] += ((idx & 1u) ? sv : -sv) * (wd[1] * wd[2]);
-                    lx[1] += ((idx & 2u) ? sv : -sv) * (wd[0] * wd[2]);
-                    lx[2] += ((idx & 4u) ? sv : -sv) * (wd[0] * wd[1]);
-                }
-#pragma unroll
-                for (int d = 0; d < 3; d++) gx[d] += scale * lx[d];
-            }
-#pragma unroll
-            for (int d = 0; d < 3; d++)
-                g_pos[3 * (size_t)i + d] = (xraw[d] >= 0.f && xraw[d] <= 1.f) ? gx[d] / (M.aabb_max[d] - M.aabb_min[d]) : 0.f;
-        }
-        // weight gradients: three staged outer-product sums over the wave's 64 points (wave-synchronous: a wave owns its U / V)
-        {   // gW2[o][k] += gz2[o] * h2[k]   (6 x 32 = 192 entries: lane owns e = lane + 64 j, j < 3)
-            for (int o = 0; o < 6; o++) U[lane * MR_BW_LD + o] = gz2[o];
-            for (int k = 0; k < 32; k++) V[lane * MR_BW_LD + k] = h2[k];
-            __builtin_amdgcn_wave_barrier();
-            for (int p = 0; p < 64; p++) {
-                const float vk = V[p * MR_BW_LD + (lane & 31)];
-#pragma unroll
-                for (int j = 0; j < 3; j++) acc2[j] = fmaf(U[p * MR_BW_LD + (lane >> 5) + 2 * j], vk, acc2[j]);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        {   // gW1[o][k] += gh2[o] * h1[k]
-            for (int o = 0; o < 32; o++) U[lane * MR_BW_LD + o] = gh2[o];
-            for (int k = 0; k < 32; k++) V[lane * MR_BW_LD + k] = h1[k];
-            __builtin_amdgcn_wave_barrier();
-            for (int p = 0; p < 64; p++) {
-                const float vk = V[p * MR_BW_LD + (lane & 31)];
-#pragma unroll
-                for (int j = 0; j < 16; j++) acc1[j] = fmaf(U[p * MR_BW_LD + (lane >> 5) + 2 * j], vk, acc1[j]);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        {   // gW0[o][k] += gh1[o] * a0[k]
-            for (int o = 0; o < 32; o++) U[lane * MR_BW_LD + o] = gh1[o];
-            for (int k = 0; k < 32; k++) V[lane * MR_BW_LD + k] = a0[k];
-            __builtin_amdgcn_wave_barrier();
-            for (int p = 0; p < 64; p++) {
-                const float vk = V[p * MR_BW_LD + (lane & 31)];
-#pragma unroll
-                for (int j = 0; j < 16; j++) acc0[j] = fmaf(U[p * MR_BW_LD + (lane >> 5) + 2 * j], vk, acc0[j]);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        // hash-grid gradient: fp32 atomics into the master-precision gradient table (tcnn accumulates its grid gradient the same way). The 64
-        // points of a wave are neighbouring pixels: on the coarse levels they fall into a handful of cells, and 164 M scattered global atomics
-        // (with that contention) were what the kernel waited for. Levels < MR_BW_COARSE therefore go through a per-wave LDS table (the wave's
-        // staging area, free after the outer products: open addressing, two probes, overflow straight to global memory), flushed per tile.
-        if (g_params) {
-            // Round 6 (profiles/r06_atomic_rate.txt): the memory side takes 21 G scattered atomic REQUESTS per second, and the lanes of one instruction that fall into the
-            // same 32-byte sector are one request. A table entry's two features are 8 consecutive bytes: every update is issued by a PAIR of lanes (even lane: feature 0,
-            // odd lane: feature 1 of the same entry; first the even lane's entry, then the odd lane's) — half the requests for the same adds, in the same order per word.
-            int* const keys = reinterpret_cast<int*>(U); float* const vals = V;
-            for (int e = lane; e < MR_BW_TABLE; e += 64) { keys[e] = -1; vals[2 * e] = 0.f; vals[2 * e + 1] = 0.f; }
-            __builtin_amdgcn_wave_barrier();
-            const int odd = lane & 1;
-            for (int lv = 0; lv < MR_LEVELS; lv++) {      // every lane walks every level (a dead or gradient-free lane contributes nothing): the pairs must stay together
-                const float scale = L.scale[lv]; const uint32_t res = L.res[lv], size = L.size[lv];
-                float p[3]; uint32_t pg[3];
-#pragma unroll
-                for (int d = 0; d < 3; d++) { float q = fmaf(scale, x[d], 0.5f); float fl = floorf(q); pg[d] = (uint32_t)(int)fl; p[d] = q - fl; }
-                const float g0 = ga0[2 * lv], g1 = ga0[2 * lv + 1];
-                const bool lvalid = live && !(g0 == 0.f && g1 == 0.f);
-                if (!__ballot(lvalid)) continue;
-                uint32_t ci[8]; corner_indices(size, res, pg, ci);
-#pragma unroll
-                for (uint32_t idx = 0; idx < 8; idx++) {
-                    float w = 1.f;
-#pragma unroll
-                    for (int d = 0; d < 3; d++) w *= (idx & (1u << d)) == 0 ? 1 - p[d] : p[d];
-                    const uint32_t e = L.offset[lv] + ci[idx];
-                    bool direct = lvalid;
-                    if (lv < MR_BW_COARSE && lvalid) {
-                        uint32_t h = (e * 2654435761u) >> (32 - MR_BW_TABLE_LOG2);
-#pragma unroll
-                        for (int probe = 0; probe < 2 && direct; probe++) {
-                            const int old = atomicCAS(&keys[h], -1, (int)e);
-                            if (old == -1 || old == (int)e) { atomicAdd(&vals[2 * h], w * g0); atomicAdd(&vals[2 * h + 1], w * g1); direct = false; }
-                            h = (h + 1) & (MR_BW_TABLE - 1);
-                        }
-                    }
-                    const float v0 = w * g0, v1 = w * g1;
-#pragma unroll
-                    for (int r = 0; r < 2; r++) {
-                        const int src = (lane & ~1) | r;
-                        const uint32_t e_s = (uint32_t)__shfl((int)e, src, 64);
-                        const int d_s = __shfl(direct ? 1 : 0, src, 64);
-                        const float a_s = __shfl(v0, src, 64), b_s = __shfl(v1, src, 64);
-                        if (d_s) atomicAdd(&g_params[2 * (size_t)e_s + odd], odd ? b_s : a_s);
-                    }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int j = lane; j < 2 * MR_BW_TABLE; j += 64) {      // lane pairs again: entry j / 2, feature j % 2
-                const int key = keys[j >> 1];
-                if (key >= 0) atomicAdd(&g_params[2 * (size_t)key + (j & 1)], vals[j]);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (g_pos && live) position_gradient(M, L, x, xraw, ga0, g_pos, i);
+        outer_accumulate<3>(U, V, lane, gz2, h2, acc2);       // gW2[o][k] += gz2[o] * h2[k]   (6 x 32 = 192 entries)
+        outer_accumulate<16>(U, V, lane, gh2, h1, acc1);      // gW1[o][k] += gh2[o] * h1[k]
+        outer_accumulate<16>(U, V, lane, gh1, a0, acc0);      // gW0[o][k] += gh1[o] * a0[k]
+        if (g_params) grid_gradient_scatter(L, x, ga0, live, lane, U, V, g_params);
     }
-    // reduce the four waves' register accumulators through LDS (entry e = lane + 64 j  <->  [o = e / 32][k = e % 32]), one global atomic per entry
-    __syncthreads();
-    float* red = &sU[0][0];            // 2 240 floats needed, 4 * 64 * 33 available
-    for (int i = threadIdx.x; i < 2240; i += blockDim.x) red[i] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) { atomicAdd(&red[lane + 64 * j], acc0[j]); atomicAdd(&red[1024 + lane + 64 * j], acc1[j]); }
-#pragma unroll
-    for (int j = 0; j < 3; j++) atomicAdd(&red[2048 + lane + 64 * j], acc2[j]);
-    __syncthreads();
-    for (int k = threadIdx.x; k < 1024; k += blockDim.x) { if (g_w0 && red[k] != 0.f) atomicAdd(&g_w0[k], red[k]); if (g_w1 && red[1024 + k] != 0.f) atomicAdd(&g_w1[k], red[1024 + k]); }
-    for (int k = threadIdx.x; k < 192; k += blockDim.x) if (g_w2 && red[2048 + k] != 0.f) atomicAdd(&g_w2[k], red[2048 + k]);
+    reduce_weight_gradients(&sU[0][0], lane, acc0, acc1, acc2, g_w0, g_w1, g_w2);      // 2 240 floats needed, 4 * 64 * 33 available
 }
 
 }  // namespace mr
@@ -537,11 +510,8 @@ int mirres_matnet_bwd(const mirres_matnet_t* m, const float* pos, int n, const f
                       float* g_w1, float* g_w2, float* g_pos, void* stream) {
     if (!m || !pos || !grad_out || n < 0) { set_error("mirres_matnet_bwd: bad argument"); return MIRRES_E_ARG; }
     if (n == 0) return MIRRES_OK;
-    MatNetB M; M.grid = reinterpret_cast<const __half2*>(m->grid_f16); M.w0 = m->w0; M.w1 = m->w1; M.w2 = m->w2;
-    for (int i = 0; i < 3; i++) { M.aabb_min[i] = m->aabb_min[i]; M.aabb_max[i] = m->aabb_max[i]; }
-    for (int i = 0; i < 6; i++) { M.mn[i] = m->out_min[i]; M.mx[i] = m->out_max[i]; }
     int grd = grid_for(n, MR_BLOCK); if (grd > 256 * 4) grd = 256 * 4;      // workgroups loop over point tiles and keep the weight gradients in registers
-    k_matnet_bwd<<<grd, MR_BLOCK, 0, (hipStream_t)stream>>>(M, host_levels_b(), pos, n, grad_out, g_params_f32, g_w0, g_w1, g_w2, g_pos);
+    k_matnet_bwd<<<grd, MR_BLOCK, 0, (hipStream_t)stream>>>(matd(m), host_levels(nullptr), pos, n, grad_out, g_params_f32, g_w0, g_w1, g_w2, g_pos);
     MR_LAUNCH_CHECK("matnet_bwd");
     return MIRRES_OK;
 }

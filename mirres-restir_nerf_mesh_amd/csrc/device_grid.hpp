@@ -1,10 +1,14 @@
-// device_grid.hpp — index arithmetic and the fp16 interpolation step of the multi-resolution hash grid (tcnn HashGrid semantics), shared by the forward
-// kernels (matnet.hip) and the backward's forward recompute / gradient scatter (backward.hip): one definition, so the recompute reproduces the forward's bits.
+// device_grid.hpp — the material field's device code (multi-resolution hash grid with tcnn HashGrid semantics + the bias-free 32-32-32-6 MLP), shared by the forward
+// kernels (matnet.hip) and the backward's forward recompute, position gradient and gradient scatter (backward.hip): one definition, so the recompute reproduces the
+// forward's bits. What both sides call: normalise_pos (point -> unit cube), level_cell / corner_indices / corner_weight (cell, table entries and trilinear weights of
+// one level), interpolate_cell over weighted_half2 (the fp16 interpolation), dense_layer (one k-ascending fmaf-chain layer) and stage_weights; MatNetD / matd() are
+// the field as every kernel receives it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <cmath>
+#include "engine.hpp"
 #include "device_math.hpp"
 
 namespace mr {
@@ -42,6 +46,20 @@ MR_DEV uint32_t grid_index(uint32_t size, uint32_t res, uint32_t px, uint32_t py
     return index % size;
 }
 
+// The cell of x (in [0,1]^3) on a level: pos = fmaf(scale, x, 0.5) (tcnn grid.h), pg = its integer part (corner 0 of the cell), p = its fraction.
+MR_DEV void level_cell(float scale, const float x[3], uint32_t pg[3], float p[3]) {
+#pragma unroll
+    for (int d = 0; d < 3; d++) { float q = fmaf(scale, x[d], 0.5f); float fl = floorf(q); pg[d] = (uint32_t)(int)fl; p[d] = q - fl; }
+}
+// Trilinear weight of corner idx (bit d set: the far corner along d): the product over d, in ascending d, of corner_factor. The position gradient takes the
+// product of two of the three factors.
+MR_DEV float corner_factor(const float p[3], uint32_t idx, int d) { return (idx & (1u << d)) == 0 ? 1 - p[d] : p[d]; }
+MR_DEV float corner_weight(const float p[3], uint32_t idx) {
+    float w = 1.f;
+#pragma unroll
+    for (int d = 0; d < 3; d++) w *= corner_factor(p, idx, d);
+    return w;
+}
 // (T)(weight * value) of tcnn's interpolation (grid.h): the fp32 product is ROUNDED TO fp32 and then to fp16. Left to itself the compiler turns
 // fptrunc(fmul) into v_fma_mixlo_f16 — one rounding of the exact product — whenever it does not happen to pack the multiplication with a neighbour
 // (round 2: -fno-vectorize changed 1 feature in ~10^4 by one fp16 ulp against tcnn's two-step rounding); the empty asm pins the two-step form in every build.
@@ -52,6 +70,13 @@ MR_DEV __half2 weighted_half2(float w, __half2 v) {
     asm("" : "+v"(p0), "+v"(p1));
     return __floats2half2_rn(p0, p1);
 }
+// One level's two features: the eight corners' entries, weighted and summed in fp16 in corner order (tcnn's accumulation).
+MR_DEV __half2 interpolate_cell(const float p[3], const __half2 v[8]) {
+    __half2 r = __floats2half2_rn(0.f, 0.f);
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) r = __hadd2(r, weighted_half2(corner_weight(p, idx), v[idx]));
+    return r;
+}
 // The eight table entries of a cell, tcnn's grid_index for every corner (dx, dy, dz) at once — same values as grid_index(size, res, px + dx, py + dy,
 // pz + dz), without its per-corner multiplications and its u32 modulo (a ~30-instruction sequence, eight times per level: it was most of the
 // encoder's instructions). The level kind is uniform, so the branch is scalar:
@@ -60,10 +85,10 @@ MR_DEV __half2 weighted_half2(float w, __half2 v) {
 //   dense: px + py * res + pz * res^2 plus the corner strides; an index can pass `size` only at the far faces (a corner coordinate equal to res),
 //     where it stays below 2 * size (res + res^2 + res^3 < 2 res^3), so `% size` is one conditional subtraction — the modulo is kept behind a
 //     branch no wave takes for points inside the unit cube.
+MR_DEV bool hashed(uint32_t size, uint32_t res) { return (uint64_t)res * res * res > (uint64_t)size && (size & (size - 1u)) == 0u; }
 MR_DEV void corner_indices(uint32_t size, uint32_t res, const uint32_t pg[3], uint32_t idx[8]) {
-    const bool hashed = (uint64_t)res * res * res > (uint64_t)size && (size & (size - 1u)) == 0u;
     const bool dense = (uint64_t)res * res * res <= (uint64_t)size;
-    if (hashed) {
+    if (hashed(size, res)) {
         const uint32_t m = size - 1u;
         const uint32_t hx[2] = {pg[0], pg[0] + 1u};
         const uint32_t y0 = pg[1] * 2654435761u, z0 = pg[2] * 805459861u;
@@ -113,5 +138,43 @@ MR_DEV void gather_cell(const __half2* __restrict__ g, const uint32_t ci[8], boo
             v[c + 1] = as_half2(o);
         }
     }
+}
+
+// ---------------------------------------------------------------- the field as the kernels receive it
+struct MatNetD { const __half2* grid; const float *w0, *w1, *w2; float aabb_min[3], aabb_max[3], mn[6], mx[6]; };
+static MatNetD matd(const mirres_matnet_t* m) {
+    MatNetD M; M.grid = reinterpret_cast<const __half2*>(m->grid_f16); M.w0 = m->w0; M.w1 = m->w1; M.w2 = m->w2;
+    for (int i = 0; i < 3; i++) { M.aabb_min[i] = m->aabb_min[i]; M.aabb_max[i] = m->aabb_max[i]; }
+    for (int i = 0; i < 6; i++) { M.mn[i] = m->out_min[i]; M.mx[i] = m->out_max[i]; }
+    return M;
+}
+// point i in the field's box: xraw = (pos - aabb_min) / (aabb_max - aabb_min), x = xraw clamped to [0, 1] (torch.clamp: the backward gates the position
+// gradient on xraw)
+MR_DEV float unit_coord(const MatNetD& M, const float* __restrict__ pos, size_t i, int d) { return (pos[3 * i + d] - M.aabb_min[d]) / (M.aabb_max[d] - M.aabb_min[d]); }
+MR_DEV void normalise_pos(const MatNetD& M, const float* __restrict__ pos, size_t i, float x[3], float xraw[3]) {
+#pragma unroll
+    for (int d = 0; d < 3; d++) { xraw[d] = unit_coord(M, pos, i, d); x[d] = fminf(fmaxf(xraw[d], 0.f), 1.f); }
+}
+MR_DEV void normalise_pos(const MatNetD& M, const float* __restrict__ pos, size_t i, float x[3]) { float xraw[3]; normalise_pos(M, pos, i, x, xraw); }
+// weights staged once per block in LDS (row-major [o][k] as given: the lanes of a wave read the same word, a broadcast)
+MR_DEV void stage_weights(const MatNetD& M, float* sw0, float* sw1, float* sw2) {
+    for (int i = threadIdx.x; i < 1024; i += blockDim.x) { sw0[i] = M.w0[i]; sw1[i] = M.w1[i]; }
+    for (int i = threadIdx.x; i < 192; i += blockDim.x) sw2[i] = M.w2[i];
+    __syncthreads();
+}
+// One bias-free layer of 32 inputs: out[o] = act(chain, o) with the chain acc = fmaf(in[k], w[o][k], acc) from 0 in ASCENDING k (torch.nn.Linear in fp32 written as
+// a chain, and the order k_mlp_mfma's K = 2 steps reproduce). The backward's recompute calls this too: its ReLU masks are the forward's only because the order is.
+// act is applied where the chain ends (ActRelu, ActNone, or the forward's sigmoid / range): with the output layer's sigmoids in a loop of their own the compiler
+// hoists that layer's 192 weight loads and the per-lane forward kernels go from 75 to 200 registers. UNROLL outputs are unrolled together: the per-lane forward
+// kernels take a hidden layer in fours (a full unroll: 218 registers), k_matnet_bwd whole (in fours: 300 B more scratch); profiles/matnet_shared_regs.txt.
+struct ActRelu { MR_DEV float operator()(float a, int) const { return fmaxf(a, 0.f); } };
+struct ActNone { MR_DEV float operator()(float a, int) const { return a; } };
+template <int NO, int UNROLL = NO, class Act>
+MR_DEV void dense_layer(const float* w, const float in[32], float out[NO], Act act) {
+#pragma unroll UNROLL
+    for (int o = 0; o < NO; o++) { float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 32; k++) acc = fmaf(in[k], w[o * 32 + k], acc);
+        out[o] = act(acc, o); }
 }
 }  // namespace mr

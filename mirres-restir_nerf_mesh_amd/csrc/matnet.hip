@@ -23,57 +23,24 @@ MR_DEV void encode_point(const GridLevels& L, const __half2* __restrict__ grid, 
     for (int lv = 0; lv < MR_LEVELS; lv++) {
         const float scale = L.scale[lv]; const uint32_t res = L.res[lv], size = L.size[lv];
         const __half2* __restrict__ g = grid + L.offset[lv];
-        float pos[3]; uint32_t pg[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) { float p = fmaf(scale, x[d], 0.5f); float fl = floorf(p); pg[d] = (uint32_t)(int)fl; pos[d] = p - fl; }
-        uint32_t ci[8];
+        uint32_t pg[3], ci[8]; float p[3];
+        level_cell(scale, x, pg, p);
         corner_indices(size, res, pg, ci);
         __half2 v[8];
-        gather_cell(g, ci, (uint64_t)res * res * res > (uint64_t)size && (size & (size - 1u)) == 0u, v);
-        __half2 r = __floats2half2_rn(0.f, 0.f);
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++) {
-            float w = 1.f;
-#pragma unroll
-            for (int d = 0; d < 3; d++) w *= (idx & (1u << d)) == 0 ? 1 - pos[d] : pos[d];
-            r = __hadd2(r, weighted_half2(w, v[idx]));
-        }
+        gather_cell(g, ci, hashed(size, res), v);
+        const __half2 r = interpolate_cell(p, v);
         enc[2 * lv] = __low2half(r); enc[2 * lv + 1] = __high2half(r);
     }
 }
 
-struct MatNetD { const __half2* grid; const float *w0, *w1, *w2; float aabb_min[3], aabb_max[3], mn[6], mx[6]; };
-
-// weights staged once per block in LDS (transposed to [k][o] so that the lanes of a wave read the same word: broadcast)
-MR_DEV void stage_weights(const MatNetD& M, float* sw0, float* sw1, float* sw2) {
-    for (int i = threadIdx.x; i < 1024; i += blockDim.x) { sw0[i] = M.w0[i]; sw1[i] = M.w1[i]; }
-    for (int i = threadIdx.x; i < 192; i += blockDim.x) sw2[i] = M.w2[i];
-    __syncthreads();
-}
+// the MLP of one point on the staged weights: fp16 features -> sigmoid / affine range
 MR_DEV void mlp_point(const float* sw0, const float* sw1, const float* sw2, const MatNetD& M, const __half enc[32], float out[6]) {
     float a[32], h[32];
 #pragma unroll
     for (int i = 0; i < 32; i++) a[i] = __half2float(enc[i]);
-#pragma unroll 4
-    for (int o = 0; o < 32; o++) { float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 32; k++) acc = fmaf(a[k], sw0[o * 32 + k], acc);
-        h[o] = fmaxf(acc, 0.f); }
-#pragma unroll 4
-    for (int o = 0; o < 32; o++) { float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 32; k++) acc = fmaf(h[k], sw1[o * 32 + k], acc);
-        a[o] = fmaxf(acc, 0.f); }
-#pragma unroll
-    for (int o = 0; o < 6; o++) { float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 32; k++) acc = fmaf(a[k], sw2[o * 32 + k], acc);
-        float s = mrf_sigmoid(acc);
-        out[o] = s * (M.mx[o] - M.mn[o]) + M.mn[o]; }
-}
-MR_DEV void normalise_pos(const MatNetD& M, const float* __restrict__ pos, size_t i, float x[3]) {
-#pragma unroll
-    for (int d = 0; d < 3; d++) x[d] = fminf(fmaxf((pos[3 * i + d] - M.aabb_min[d]) / (M.aabb_max[d] - M.aabb_min[d]), 0.f), 1.f);
+    dense_layer<32, 4>(sw0, a, h, ActRelu());
+    dense_layer<32, 4>(sw1, h, a, ActRelu());
+    dense_layer<6>(sw2, a, out, [&](float z, int o) { return mrf_sigmoid(z) * (M.mx[o] - M.mn[o]) + M.mn[o]; });
 }
 
 __global__ void __launch_bounds__(MR_BLOCK) k_matnet_fwd(MatNetD M, GridLevels L, const float* __restrict__ pos, int n, float* __restrict__ out,
@@ -327,7 +294,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_active_from_live(const float* __re
                 uint32_t q[3];
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
-                    const float u = (pos[3 * (size_t)sl[j] + a] - M.aabb_min[a]) / (M.aabb_max[a] - M.aabb_min[a]);
+                    const float u = unit_coord(M, pos, (size_t)sl[j], a);
                     q[a] = (uint32_t)fminf(fmaxf(u * (float)(1 << bits), 0.f), (float)((1 << bits) - 1));      // (NaN -> 0: any bucket will do)
                 }
                 const uint32_t key = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
@@ -441,13 +408,6 @@ __global__ void __launch_bounds__(MR_BLOCK) k_pack_grid(const float* __restrict_
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) out[i] = __half_as_ushort(__float2half(in[i]));
-}
-
-static MatNetD matd(const mirres_matnet_t* m) {
-    MatNetD M; M.grid = reinterpret_cast<const __half2*>(m->grid_f16); M.w0 = m->w0; M.w1 = m->w1; M.w2 = m->w2;
-    for (int i = 0; i < 3; i++) { M.aabb_min[i] = m->aabb_min[i]; M.aabb_max[i] = m->aabb_max[i]; }
-    for (int i = 0; i < 6; i++) { M.mn[i] = m->out_min[i]; M.mx[i] = m->out_max[i]; }
-    return M;
 }
 
 int launch_matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rm, int use_scale, const float* scale3,

@@ -184,3 +184,29 @@ def test_material_field_adjoint_at_frame_point_order(order, oracle, scene_mod):
         return pos, torch.rand((len(idx), 6), device="cuda", generator=g)
     assert len(pos_np) % 64 != 0
     _material_field_check(oracle, scene_mod, points, 10000 if order == "frame_pixels" else 1000, kernel_encoding=True)
+
+
+# n points -> (floor, entries the float64 reference alone touches on the CPU with these inputs); at n = 1 an interior point touches 16 levels x 8 corners x 2 features
+SMALL_N = {1: (255, 256), 63: (15000, 15950), 65: (16000, 16456), 257: (60000, 63164)}
+
+
+def small_n_points(n):
+    """Inputs of the small-n cases: numpy-seeded, so that tests/test_matnet_small_n_counts.py recounts SMALL_N without a GPU."""
+    rng = np.random.RandomState(n)
+    return (rng.rand(n, 3) * 1.6 - 0.8).astype(np.float32), rng.rand(n, 6).astype(np.float32)
+
+
+@pytest.mark.parametrize("n", sorted(SMALL_N))
+def test_material_field_adjoint_at_small_point_counts(n, oracle, scene_mod):
+    """The same comparison, at the same tolerances, where k_matnet_bwd runs nearly empty: n = 1 (one live lane in the only wave), 63 (a ragged single tile),
+    65 (a second tile, i.e. a second wave, with one live lane) and 257 (a second workgroup with one live lane: the cross-wave LDS reduction of the weight
+    gradients and the cross-workgroup atomics on them). Points are uniform in the inner 80 % of the box, cotangents uniform in [0, 1), both from a numpy
+    generator seeded with n so that the float64 reference can be run without a GPU: SMALL_N holds the number of table entries it touches there
+    (recounted by tests/test_matnet_small_n_counts.py)."""
+    floor, counted = SMALL_N[n]
+    assert counted > floor
+
+    def points(torch, g):
+        pos, cot = small_n_points(n)
+        return torch.from_numpy(pos).cuda(), torch.from_numpy(cot).cuda()
+    _material_field_check(oracle, scene_mod, points, floor, kernel_encoding=True)
