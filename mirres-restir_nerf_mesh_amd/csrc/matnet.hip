@@ -410,19 +410,25 @@ __global__ void __launch_bounds__(MR_BLOCK) k_pack_grid(const float* __restrict_
     for (; i < n; i += stride) out[i] = __half_as_ushort(__float2half(in[i]));
 }
 
-int launch_matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rm, int use_scale, const float* scale3,
-                               int32_t* index, uint32_t* count, hipStream_t s, const int32_t* live, const uint32_t* live_count, const GridSort* gs) {
+// what a development entry point copies out of the lookup, in stream order between the launches (each n entries; any may be null): the compacted list before the
+// sort, the list the lookup kernel walks, and the keys in that list's order (sorted lists only)
+struct ScatterTap { int32_t* unsorted; int32_t* walked; uint32_t* walked_keys; };
+
+// sort_on: order the list by position (needs a live list and the GridSort scratch); bits = 1 .. 8 per axis of the key
+static int matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rm, int use_scale, const float* scale3,
+                               int32_t* index, uint32_t* count, hipStream_t s, const int32_t* live, const uint32_t* live_count, const GridSort* gs, bool sort_on, int bits,
+                               const ScatterTap* tap) {
     float sx = scale3 ? scale3[0] : 1.f, sy = scale3 ? scale3[1] : 1.f, sz = scale3 ? scale3[2] : 1.f;
     MR_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
-    static const bool sort_on = [] { const char* e = getenv("MIRRES_GRID_SORT"); return !(e && e[0] == '0'); }();
     const bool sort = sort_on && live && gs && gs->keys && gs->keys2 && gs->sorted && gs->hist;
+    const uint32_t* list_keys = nullptr;
     const int32_t* list = index;     // the list the lookup kernel walks
     // (with a live list the whole-map clamp of use_scale is not applied to slots without a vertex: nothing reads their albedo)
     if (live) {
         int ga = grid_for(n, MR_BLOCK * 8); if (ga > 256 * 8) ga = 256 * 8;
         if (sort) {
-            static const int bits = [] { const char* e = getenv("MIRRES_GS_BITS"); const int b = e ? atoi(e) : MR_GS_BITS; return b < 1 ? 1 : (b > 8 ? 8 : b); }();
             k_active_from_live<true><<<ga, MR_BLOCK, 0, s>>>(occ, live, live_count, index, count, matd(m), pos, gs->keys, bits);
+            if (tap && tap->unsorted) MR_HIP(hipMemcpyAsync(tap->unsorted, index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
             uint32_t* const hist = gs->hist; uint32_t* const totals = hist + 256 * MR_LS_GRID;
             // LSD passes over the key's bytes, ping-pong (keys, index) <-> (keys2, sorted); after an even number of passes the sorted list is where the unsorted one was
             uint32_t *ka = gs->keys, *kb = gs->keys2; int32_t *va = index, *vb = gs->sorted;
@@ -432,14 +438,27 @@ int launch_matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const
                 k_ls_scatter<<<MR_LS_GRID, MR_BLOCK, 0, s>>>(ka, va, kb, vb, count, shift, hist, totals);
                 uint32_t* tk = ka; ka = kb; kb = tk; int32_t* tv = va; va = vb; vb = tv;
             }
-            list = va;
-        } else k_active_from_live<false><<<ga, MR_BLOCK, 0, s>>>(occ, live, live_count, index, count, MatNetD(), nullptr, nullptr, 0);
+            list = va; list_keys = ka;
+        } else {
+            k_active_from_live<false><<<ga, MR_BLOCK, 0, s>>>(occ, live, live_count, index, count, MatNetD(), nullptr, nullptr, 0);
+            if (tap && tap->unsorted) MR_HIP(hipMemcpyAsync(tap->unsorted, index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+        }
     }
     else k_active_list<<<grid_for(n, MR_BLOCK * MR_AL_PER), MR_BLOCK, 0, s>>>(occ, n, index, count, kd, use_scale);
+    if (tap && tap->walked) MR_HIP(hipMemcpyAsync(tap->walked, list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    if (tap && tap->walked_keys && list_keys) MR_HIP(hipMemcpyAsync(tap->walked_keys, list_keys, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
     int g = grid_for(n, MR_BLOCK); if (g > 256 * 8) g = 256 * 8;
     k_mlp_mfma<1, 2><<<g, MR_BLOCK, 0, s>>>(matd(m), host_levels(nullptr), nullptr, pos, list, count, 0, nullptr, kd, rm, use_scale, sx, sy, sz);
     MR_LAUNCH_CHECK("matnet_scatter_mfma");
     return 0;
+}
+
+// mirres_render's entry: the two knobs are read once per process (MIRRES_GRID_SORT=0: slot order; MIRRES_GS_BITS: bits per axis of the key)
+int launch_matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rm, int use_scale, const float* scale3,
+                               int32_t* index, uint32_t* count, hipStream_t s, const int32_t* live, const uint32_t* live_count, const GridSort* gs) {
+    static const bool sort_on = [] { const char* e = getenv("MIRRES_GRID_SORT"); return !(e && e[0] == '0'); }();
+    static const int bits = [] { const char* e = getenv("MIRRES_GS_BITS"); const int b = e ? atoi(e) : MR_GS_BITS; return b < 1 ? 1 : (b > 8 ? 8 : b); }();
+    return matnet_scatter_mfma(m, occ, pos, n, kd, rm, use_scale, scale3, index, count, s, live, live_count, gs, sort_on, bits, nullptr);
 }
 
 int launch_matnet_scatter(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rm, int use_scale, const float* scale3,
@@ -499,6 +518,31 @@ int mirres_matnet_scatter(const mirres_matnet_t* m, const float* occ, const floa
 int mirres_debug_matnet_scatter_mfma(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rough_metal, int32_t* index, uint32_t* count, void* stream) {
     if (!m || !occ || !pos || !kd || !rough_metal || !index || !count || n <= 0) return MIRRES_E_ARG;
     return launch_matnet_scatter_mfma(m, occ, pos, n, kd, rough_metal, 0, nullptr, index, count, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}
+
+// the same with the albedo scale of mirres_render_args_t (use_scale, h_scale3: host float[3] or null): without a live list the clamp of use_scale reaches every row
+int mirres_debug_matnet_scatter_mfma_scaled(const mirres_matnet_t* m, const float* occ, const float* pos, int n, float* kd, float* rough_metal, int use_scale,
+                                            const float* h_scale3, int32_t* index, uint32_t* count, void* stream) {
+    if (!m || !occ || !pos || !kd || !rough_metal || !index || !count || n <= 0) { set_error("mirres_debug_matnet_scatter_mfma_scaled: bad argument"); return MIRRES_E_ARG; }
+    return launch_matnet_scatter_mfma(m, occ, pos, n, kd, rough_metal, use_scale, h_scale3, index, count, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}
+
+// development aid (not part of include/mirres.h): the lookup as mirres_render's batches run it — live-slot list (live: int32[<= nv] slots in [0, nv), each once;
+// live_count: uint32[1] on the DEVICE) -> slots with occ >= 0.5, compacted -> (sort != 0) ordered by the Morton key of their positions, `bits` = 1 .. 8 per axis
+// -> fused gather + MFMA MLP -> scatter into kd / rough_metal by slot.  Scratch as mirres_render sizes it: index, keys, keys2, sorted of nv entries each, hist of
+// 4 * (256 * 1024 + 256) bytes, count: uint32[1] (the number of listed slots afterwards).  Copied out in stream order, each nv entries of which the first *count
+// are meaningful, any may be null: out_unsorted = the compacted list before the sort, out_walked = the list the lookup kernel walked, out_keys = the keys in
+// that list's order (written only when sort != 0).
+int mirres_debug_matnet_scatter_live(const mirres_matnet_t* m, const float* occ, const float* pos, int nv, float* kd, float* rough_metal, int use_scale,
+                                     const float* h_scale3, const int32_t* live, const uint32_t* live_count, int sort, int bits, int32_t* index, uint32_t* keys,
+                                     uint32_t* keys2, int32_t* sorted, uint32_t* hist, uint32_t* count, int32_t* out_unsorted, int32_t* out_walked,
+                                     uint32_t* out_keys, void* stream) {
+    if (!m || !occ || !pos || !kd || !rough_metal || !live || !live_count || !index || !keys || !keys2 || !sorted || !hist || !count || nv <= 0 || bits < 1 || bits > 8) {
+        set_error("mirres_debug_matnet_scatter_live: bad argument"); return MIRRES_E_ARG;
+    }
+    const GridSort gs = {keys, keys2, sorted, hist};
+    const ScatterTap tap = {out_unsorted, out_walked, out_keys};
+    return matnet_scatter_mfma(m, occ, pos, nv, kd, rough_metal, use_scale, h_scale3, index, count, (hipStream_t)stream, live, live_count, &gs, sort != 0, bits, &tap);
 }
 
 }  // extern "C"

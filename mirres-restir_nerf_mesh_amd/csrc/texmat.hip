@@ -143,3 +143,12 @@ extern "C" int mirres_texmat_lookup(const mirres_texmat_t* t, const float* occ, 
     MR_LAUNCH_CHECK("texmat_lookup");
     return MIRRES_OK;
 }
+
+// development aid (not part of include/mirres.h): the lookup as mirres_render's batches run it (launch_texmat_live) on caller-given lists — live: int32 slots in
+// [0, nv), live_count: uint32[1] on the DEVICE, slot_c: int32[nv] ray of every slot (or -1), ray_prim: int32 triangle of every ray; occ may be null.
+extern "C" int mirres_debug_texmat_live(const mirres_texmat_t* t, const float* occ, const float* pos, int nv, float* kd, float* rough_metal, int use_scale,
+                                        const float* h_scale3, const int32_t* live, const uint32_t* live_count, const int32_t* slot_c, const int32_t* ray_prim,
+                                        void* stream) {
+    if (!pos || !kd || !rough_metal || !live || !live_count || !slot_c || !ray_prim || nv <= 0) { set_error("mirres_debug_texmat_live: bad argument"); return MIRRES_E_ARG; }
+    return launch_texmat_live(t, occ, pos, nv, kd, rough_metal, use_scale, h_scale3, live, live_count, slot_c, ray_prim, (hipStream_t)stream);
+}
