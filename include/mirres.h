@@ -437,12 +437,23 @@ int mirres_mc_emit(const float* vol, int nx, int ny, int nz, float iso, const vo
  * <= 1024) -> vol f32[S][S][S].  renderer.py:532-539: vol f32[R][R][R] *= (grid_vol[S][S][S] upsampled by F.interpolate(mode='nearest') > thresh).          */
 int mirres_mc_unpack_morton(const float* grid, int S, float* vol, void* stream);
 int mirres_mc_mask_nearest(float* vol, int R, const float* grid_vol, int S, float thresh, void* stream);
+/* renderer.py:653-655, the outer cascades (cas >= 1) of export_stage0: grid_vol f32[S][S][S] (S a power of two in [2, 1024]) resampled to R^3 (R in [1, 1024]; R < S,
+ * R == S and non-integer ratios included) as F.interpolate(mode='trilinear', align_corners=False) does — per axis src = max(scale * (d + 0.5f) - 0.5f, 0) with
+ * scale = (float)S / R, i0 = floor(src), i1 = min(i0 + 1, S - 1), l1 = src - i0, l0 = 1 - l1; the eight products summed w inside h inside t; every product and
+ * sum one fp32 rounding, zero weights multiplied (a non-finite neighbour makes the value NaN) — then nan_to_num(., 0) and > thresh: occ_out f32[R][R][R] = 1.0f / 0.0f
+ * (NaN -> 0, +inf -> 1).  value_out (NULL: not stored) f32[R][R][R] receives the interpolated value itself.                                                     */
+int mirres_mc_occupancy_trilinear(const float* grid_vol, int S, int R, float thresh, float* occ_out, float* value_out, void* stream);
 /* mark_unseen_triangles (renderer.py:1421-1427): seen[id - 1] = 1 for the triangle id (+ 1, fourth component) of every pixel of rast f32[n,4]; id 0 (background)
  * marks nothing — the reference's mask[-1] += 1 for background pixels is not reproduced.  seen u8[T] is the caller's, cleared by the caller. */
 int mirres_mesh_mark_seen(const float* rast, long long n, int T, uint8_t* seen, void* stream);
 /* One ring of apply_selection_dilatation (meshutils.py:113-114): a vertex is selected when a selected face uses it (vert_flags u8[V], scratch, cleared inside),
  * then face_out[f] = any of its vertices selected.  face_in and face_out (u8[T]) are different buffers.                                                       */
 int mirres_mesh_dilate(const int32_t* tris, int T, int V, const uint8_t* face_in, uint8_t* vert_flags, uint8_t* face_out, void* stream);
+/* remove_selected_verts (meshutils.py:159-181) as export_stage0 calls it (renderer.py:663, :676): keep_face[f] = 0 iff some vertex of face f is selected, else 1.
+ * box = {xmn, ymn, zmn, xmx, ymx, zmx} (host doubles).  outside = 0 selects x <= xmx && x >= xmn && y ... (the closed box), outside = 1 selects
+ * x <= xmn || x >= xmx || y ... (everything not strictly inside).  Coordinates are compared as doubles with the given doubles; a NaN coordinate is selected by
+ * neither; a face with an index outside [0, V) is dropped.  The caller compacts with mirres_mesh_compact(keep_face).                                            */
+int mirres_mesh_select_box(const float* verts, int V, const int32_t* tris, int T, const double* box, int outside, uint8_t* keep_face, void* stream);
 /* meshing_remove_selected_faces + meshing_remove_unreferenced_vertices (meshutils.py:118-121, :195): keeps the faces with keep_face[f] != 0 and the vertices they
  * use, both in their old order, indices remapped.  out_verts f32[V,3] / out_tris i32[T,3] are sized for the input; h_counts = {V', T'}; BLOCKS.  `scratch`:
  * mirres_mesh_scratch_bytes(V, T) device bytes.                                                                                                               */
@@ -473,7 +484,10 @@ int mirres_dec_vertex_flags(const unsigned long long* edge_keys, const int32_t* 
 int mirres_dec_quadrics(const float* verts, int V, const int32_t* tris, int T, const int32_t* vstart, const int32_t* vcorner, const int32_t* corner_edge,
                         const int32_t* edge_mult, int E, double* quadrics, void* stream);
 /* mirres_dec_edge (meshutils.py:64-97; optimalplacement as MeshLab's flag): per edge (a, b), Q = Q[a] + Q[b]; position f32[E,3] = the solution of the 3 x 3 system
- * by cofactors rounded to fp32 (optimalplacement and |det| > 1e-9 * max|entry|^3 and finite), else the cheapest of p_a, p_b, fp32(midpoint), ties in that order;
+ * by cofactors rounded to fp32 (optimalplacement == 1 and |det| > 1e-9 * max|entry|^3 and finite), else the cheapest of p_a, p_b, fp32(midpoint), ties in that order;
+ * optimalplacement == 2: the cheaper of p_a, p_b only, as MeshLab collapses with optimalplacement off — every vertex of the result is one of the input's
+ * (renderer.py:685, the outer meshes), and the low word of a key is the edge id times 0x9E3779B1 mod 2^32 (a bijection: equal costs, which a flat mesh has
+ * everywhere, are then ordered without regard to position and a round finds an independent set of useful size; the caller multiplies by the inverse 0x0E8B2F51);
  * cost f64[E] = max(v^T Q v, 0) at that fp32 position; flags i32[E], 0 = valid: 1 multiplicity not 1 or 2, or an end point on an edge with more than two faces;
  * 2 link condition (distinct common neighbours != multiplicity, or both (a, c0, c1) and (b, c0, c1) are faces); 4 interior edge between two boundary vertices;
  * 8 a face around a or b (not both) would turn its normal by acos(0.2) or more or lose its area; 16 cost (as fp32) or position not finite.

@@ -143,8 +143,10 @@ SIGNATURES = {
     "mirres_mc_emit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32, vp, vp, C.c_int, vp, C.c_int, vp]),
     "mirres_mc_unpack_morton": (C.c_int, [vp, C.c_int, vp, vp]),
     "mirres_mc_mask_nearest": (C.c_int, [vp, C.c_int, vp, C.c_int, f32, vp]),
+    "mirres_mc_occupancy_trilinear": (C.c_int, [vp, C.c_int, C.c_int, f32, vp, vp, vp]),
     "mirres_mesh_mark_seen": (C.c_int, [vp, C.c_longlong, C.c_int, vp, vp]),
     "mirres_mesh_dilate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "mirres_mesh_select_box": (C.c_int, [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp]),
     "mirres_mesh_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "mirres_mesh_compact": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
     "mirres_mesh_components": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int), vp]),

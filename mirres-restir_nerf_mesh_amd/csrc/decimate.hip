@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(DEC_BLOCK) k_dec_edge(const float* __restrict_
     const D3 pa = d3_load(pos, a), pb = d3_load(pos, b);
     // placement
     float vx = 0.f, vy = 0.f, vz = 0.f; bool placed = false;
-    if (optimal) {
+    if (optimal == 1) {
         const double c00 = q[4] * q[7] - q[5] * q[5], c01 = q[2] * q[5] - q[1] * q[7], c02 = q[1] * q[5] - q[2] * q[4];
         const double c11 = q[0] * q[7] - q[2] * q[2], c12 = q[1] * q[2] - q[0] * q[5], c22 = q[0] * q[4] - q[1] * q[1];
         const double det = (q[0] * c00 + q[1] * c01) + q[2] * c02;
@@ -158,12 +158,12 @@ __global__ void __launch_bounds__(DEC_BLOCK) k_dec_edge(const float* __restrict_
     double cost;
     if (placed) {
         cost = q_eval(q, (double)vx, (double)vy, (double)vz);
-    } else {                                                                         // p_a, p_b, their midpoint: the cheapest, ties in that order
+    } else {                                                                         // p_a, p_b, their midpoint (optimal == 2: the end points only): the cheapest, ties in that order
         const float mx = (float)(0.5 * (pa.x + pb.x)), my = (float)(0.5 * (pa.y + pb.y)), mz = (float)(0.5 * (pa.z + pb.z));
         const double ca = q_eval(q, pa.x, pa.y, pa.z), cb = q_eval(q, pb.x, pb.y, pb.z), cm = q_eval(q, (double)mx, (double)my, (double)mz);
         cost = ca; vx = (float)pa.x; vy = (float)pa.y; vz = (float)pa.z;
         if (cb < cost) { cost = cb; vx = (float)pb.x; vy = (float)pb.y; vz = (float)pb.z; }
-        if (cm < cost) { cost = cm; vx = mx; vy = my; vz = mz; }
+        if (optimal != 2 && cm < cost) { cost = cm; vx = mx; vy = my; vz = mz; }
     }
     cost = cost > 0.0 ? cost : (cost == cost ? 0.0 : cost);                          // max(cost, 0), a NaN kept for the finiteness bit
     const float cf = (float)cost;
@@ -199,7 +199,11 @@ __global__ void __launch_bounds__(DEC_BLOCK) k_dec_edge(const float* __restrict_
     cost_out[e] = cost;
     epos[3 * (long long)e] = vx; epos[3 * (long long)e + 1] = vy; epos[3 * (long long)e + 2] = vz;
     eflags[e] = flags;
-    keys[e] = flags ? DEC_KEY_NONE : (((unsigned long long)__float_as_uint(cf) << 32) | (unsigned long long)(unsigned)e);
+    // optimal == 2: equal costs are ordered by a bijective scramble of the edge id (e * 0x9E3779B1 mod 2^32; the host multiplies by the inverse).  The mesh of a 0 / 1
+    // volume is flat almost everywhere, cost exactly 0: ordered by the id itself, which follows the grid, an edge is the cheapest of its region only where a flat
+    // stretch begins, and a round collapses a few dozen edges of 10^5 candidates
+    const unsigned low = optimal == 2 ? (unsigned)e * 0x9E3779B1u : (unsigned)e;
+    keys[e] = flags ? DEC_KEY_NONE : (((unsigned long long)__float_as_uint(cf) << 32) | (unsigned long long)low);
 }
 
 // region of an edge: a, b and every vertex of a face around a or b.  mode 0: atomicMin of the key into vkey over the region; mode 1: true when all of them hold the key
@@ -317,7 +321,7 @@ extern "C" int mirres_dec_edge(const float* verts, const double* quadrics, int V
         set_error("mirres_dec_edge: bad argument (V %d, T %d, E %d)", V, T, E); return MIRRES_E_ARG;
     }
     k_dec_edge<<<grid_for((size_t)E, DEC_BLOCK), DEC_BLOCK, 0, (hipStream_t)stream>>>(verts, quadrics, V, tris, vstart, vcorner, edge_keys, edge_mult, vflag, E,
-                                                                                     optimalplacement ? 1 : 0, cost, position, flags, keys);
+                                                                                     optimalplacement == 2 ? 2 : (optimalplacement ? 1 : 0), cost, position, flags, keys);
     MR_LAUNCH_CHECK("dec_edge");
     return MIRRES_OK;
 }

@@ -11,11 +11,17 @@ nvdiffrast behind it.
     field = DensityField.from_checkpoint(ck, bound=1.0)    # self.density (nerf/network.py:177-192): hash-grid encoder + sigma_net + exp, csrc/density.hip
     vol = field.volume(512, grid_vol, thresh)              # :516-541: the --mcubes_reso lattice, masked by the density grid
     export_stage0(save_path, ckpt=..., cameras=(mvps, H, W), resolution=512)
+    occ = occupancy_volume(grid_vol, 256, thresh)          # :653-655: a cascade's grid, trilinear to env_reso^3, nan_to_num, > thresh -> 0 / 1
+    v, t = remove_selected_verts(v, t, box, "inside")      # meshutils.py:159-181 (:663, :676)
+    v, t = outer_shell(grid_vol, cas, bound, 256, thresh, aabb)                 # :642-676: one outer cascade up to (not including) cleaning
+    export_outer_meshes(save_path, ckpt, bound=2)          # :632-698: mesh_1.ply ... for a checkpoint trained with bound > 1 (export_stage0(outer=True))
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
 when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
 collapses independent sets of edges round by round instead of one edge at a time from a global heap, without MeshLab's quality / normal / planar extras, and may
-end one face below the target; the density network is evaluated in fp32 (the reference: fp16 autocast), unfused, and a NaN coordinate counts as out of bounds.
+end one face below the target; the density network is evaluated in fp32 (the reference: fp16 autocast), unfused, and a NaN coordinate counts as out of bounds;
+the outer cascades' vertices are fp32 from marching cubes on (the reference holds float64 until after decimation), and the --sdf / contracted outer mesh
+(:575-629) is not built.
 Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
 import ctypes as C
 import os
@@ -28,7 +34,7 @@ from ._lib import lib, check, ptr, stream_ptr
 
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
            "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "density_layout",
-           "synthetic_checkpoint", "export_stage0"]
+           "synthetic_checkpoint", "export_stage0", "occupancy_volume", "remove_selected_verts", "outer_shell", "export_outer_meshes"]
 
 
 def _dev():
@@ -106,6 +112,74 @@ def index_to_world(vertices, resolution):
     """nerf/renderer.py:553; `resolution` an int or one per axis."""
     r = torch.as_tensor(resolution, dtype=torch.float32, device=vertices.device)
     return (vertices / (r - 1.0) * 2 - 1).to(torch.float32)
+
+
+def occupancy_volume(grid_vol, resolution, thresh, return_values=False):
+    """nerf/renderer.py:653-655 in one launch: grid_vol [S, S, S] -> F.interpolate(., [R] * 3, mode='trilinear') -> nan_to_num(., 0) -> > thresh, as f32 [R, R, R]
+    of 0 / 1 (what mcubes.marching_cubes(occ, 0.5) reads).  return_values: (occ, the interpolated values f32 [R, R, R])."""
+    g = torch.as_tensor(grid_vol).to(_dev(), torch.float32).contiguous()
+    if g.dim() != 3 or len(set(g.shape)) != 1:
+        raise ValueError("occupancy_volume: a cubic grid_vol expected, got %s" % (tuple(g.shape),))
+    R = int(resolution)
+    if R < 1 or R > 1024:
+        raise ValueError("occupancy_volume: resolution %d is not in [1, 1024]" % R)
+    occ = torch.empty((R, R, R), dtype=torch.float32, device=g.device)
+    val = torch.empty_like(occ) if return_values else None
+    check(lib().mirres_mc_occupancy_trilinear(ptr(g), int(g.shape[0]), R, float(thresh), ptr(occ), ptr(val), stream_ptr()), "mirres_mc_occupancy_trilinear")
+    return (occ, val) if return_values else occ
+
+
+def _box6(box):
+    b = [float(x) for x in np.asarray(box, np.float64).reshape(-1)]
+    if len(b) != 6 or any(x != x for x in b):
+        raise ValueError("a box is (xmn, ymn, zmn, xmx, ymx, zmx) without NaN, got %r" % (box,))
+    return b
+
+
+def remove_selected_verts(vertices, triangles, box, where="inside", log=None):
+    """meshutils.py:159-181 with the two queries export_stage0 builds: box = (xmn, ymn, zmn, xmx, ymx, zmx); where = "inside" deletes every vertex with
+    x <= xmx && x >= xmn && ... (the closed box, renderer.py:663), "outside" every vertex with x <= xmn || x >= xmx || ... (:676).  A face goes when it touches a
+    deleted vertex; so do the vertices no face uses any more; order is kept."""
+    if where not in ("inside", "outside"):
+        raise ValueError("remove_selected_verts: where is 'inside' or 'outside', got %r" % (where,))
+    b = _box6(box)
+    v, t = _verts(vertices), _tris(triangles)
+    V, T = int(v.shape[0]), int(t.shape[0])
+    keep = torch.empty(T, dtype=torch.uint8, device=v.device)
+    check(lib().mirres_mesh_select_box(ptr(v) if V else None, V, ptr(t) if T else None, T, (C.c_double * 6)(*b), 1 if where == "outside" else 0, ptr(keep) if T else None,
+                                       stream_ptr()), "mirres_mesh_select_box")
+    ov, ot = compact_mesh(v, t, keep)
+    if log:
+        log("[INFO] mesh remove verts: %s --> %s, %s --> %s" % (tuple(v.shape), tuple(ov.shape), tuple(t.shape), tuple(ot.shape)))
+    return ov, ot
+
+
+OUTER_CENTRE = 0.45                          # renderer.py:662: the part of an outer cascade's cube the cascades before it cover
+
+
+def outer_shell(grid_vol, cas, bound, env_reso, thresh, aabb, log=None):
+    """One outer cascade of export_stage0 (nerf/renderer.py:642-676) up to, not including, cleaning: grid_vol [S, S, S] is cascade `cas` (>= 1) of the density
+    grid; occupancy at env_reso^3 (occupancy_volume), marching cubes at 0.5, vertices to [-1, 1], the closed centre box of +-0.45 removed, vertices scaled by
+    bound_cas - half (bound_cas = min(2^cas, bound), half = bound_cas / env_reso), everything not strictly inside aabb (6 values, aabb_train) shrunk by half
+    removed -> (vertices f32 [V, 3] in world space, triangles i32 [T, 3]); V = T = 0 when nothing is left."""
+    cas, R = int(cas), int(env_reso)
+    if cas < 1:
+        raise ValueError("outer_shell: cascade %d is not an outer one" % cas)
+    if R < 2 or R > 1024:
+        raise ValueError("outer_shell: env_reso %d is not in [2, 1024]" % R)
+    a = _box6(aabb)
+    bound_cas = min(2.0 ** cas, float(bound)); half = bound_cas / R
+    occ = occupancy_volume(grid_vol, R, thresh)
+    v, t = marching_cubes(occ, 0.5)
+    if log:
+        log("[INFO] cascade %d: marching cubes at %s of the occupancy > %g: %d vertices, %d triangles" % (cas, "x".join([str(R)] * 3), thresh, v.shape[0], t.shape[0]))
+    v = index_to_world(v, R)
+    r = OUTER_CENTRE
+    v, t = remove_selected_verts(v, t, (-r, -r, -r, r, r, r), "inside", log=log)
+    if v.shape[0] == 0:
+        return v, t
+    v = (v * float(bound_cas - half)).to(torch.float32)
+    return remove_selected_verts(v, t, [a[0] + half, a[1] + half, a[2] + half, a[3] - half, a[4] - half, a[5] - half], "outside", log=log)
 
 
 @torch.no_grad()
@@ -241,6 +315,7 @@ def clean_mesh(vertices, triangles, min_f=8, min_d=5, max_rounds=0, log=None):
 
 DEC_MAX_ROUNDS = 4096                        # decimate_mesh's cap on rounds (max_rounds = 0)
 DEC_KEY_NONE = 0x7FFFFFFFFFFFFFFF            # the key of an edge that may not be collapsed
+DEC_KEY_UNSCRAMBLE = pow(0x9E3779B1, -1, 1 << 32)      # endpoints_only: the inverse of the multiplier that scrambles the edge id in a key
 DEC_FLAGS = {"multiplicity": 1, "link": 2, "boundary": 4, "flip": 8, "finite": 16}      # bits of decimate_round's per-edge flags (include/mirres.h)
 
 
@@ -257,12 +332,13 @@ def _dec_topology(t, V):
                 E=int(ekeys.shape[0]))
 
 
-def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True, mark=None):
+def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True, mark=None, endpoints_only=False):
     """One round of decimate_mesh on device tensors whose indices are in range (vertices f32 [V, 3], quadrics f64 [V, 10] or None before the first round, triangles
     i32 [T, 3], T > target) -> (vertices, quadrics, triangles, info); the inputs are left as they are.  info: the round's edge list and CSR (`ekeys`, `emult`,
     `corner_edge`, `vcorner`, `vstart`, `E`), `vflag`, the quadrics the round started from (`quadrics`), per edge `cost` f64, `position` f32 [E, 3], `flags` i32
     (DEC_FLAGS; 0 = valid) and `keys` i64, the candidates `cand` (edge ids, cheapest first), `sel` u8 per candidate, and `selected`, their number (0: nothing could
-    be collapsed, the mesh comes back as it was).  `mark(name)` is called after each stage ("edges", "k_dec_edge", "select", "apply") for timing."""
+    be collapsed, the mesh comes back as it was).  `mark(name)` is called after each stage ("edges", "k_dec_edge", "select", "apply") for timing.
+    endpoints_only (without optimalplacement): the midpoint is no candidate, the edge collapses onto the cheaper of its two end points."""
     L = lib(); s = stream_ptr
     mark = mark or (lambda name: None)
     v, t = vertices.clone(), triangles.clone()
@@ -279,7 +355,7 @@ def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True,
     mark("edges")
     cost = torch.empty(E, dtype=torch.float64, device=dev); pos = torch.empty((E, 3), dtype=torch.float32, device=dev)
     flags = torch.empty(E, dtype=torch.int32, device=dev); keys = torch.empty(E, dtype=torch.int64, device=dev)
-    check(L.mirres_dec_edge(ptr(v), ptr(q), V, ptr(t), T, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["ekeys"]), ptr(tp["emult"]), ptr(vflag), E, 1 if optimalplacement else 0,
+    check(L.mirres_dec_edge(ptr(v), ptr(q), V, ptr(t), T, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["ekeys"]), ptr(tp["emult"]), ptr(vflag), E, 1 if optimalplacement else (2 if endpoints_only else 0),
                             ptr(cost), ptr(pos), ptr(flags), ptr(keys), s()), "mirres_dec_edge")
     mark("k_dec_edge")
     skeys = torch.sort(keys).values
@@ -287,7 +363,10 @@ def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True,
     info = dict(tp, vflag=vflag, quadrics=q0, cost=cost, position=pos, flags=flags, keys=keys, cand=skeys[:0].to(torch.int32), sel=torch.empty(0, dtype=torch.uint8, device=dev), selected=0)
     if n_cand <= 0:
         return v, q, t, info
-    cand = (skeys[:n_cand] & 0xFFFFFFFF).to(torch.int32).contiguous()
+    cand = skeys[:n_cand] & 0xFFFFFFFF
+    if endpoints_only and not optimalplacement:
+        cand = (cand * DEC_KEY_UNSCRAMBLE) & 0xFFFFFFFF                                 # the key's low word is the edge id times 0x9E3779B1 mod 2^32 in this mode
+    cand = cand.to(torch.int32).contiguous()
     vkey = torch.empty(V, dtype=torch.int64, device=dev); sel = torch.empty(n_cand, dtype=torch.uint8, device=dev); cnt = torch.empty(1, dtype=torch.int32, device=dev)
     check(L.mirres_dec_select(ptr(t), T, V, ptr(tp["vstart"]), ptr(tp["vcorner"]), ptr(tp["ekeys"]), E, ptr(keys), ptr(cand), n_cand, ptr(vkey), ptr(sel), ptr(cnt), s()), "mirres_dec_select")
     mark("select")
@@ -306,11 +385,12 @@ def decimate_round(vertices, quadrics, triangles, target, optimalplacement=True,
     return ov[: counts[0]].contiguous(), q, ot[: counts[1]].contiguous(), info
 
 
-def decimate_mesh(vertices, triangles, target, optimalplacement=True, max_rounds=0, log=None):
+def decimate_mesh(vertices, triangles, target, optimalplacement=True, max_rounds=0, log=None, endpoints_only=False):
     """decimate_mesh (meshutils.py:64-97; nerf/renderer.py:566-567) -> (vertices f32 [V', 3], triangles i32 [T', 3]) with target - 1 <= T' <= target: quadric-error
     edge collapse (Garland & Heckbert 1997) in rounds, every round collapsing an independent set of the cheapest valid edges (decimate_round; csrc/decimate.hip,
     DESIGN.md section 5.10).  Surviving vertices and faces keep their order; equal inputs give equal bytes.  `optimalplacement`: the new vertex minimises the summed
-    quadric where the system can be solved, else (and always without it) it is the cheapest of the two end points and their midpoint.  target >= T (or T == 0)
+    quadric where the system can be solved, else (and always without it) it is the cheapest of the two end points and their midpoint; `endpoints_only` (without
+    optimalplacement) leaves the midpoint out, as MeshLab does with optimalplacement off: the result's vertices are a subset of the input's.  target >= T (or T == 0)
     returns the input.  A round without a valid edge (stall) or `max_rounds` rounds (0: DEC_MAX_ROUNDS) end the run early with one [WARN] line."""
     v, t = _verts(vertices), _tris(triangles)
     V, T0 = int(v.shape[0]), int(t.shape[0]); target = int(target)
@@ -329,7 +409,7 @@ def decimate_mesh(vertices, triangles, target, optimalplacement=True, max_rounds
     while ot.shape[0] > target:
         if rounds >= cap:
             why = "%d rounds done (max_rounds)" % rounds; break
-        ov, q, ot, info = decimate_round(ov, q, ot, target, optimalplacement)
+        ov, q, ot, info = decimate_round(ov, q, ot, target, optimalplacement, endpoints_only=endpoints_only)
         if info["selected"] == 0:
             why = "no edge can be collapsed after %d rounds (stall)" % rounds; break
         rounds += 1
@@ -462,14 +542,37 @@ class DensityField:
         return out
 
 
-def synthetic_checkpoint(S=16, radius=0.6):
+def _synthetic_outer_row(S, k, c, A):
+    """Row k >= 1 of synthetic_checkpoint's density_grid in [x][y][z] order: the scene at the centres of cascade k's cells (world = normalised * 2^k)."""
+    cc = (np.arange(S, dtype=np.float64) + 0.5) / S * 2.0 - 1.0
+    x, y, z = (w * 2.0 ** k for w in np.meshgrid(cc, cc, cc, indexing="ij"))
+    r = np.sqrt(x * x + y * y + z * z)
+    row = np.exp(c * (A - r))                                                   # the ball
+    solid = np.zeros(row.shape, bool)
+    for j in range(1, k + 1):                                                   # cascade j's slab and dome, at its own scale
+        u = 2.0 ** j
+        solid |= (z > -0.85 * u) & (z < -0.6 * u) & (np.abs(x) < 0.85 * u) & (np.abs(y) < 0.85 * u)
+        solid |= (r > 0.7 * u) & (r < 0.9 * u) & (z > 0.25 * u)
+    row[solid] = np.exp(c * A)
+    row[(x > 0.9 * 2.0 ** k) & (y > 0.9 * 2.0 ** k)] = -1.0                     # a column of cells no training step has updated (torch-ngp marks them -1)
+    return row.astype(np.float32)
+
+
+def synthetic_checkpoint(S=16, radius=0.6, cascades=1):
     """A stage-0 checkpoint dict (bound 1, the reference's hash-grid configuration) whose network encodes a ball, for tests and smoke runs: feature 0 of level 0
     holds 2 - |x| at the level's vertices (vertex i of an axis sits at u = (i - 0.5) / 15), every other table entry is 0, W0[0, 0] = c = 1.5, W1[0, 0] = 1 and all
     other weights are 0, so sigma = exp(1.5 * trilinear(2 - |x|)): it falls with the radius everywhere in the cube and passes mean_density = exp(1.5 * (2 - radius))
     (8.17 at the default, below the default density_thresh) at |x| = radius up to level 0's interpolation error (< 0.01).  density_grid [1, S^3] (Morton order)
     holds, per cell, the density a full cell diagonal nearer to the centre than the cell's own centre: an upper bound over the cell and its neighbours, as a trained
-    grid's running maximum is, so masking by it removes nothing the iso level would keep."""
+    grid's running maximum is, so masking by it removes nothing the iso level would keep.
+    cascades = 2 or 3 (bound 2 or 4) adds `aabb_train` (+-bound) and rows 1 ... of density_grid: row k is cascade k's view of one scene in its normalised coordinates
+    (world / 2^k), sampled at the cell centres — the ball (inside the 0.45 box of every outer cascade, so no outer mesh may show it), per cascade j <= k a ground slab
+    (-0.85 < z / 2^j < -0.6, |x|, |y| < 0.85 * 2^j) and a dome (0.7 < |p| / 2^j < 0.9, z > 0.25 * 2^j) at exp(c * A), which lie between 0.55 and 0.9 of cascade j's
+    cube and inside the 0.45 box of the cascades after it, and a corner column of untrained cells (-1).  The network still describes the ball in [-1, 1]^3 only."""
     S = int(S); c, A = 1.5, 2.0
+    cascades = int(cascades)
+    if cascades < 1 or cascades > 3:
+        raise ValueError("synthetic_checkpoint: %d cascades (1, 2 or 3)" % cascades)
     net, total = density_layout(1.0)
     table = torch.zeros((total, 2), dtype=torch.float32)
     s1 = int(net.resolution[0]) + 1
@@ -486,13 +589,93 @@ def synthetic_checkpoint(S=16, radius=0.6):
     grid = np.zeros(S ** 3, np.float32)
     grid[morton_indices(S).reshape(-1)] = np.exp(c * (A - r)).reshape(-1).astype(np.float32)
     offsets = torch.tensor([int(net.offsets[k]) for k in range(net.num_levels + 1)], dtype=torch.int32)
-    return {"mean_density": float(np.exp(c * (A - float(radius)))),
-            "model": {"encoder.embeddings": table, "encoder.offsets": offsets, "sigma_net.0.weight": w0, "sigma_net.1.weight": w1,
-                      "density_grid": torch.from_numpy(grid)[None]}}
+    ck = {"mean_density": float(np.exp(c * (A - float(radius)))),
+          "model": {"encoder.embeddings": table, "encoder.offsets": offsets, "sigma_net.0.weight": w0, "sigma_net.1.weight": w1,
+                    "density_grid": torch.from_numpy(grid)[None]}}
+    if cascades > 1:
+        rows = [grid]
+        for k in range(1, cascades):
+            row = np.zeros(S ** 3, np.float32)
+            row[morton_indices(S).reshape(-1)] = _synthetic_outer_row(S, k, c, A).reshape(-1)
+            rows.append(row)
+        b = float(2 ** (cascades - 1))
+        ck["model"]["density_grid"] = torch.from_numpy(np.stack(rows, 0))
+        ck["model"]["aabb_train"] = torch.tensor([-b, -b, -b, b, b, b], dtype=torch.float32)
+    return ck
+
+
+def _outer_plan(save_path, ckpt, bound, env_reso, sdf, overwrite):
+    """What export_outer_meshes checks before it touches the device -> (density_grid, aabb as 6 floats, the paths of mesh_1.ply ...)."""
+    from . import checkpoint as CK
+    if ckpt is None:
+        raise ValueError("the outer meshes come from a checkpoint's density_grid: no ckpt given")
+    if sdf:
+        raise NotImplementedError("the --sdf outer mesh (contracted background, nerf/renderer.py:575-629) is not built")
+    if not (float(bound) > 0 and np.isfinite(float(bound))):
+        raise ValueError("bound %r" % (bound,))
+    if int(env_reso) < 2 or int(env_reso) > 1024:
+        raise ValueError("env_reso %d is not in [2, 1024]" % int(env_reso))
+    model = ckpt["model"] if "model" in ckpt else ckpt
+    if "mean_density" not in ckpt:
+        raise KeyError("checkpoint has no top-level mean_density")
+    grid = torch.as_tensor(model["density_grid"])
+    rows = int(grid.shape[0]) if grid.dim() == 2 else 1
+    want = CK.cascade_of_bound(float(bound))
+    if rows != want:
+        raise ValueError("the checkpoint's density_grid has %d cascades, --bound %g has %d: pass the --bound the checkpoint was trained with" % (rows, float(bound), want))
+    if "aabb_train" in model:
+        aabb = _box6(torch.as_tensor(model["aabb_train"]).detach().cpu().numpy())
+    else:
+        aabb = [-float(bound)] * 3 + [float(bound)] * 3
+    paths = [os.path.join(save_path, "mesh_%d.ply" % cas) for cas in range(1, rows)]
+    for f in paths:
+        if os.path.exists(f) and not overwrite:
+            raise FileExistsError("%s exists (pass overwrite to replace it)" % f)
+    return grid, aabb, paths
+
+
+def export_outer_meshes(save_path, ckpt, bound, env_reso=256, density_thresh=10.0, cameras=None, dilation=5, min_f=8, min_d=5, decimate_target=3e5, overwrite=False,
+                        log=print, sdf=False):
+    """The non-SDF outer meshes of NeRFRenderer.export_stage0 (nerf/renderer.py:632-698) -> the list of written paths, `mesh_{cas}.ply` for cas = 1 ... .
+    ckpt: a stage-0 checkpoint whose density_grid has exactly checkpoint.cascade_of_bound(bound) rows; model["aabb_train"] when present, else +-bound, bounds the
+    meshes.  Per cascade: outer_shell at env_reso with thresh = min(mean_density, density_thresh), clean_mesh(min_f, min_d), decimate_mesh to HALF of decimate_target
+    (:635) with every edge collapsed onto one of its end points (optimalplacement=False as MeshLab reads it, :685: the vertices stay a subset of the shell's), and only
+    then the visibility cull (cameras = (mvps, H, W), :692-694).
+    A cascade whose mesh is empty after the centre is removed (:664), after cleaning (:681) or after the cull is skipped with one log line: no file is written.
+    The cull casts rays through the BVH, whose box test passes no ray through a box of zero thickness: faces that lie exactly in an axis-aligned plane, of which the
+    mesh of a 0 / 1 volume has many, count as unseen and stay only within `dilation` rings of a seen face.
+    sdf = True is refused (the contracted outer mesh, :575-629, is not built)."""
+    from . import checkpoint as CK
+    grid, aabb, paths = _outer_plan(save_path, ckpt, bound, env_reso, sdf, overwrite)
+    thresh = select_iso(ckpt["mean_density"], density_thresh)
+    target = decimate_target // 2                                                 # :635, once: the inner mesh has been written with the full target
+    written = []
+    for cas, out in zip(range(1, len(paths) + 1), paths):
+        v, t = outer_shell(unpack_density_grid(grid, cas), cas, bound, env_reso, thresh, aabb, log=log)
+        if v.shape[0]:
+            v, t = clean_mesh(v, t, min_f=min_f, min_d=min_d, log=log)
+        if v.shape[0] == 0 or t.shape[0] == 0:
+            log("[INFO] cascade %d: nothing outside the centre box is left, %s is not written" % (cas, os.path.basename(out)))
+            continue
+        if target > 0 and t.shape[0] > target:
+            v, t = decimate_mesh(v, t, int(target), optimalplacement=False, endpoints_only=True, log=log)
+        log("[INFO] exporting outer mesh at cas %d, v = %s, f = %s" % (cas, tuple(v.shape), tuple(t.shape)))
+        if cameras is not None:
+            mvps, H, W = cameras
+            unseen = mark_unseen_triangles(v, t, mvps, H, W, log=log)
+            v, t = remove_masked_trigs(v, t, unseen, dilation=dilation, log=log)
+            if t.shape[0] == 0:
+                log("[INFO] cascade %d: no camera sees the mesh, %s is not written" % (cas, os.path.basename(out)))
+                continue
+        os.makedirs(save_path, exist_ok=True)
+        CK.write_ply(out, v.cpu().numpy(), t.cpu().numpy())
+        log("[INFO] wrote %s: %d vertices, %d triangles" % (out, v.shape[0], t.shape[0]))
+        written.append(out)
+    return written
 
 
 def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, density_thresh=10.0, mesh=None, cameras=None, dilation=5, min_f=8, min_d=5,
-                  decimate_target=3e5, optimalplacement=True, overwrite=False, log=print, resolution=None, bound=1.0):
+                  decimate_target=3e5, optimalplacement=True, overwrite=False, log=print, resolution=None, bound=1.0, outer=False, env_reso=256):
     """NeRFRenderer.export_stage0 (nerf/renderer.py:498-570) -> path of the written mesh_0.ply.
     Exactly one geometry source, or a volume together with the checkpoint that masks it:
       ckpt    a stage-0 checkpoint dict (top-level `mean_density`, `model` -> `density_grid` [cascade, S^3]): cascade 0 at the grid's own resolution (:511-515),
@@ -502,8 +685,14 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
               :532-539) or, with sdf, a signed distance extracted as (-volume, 0) (:549);
       mesh    (vertices, triangles) of a foreign mesh in world space: cull, clean and decimate only.
     Above decimate_target (> 0) triangles the cleaned mesh is decimated to it (:566-567, decimate_mesh).
-    cameras = (mvps [B, 4, 4], H, W) switches the visibility cull on (:557-560)."""
+    cameras = (mvps [B, 4, 4], H, W) switches the visibility cull on (:557-560).
+    outer (needs ckpt, excludes sdf): after mesh_0.ply the outer cascades' meshes mesh_1.ply ... of a checkpoint trained with `bound` > 1 are written from its density
+    grid at env_reso (export_outer_meshes, :632-698); a checkpoint of one cascade has none.  Its arguments are checked before anything is written."""
     from . import checkpoint as CK
+    if outer:
+        if ckpt is None:
+            raise ValueError("export_stage0: outer needs a checkpoint (the outer meshes come from its density_grid)")
+        _outer_plan(save_path, ckpt, bound, env_reso, sdf, overwrite)
     if mesh is not None and (ckpt is not None or volume is not None):
         raise ValueError("export_stage0: a mesh excludes a checkpoint and a volume")
     if mesh is None and ckpt is None and volume is None:
@@ -523,7 +712,8 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
             model = ckpt["model"] if "model" in ckpt else ckpt
             grid = torch.as_tensor(model["density_grid"])
             if grid.dim() == 2 and grid.shape[0] > 1:
-                log("[INFO] checkpoint has %d cascades: exporting cascade 0 only, the outer meshes (bound > 1) are not built" % grid.shape[0])
+                log("[INFO] checkpoint has %d cascades: %s" % (grid.shape[0], "cascade 0 first, the outer meshes follow" if outer else
+                                                                 "exporting cascade 0 only, outer=True (--outer_meshes) writes the outer meshes (bound > 1)"))
             grid_vol = unpack_density_grid(grid, 0)
             if not sdf:
                 if "mean_density" not in ckpt:
@@ -558,4 +748,7 @@ def export_stage0(save_path, ckpt=None, volume=None, iso=None, sdf=False, densit
     os.makedirs(save_path, exist_ok=True)
     CK.write_ply(out, v.cpu().numpy(), t.cpu().numpy())
     log("[INFO] wrote %s: %d vertices, %d triangles" % (out, v.shape[0], t.shape[0]))
+    if outer:
+        export_outer_meshes(save_path, ckpt, bound, env_reso=env_reso, density_thresh=density_thresh, cameras=cameras, dilation=dilation, min_f=min_f, min_d=min_d,
+                            decimate_target=decimate_target, overwrite=overwrite, log=log)
     return out

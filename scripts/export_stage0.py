@@ -7,6 +7,8 @@ file train_stage1.py, evaluate.py, export_stage1.py and albedo_eval.py start fro
     python scripts/export_stage0.py --workspace <ws> --mesh foreign.ply --transforms <data>/transforms_train.json                  # cull, clean and decimate only
     python scripts/export_stage0.py --synthetic [--workspace <ws>]                                                                 # analytic volume, smoke run
     python scripts/export_stage0.py --synthetic --network [--mcubes_reso 48]                                                       # a synthetic checkpoint's network, end to end
+    python scripts/export_stage0.py --workspace <ws> --bound 2 --outer_meshes [--env_reso 256]                                     # + mesh_1.ply ...: the outer cascades of bound > 1
+    python scripts/export_stage0.py --synthetic --bound 2 --outer_meshes                                                           # a synthetic 2-cascade checkpoint's grid, smoke run
 
 Exactly one geometry source.  The checkpoint (default: the latest stage-0 checkpoint of the workspace): its density grid, or with `--mcubes_reso R` (the
 reference's flag, 512 in its main.py; unset: the grid) its density network evaluated on the R^3 lattice of [-1, 1]^3 on the HIP path (stage0.DensityField: torch-ngp
@@ -18,7 +20,11 @@ otherwise at `--iso` / `--density_thresh`; `--sdf`: a signed distance, extracted
 --offset as in evaluate.py) gives the training cameras of the visibility cull (--mesh_visibility_culling, which -O switches on); without it nothing is culled.
 Above `--decimate_target` triangles (default 3e5 as in the reference's main.py; 0 switches it off) the cleaned mesh is decimated to it by quadric edge collapse
 (stage0.decimate_mesh: deterministic rounds of independent collapses, the result has the target's face count or one less; `--no_optimal_placement` places a
-collapsed vertex at the cheapest of the two end points and their midpoint instead of the quadric's minimum).  This holds for `--mesh` as well."""
+collapsed vertex at the cheapest of the two end points and their midpoint instead of the quadric's minimum).  This holds for `--mesh` as well.
+`--outer_meshes` (a checkpoint trained with `--bound` > 1, whose density grid has 1 + ceil(log2(bound)) cascades): after mesh_0.ply the reference's outer meshes
+mesh_1.ply ... (nerf/renderer.py:632-698) are written, one per outer cascade, from the cascade's density grid resampled to `--env_reso`^3 (the reference's flag,
+256), without the centre the cascades before it cover, decimated to half of --decimate_target and culled after decimation; a cascade with nothing left is skipped.
+It conflicts with --sdf (the contracted outer mesh is not built), --volume and --mesh.  evaluate.py / train_stage1.py read the result with --cascade."""
 import argparse, glob, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,6 +44,8 @@ def build_parser():
     p.add_argument("--mcubes_reso", type=int, default=None, help="evaluate the checkpoint's density network on this lattice (the reference's flag; unset: the density grid)")
     p.add_argument("--bound", type=float, default=1.0, help="the --bound the checkpoint was trained with (fixes the hash-grid layout)")
     p.add_argument("--network", action="store_true", help="--synthetic: a synthetic checkpoint's density network instead of the analytic volume")
+    p.add_argument("--outer_meshes", action="store_true", help="also write mesh_1.ply ... for the outer cascades of a checkpoint trained with --bound > 1")
+    p.add_argument("--env_reso", type=int, default=256, help="--outer_meshes: the resolution an outer cascade's grid is resampled to (the reference's flag)")
     return p
 
 
@@ -61,6 +69,15 @@ def parse_args(argv=None):
         p.error("--network belongs to --synthetic")
     if not (a.bound > 0):
         p.error("--bound %g: a positive number" % a.bound)
+    if a.outer_meshes:
+        if a.mesh or a.volume or a.sdf:
+            p.error("--outer_meshes reads the checkpoint's density grid: it conflicts with --mesh, --volume and --sdf (the contracted outer mesh is not built)")
+        if a.synthetic and a.network:
+            p.error("--outer_meshes with --synthetic uses the synthetic checkpoint's grid: drop --network (its hash grid is laid out for bound 1)")
+        if not (2 <= a.env_reso <= 1024):
+            p.error("--env_reso %d: between 2 and 1024" % a.env_reso)
+        if a.synthetic and a.bound > 4:
+            p.error("--synthetic --outer_meshes: --bound at most 4 (three cascades)")
     if a.synthetic:
         if a.mesh or a.volume or a.ckpt:
             p.error("--synthetic is a geometry source of its own: drop --mesh / --volume / --ckpt")
@@ -85,6 +102,10 @@ def parse_args(argv=None):
     a.out = a.out or os.path.join(a.workspace, "mesh_stage0")
     if os.path.exists(os.path.join(a.out, "mesh_0.ply")) and not a.overwrite:
         p.error("%s exists: pass --overwrite to replace it" % os.path.join(a.out, "mesh_0.ply"))
+    if a.outer_meshes and not a.overwrite:
+        old = sorted(f for f in glob.glob(os.path.join(a.out, "mesh_[1-9].ply")))
+        if old:
+            p.error("%s exists: pass --overwrite to replace it" % old[0])
     return a
 
 
@@ -109,7 +130,11 @@ def main(argv=None):
     log = lambda m: print(m, flush=True)
     kw = dict(density_thresh=a.density_thresh, iso=a.iso, sdf=a.sdf, dilation=a.visibility_mask_dilation, min_f=a.clean_min_f, min_d=a.clean_min_d,
               decimate_target=a.decimate_target, optimalplacement=not a.no_optimal_placement, overwrite=a.overwrite, log=log)
-    if a.synthetic and a.network:
+    if a.outer_meshes:
+        kw.update(outer=True, env_reso=a.env_reso, bound=a.bound)
+    if a.synthetic and a.outer_meshes:
+        kw["ckpt"] = stage0.synthetic_checkpoint(cascades=CK.cascade_of_bound(a.bound))
+    elif a.synthetic and a.network:
         kw["ckpt"] = stage0.synthetic_checkpoint(); kw["resolution"] = a.mcubes_reso if a.mcubes_reso is not None else 48
     elif a.synthetic:
         kw["volume"] = stage0.synthetic_volume(a.resolution, sdf=a.sdf)
