@@ -394,8 +394,11 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
 // whose OWN box passes the slab test of "triangle_hit accepts": a leaf's ancestors always pass when the leaf does (their boxes are
 // fmin/fmax unions and (b - o) * inv is monotone in b under IEEE rounding), hence (2) any visiting order and any pruning by ancestor
 // boxes yields the same boolean. The stack holds bare 4-byte references in LDS (16 per lane, scratch beyond); no pop-time re-test is needed.
+#ifndef MR_ANY_POOL
+#define MR_ANY_POOL 1      // the per-wave pool of prepared rays (below); 0: the refill of rounds 2-6 (idle lanes form their own rays), threshold MR_REFILL
+#endif
 #ifndef MR_ANY_LDS
-#define MR_ANY_LDS 16
+#define MR_ANY_LDS (MR_ANY_POOL ? 12 : 16)      // the pool's LDS comes out of the stack's: 12 rows were within 0.5 % of 16 before the pool (profiles/r04_ab_any_lds_stack.txt)
 #endif
 // Depth of the shadow-ray kernel's private stack (LDS part + scratch). A 4-wide node defers at most three references and the 4-wide collapse is never
 // deeper than the LBVH it was collapsed from, whose depth is bounded by the bits of the augmented sort key: 30 Morton bits + ceil(log2 T) position bits
@@ -501,6 +504,82 @@ MR_DEV v3 oct_decode_lean(v2 f) {     // oct_decode (device_math.hpp, helperDi.s
     n.y += (n.y >= 0.0f ? -t : t);
     return normalize_lean(n);
 }
+// ---------------------------------------------------------------- the per-wave pool of prepared rays (MR_ANY_POOL)
+// The old refill formed a ray — two dependent gathers for a pixel pair, the normalisation, three reciprocals, the root slab: 145 VALU instructions — in the idle
+// lanes only, 25-30 of 64, about once per five iterations; being that dear it kept the threshold at 40 busy lanes. With the pool ALL 64 lanes, busy ones included
+// (their traversal state stays in registers), each set up one ray of the wave's chunk at full width; the rays that are alive and pass the root box are compacted
+// (ballot + prefix popcount) into an LDS array private to the wave, and an idle lane picks the next entry up with ten LDS reads. Dead rays and root misses never
+// occupy a lane. The arithmetic per ray is the old refill's, expression for expression; only where it runs and which lane walks which ray change.
+// Layout: structure of arrays, pool[field * 64 + entry] — entries are written by consecutive ranks and read by consecutive ranks: no bank conflicts.
+// (MR_ANY_POOL itself is defined above MR_ANY_LDS, whose default depends on it.)
+#ifndef MR_ANY_REFILL
+#define MR_ANY_REFILL (MR_ANY_POOL ? 48 : MR_REFILL)      // the shadow-ray kernel picks rays up while fewer than this many lanes are busy
+#endif
+struct PreparedRay { float ox, oy, oz, dx, dy, dz, ix, iy, iz, t_min, t_max; uint32_t idx; };
+// INTERVAL: the entry carries the ray's own [t_min, t_max] (plain ray queues); the pixel-pair source's interval is a constant
+template <bool INTERVAL> MR_DEV constexpr int pool_dwords() { return INTERVAL ? 12 : 10; }
+template <bool INTERVAL>
+MR_DEV void pool_put(uint32_t* __restrict__ pool, int e, const PreparedRay& r) {
+    pool[0 * 64 + e] = r.idx;
+    pool[1 * 64 + e] = __float_as_uint(r.ox); pool[2 * 64 + e] = __float_as_uint(r.oy); pool[3 * 64 + e] = __float_as_uint(r.oz);
+    pool[4 * 64 + e] = __float_as_uint(r.dx); pool[5 * 64 + e] = __float_as_uint(r.dy); pool[6 * 64 + e] = __float_as_uint(r.dz);
+    pool[7 * 64 + e] = __float_as_uint(r.ix); pool[8 * 64 + e] = __float_as_uint(r.iy); pool[9 * 64 + e] = __float_as_uint(r.iz);
+    if (INTERVAL) { pool[10 * 64 + e] = __float_as_uint(r.t_min); pool[11 * 64 + e] = __float_as_uint(r.t_max); }
+}
+template <bool INTERVAL>
+MR_DEV PreparedRay pool_get(const uint32_t* __restrict__ pool, int e, float t_min_const, float t_max_const) {
+    PreparedRay r;
+    r.idx = pool[0 * 64 + e];
+    r.ox = __uint_as_float(pool[1 * 64 + e]); r.oy = __uint_as_float(pool[2 * 64 + e]); r.oz = __uint_as_float(pool[3 * 64 + e]);
+    r.dx = __uint_as_float(pool[4 * 64 + e]); r.dy = __uint_as_float(pool[5 * 64 + e]); r.dz = __uint_as_float(pool[6 * 64 + e]);
+    r.ix = __uint_as_float(pool[7 * 64 + e]); r.iy = __uint_as_float(pool[8 * 64 + e]); r.iz = __uint_as_float(pool[9 * 64 + e]);
+    r.t_min = INTERVAL ? __uint_as_float(pool[10 * 64 + e]) : t_min_const; r.t_max = INTERVAL ? __uint_as_float(pool[11 * 64 + e]) : t_max_const;
+    return r;
+}
+// how many bits of a wave-uniform mask lie below this lane: v_mbcnt, no per-lane 64-bit mask to keep in registers
+MR_DEV int rank_below(uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+// All lanes of a wave: compact the rays flagged `live` into the (empty) pool, in lane order. Returns the number of entries.
+template <bool INTERVAL>
+MR_DEV int pool_fill(uint32_t* __restrict__ pool, bool live, const PreparedRay& r) {
+    const uint64_t lv = __ballot(live);
+    if (live) pool_put<INTERVAL>(pool, rank_below(lv), r);
+    __builtin_amdgcn_wave_barrier();     // the entries are read by other lanes of this wave: keep the stores ahead of the reads (LDS serves a wave in order)
+    return __popcll(lv);
+}
+// Ray `idx` of a shadow-ray queue, set up exactly as the refill of rounds 2-6 did it (SRC, MR_ANY_LEANREFILL: see k_trace_any4q). False: the ray is dead.
+template <int SRC>
+MR_DEV bool prepare_any_ray(const Ray* __restrict__ rays, const RaySrc& src, uint32_t idx, PreparedRay& r) {
+    float4 a, b; bool dead = false;
+    if (SRC == 1) {
+        const uint2 it = reinterpret_cast<const uint2*>(rays)[idx >> 1];      // pair (a, b): even ray a -> b's light, odd ray b -> a's light
+        const uint32_t op = (idx & 1u) ? it.y : it.x, lp = (idx & 1u) ? it.x : it.y;
+        const float4 P = src.grec[4 * (size_t)op + 3], L = src.rrec[2 * (size_t)lp];
+        dead = src.skip_dead && L.w == 0.f;   // engine.hpp RaySrc: the light sample's carried luminance is 0 — nobody can see this ray's answer
+#if MR_ANY_LEANREFILL
+        const v3 dir = oct_decode_lean(V2(L.y, L.z));
+#else
+        const v3 dir = oct_decode(V2(L.y, L.z));
+#endif
+        v3 o = V3(P.x, P.y, P.z) + src.vis_near * dir;          // put_ray (passes.hip): the same two expressions
+        a.x = o.x; a.y = o.y; a.z = o.z; a.w = 0.f; b.x = dir.x; b.y = dir.y; b.z = dir.z; b.w = 1e7f;
+    } else { a = reinterpret_cast<const float4*>(rays + idx)[0]; b = reinterpret_cast<const float4*>(rays + idx)[1]; }
+    r.idx = idx; r.ox = a.x; r.oy = a.y; r.oz = a.z; r.t_min = a.w; r.t_max = b.w;
+    v3 d;
+#if MR_ANY_LEANREFILL
+    if (SRC == 1) d = normalize_lean(V3(b.x, b.y, b.z)); else d = normalize(V3(b.x, b.y, b.z));
+#else
+    d = normalize(V3(b.x, b.y, b.z));
+#endif
+    r.dx = d.x; r.dy = d.y; r.dz = d.z;
+    float dx = d.x, dy = d.y, dz = d.z;
+    if (dx == 0.f) dx = 0.000001f; if (dy == 0.f) dy = 0.000001f; if (dz == 0.f) dz = 0.000001f;
+#if MR_ANY_LEANREFILL
+    if (SRC == 1) { r.ix = lean_rcp(dx); r.iy = lean_rcp(dy); r.iz = lean_rcp(dz); } else
+#endif
+    { r.ix = 1.0f / dx; r.iy = 1.0f / dy; r.iz = 1.0f / dz; }
+    return !dead;
+}
+
 template <bool FRONT = false>   // FRONT: a conventional occlusion query — the hit must lie in front of the origin (t > 0); the reference's bvh_hit does not look at t
 MR_DEV bool tri_accepts_regs(float4 a, float4 b, float4 c, v3 ro, v3 d) {
     const v3 v0 = V3(a.x, a.y, a.z), E1 = V3(a.w, b.x, b.y), E2 = V3(b.z, b.w, c.x);
@@ -528,6 +607,11 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                                                                unsigned long long* __restrict__ stats, RaySrc src = RaySrc{nullptr, nullptr, 0.f, 0}) {
     __shared__ uint32_t lds[(MR_ANY_LDS + (MR_ANY_SEL ? 1 : 0)) * MR_TRACE_BLOCK];   // MR_ANY_SEL: one spare row for the last unconditional store of the branch-free child selection
     __shared__ __attribute__((aligned(16))) uint4 s_top[TOPN > 0 ? TOPN * 4 : 1];
+#if MR_ANY_POOL
+    __shared__ uint32_t s_pool[pool_dwords<SRC == 0>() * MR_TRACE_BLOCK];
+    uint32_t* const pool = s_pool + (threadIdx.x >> 6) * (pool_dwords<SRC == 0>() * 64);   // private to the wave
+    int pool_head = 0, pool_n = 0;                                                          // wave-uniform: entries [pool_head, pool_head + pool_n) wait for a lane
+#endif
     if (TOPN > 0) {
         const uint4* src = reinterpret_cast<const uint4*>(TOPN > 85 ? B.top341q : B.top85q);
         for (int i = threadIdx.x; i < TOPN * 4; i += MR_TRACE_BLOCK) s_top[i] = src[i];
@@ -554,7 +638,29 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
     unsigned long long c_boxes = 0, c_nodes = 0, c_leaves = 0; int c_maxsp = 0;
     unsigned long long w_iters = 0, w_leaf_iters = 0, w_leaf_lanes = 0;      // COUNT: wave iterations, those that ran the leaf branch, leaf visits (wave-uniform; lane 0 reports)
     while (true) {
+#if MR_ANY_POOL
+        // The pool's bookkeeping and the queue state are the same in every lane, but they are carried round a loop that lanes also leave and re-enter under exec
+        // masks, and the compiler then keeps them in vector registers and turns every test of them into a vector compare and an exec-mask region.
+        // Reading them from the first lane puts them back into scalar registers.
+        pool_n = __builtin_amdgcn_readfirstlane(pool_n); pool_head = __builtin_amdgcn_readfirstlane(pool_head);
+        const uint64_t need0 = __ballot(!have);
+        if (need0 && pool_n > 0) {
+            // ---- pick-up: the idle lane of rank r takes entry pool_head + r; only the margins are recomputed
+            const int r = rank_below(need0);
+            if (!have && r < pool_n) {
+                const PreparedRay p = pool_get<SRC == 0>(pool, pool_head + r, 0.f, 1e7f);
+                ox = p.ox; oy = p.oy; oz = p.oz; ix = p.ix; iy = p.iy; iz = p.iz; d = V3(p.dx, p.dy, p.dz); ro = V3(p.ox, p.oy, p.oz);
+                t_min = p.t_min; t_max = p.t_max; ridx = p.idx;
+                rc = ray_margins(scene_bs, ox, oy, oz, ix, iy, iz);
+                cur = TOPN > 0 ? MR_TOPBIT : 0; sp = 0; sbase = 0; have = true;
+            }
+            const int want = __popcll(need0), took = want < pool_n ? want : pool_n;
+            pool_head += took; pool_n -= took;
+        }
+        const uint64_t need = __ballot(!have);      // lanes still idle: the pool is empty now
+#else
         const uint64_t need = __ballot(!have);
+#endif
         if (need && exhausted) {
             // ---- the tail of the launch: the queue is empty and the wave waits for its longest rays. A shadow ray's answer is an OR over subtrees, so
             // a lane with deferred entries hands its OLDEST one (the bottom of its stack: usually the largest subtree) to an idle lane, which searches
@@ -562,7 +668,11 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
             const uint64_t donors = __ballot(have && sp > sbase && sbase < MR_ANY_LDS);
             if (donors) {
                 const int nd = __popcll(donors), ni = __popcll(need);
+#if MR_ANY_POOL
+                const int my_idle = rank_below(need), my_don = rank_below(donors);
+#else
                 const int my_idle = __popcll(need & lt_mask), my_don = __popcll(donors & lt_mask);
+#endif
                 const bool take = !have && my_idle < nd;
                 const bool give = have && sp > sbase && sbase < MR_ANY_LDS && my_don < ni;
                 uint64_t m = donors;
@@ -585,7 +695,29 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
             }
         }
         if (need && !exhausted) {
+#if MR_ANY_POOL
+            chunk_next = __builtin_amdgcn_readfirstlane(chunk_next); chunk_end = __builtin_amdgcn_readfirstlane(chunk_end);
+#endif
             if (chunk_next >= chunk_end) exhausted = !grab_chunk(work_head, n, q_per, chunk, q_cur, q_fail, q_known, chunk_next, chunk_end, lane);
+#if MR_ANY_POOL
+            if (!exhausted) {
+                // ---- prepare: the pool is empty (the idle lanes have just drained it) and the chunk has rays left. Every lane, busy or not, sets up one ray
+                // (the lanes past the end of a sub-queue's last chunk repeat its last ray and drop it: no divergent region around the set-up, whose
+                // results the compiler would otherwise carry around the loop for the lanes that skipped it — twelve registers)
+                const bool valid = chunk_next + (uint32_t)lane < chunk_end;
+                const uint32_t idx = valid ? chunk_next + (uint32_t)lane : chunk_end - 1u;
+                PreparedRay p;
+                bool live = prepare_any_ray<SRC>(rays, src, idx, p);
+                if (valid) hit_out[idx] = 0;          // set to 1 by whichever lane finds an occluder (the owner or, in the tail, a helper)
+                const float o3[3] = {p.ox, p.oy, p.oz}, i3[3] = {p.ix, p.iy, p.iz};
+                const Slab s0 = slab(B.root_box, B.root_box + 3, o3, i3, p.t_min);
+                if (COUNT && valid) c_boxes++;
+                live = live && valid && s0.tf > s0.tn && p.t_max > s0.tn;
+                pool_head = 0; pool_n = pool_fill<SRC == 0>(pool, live, p);
+                chunk_next = (chunk_next + 64u < chunk_end) ? chunk_next + 64u : chunk_end;
+                continue;      // back to the pick-up (or, when none of the 64 was live, to the next 64)
+            }
+#else
             if (!exhausted) {
                 const uint32_t idx0 = chunk_next + (uint32_t)__popcll(need & lt_mask);
                 const uint32_t idx = idx0;
@@ -631,6 +763,7 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                 const uint32_t want = (uint32_t)__popcll(need);
                 chunk_next = (chunk_next + want < chunk_end) ? chunk_next + want : chunk_end;
             }
+#endif
         }
         if (!__ballot(have)) { if (exhausted) break; else continue; }
         do {
@@ -763,7 +896,7 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                 if (done) { have = false; if (hit) hit_out[ridx] = 1; }
             }
             // in the tail leave the loop as soon as an idle lane and a lane with deferred work coexist (hand-over above)
-        } while (exhausted ? (__ballot(have) && !(__ballot(!have) && __ballot(have && sp > sbase && sbase < MR_ANY_LDS))) : (__popcll(__ballot(have)) >= MR_REFILL));
+        } while (exhausted ? (__ballot(have) && !(__ballot(!have) && __ballot(have && sp > sbase && sbase < MR_ANY_LDS))) : (__popcll(__ballot(have)) >= MR_ANY_REFILL));
     }
     if (B.dbg && (threadIdx.x & 63) == 0) B.dbg[2 * (blockIdx.x * (MR_TRACE_BLOCK / 64) + (threadIdx.x >> 6)) + 1] = wall_clock64();
     if (COUNT && stats) { atomicAdd(&stats[2], c_boxes); atomicAdd(&stats[3], c_nodes); atomicAdd(&stats[4], c_leaves); atomicMax(&stats[8], (unsigned long long)c_maxsp);
