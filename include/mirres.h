@@ -538,6 +538,56 @@ int mirres_density_points(const mirres_density_t* net, const float* pos, long lo
 int mirres_density_volume(const mirres_density_t* net, const float* xs, int nx, const float* ys, int ny, const float* zs, int nz, float bound,
                           const float* grid_vol, int S, float thresh, float* out, void* stream);
 
+/* --------------------------------------------------------------------------------------------------------------------------------------------
+ * The stage-0 ray-marching operators (raymarch.hip): torch-ngp's raymarching module (raymarching/src/raymarching.cu), fp32 only, and the upkeep of the
+ * occupancy grid the marchers read (nerf/renderer.py:1438-1595).  The arithmetic is FIXED (csrc/device_march.hpp): no contraction, IEEE
+ * division, the reference's own C++ promotions, mrf_exp where the reference has __expf.  Deviations: march_rays_train hands out point offsets as the exclusive
+ * prefix sum of the per-ray counts (no atomic counter); every marching loop terminates for every input (a ray with a zero / non-finite direction or a NaN near /
+ * far takes no step; the voxel-skipping loop also ends at t >= far and when t + dt == t); a ray whose span leaves [0, M) and a rays_alive entry outside [0, N)
+ * are skipped, never followed.  Counts are 64-bit and at most 2^31 per call (one launch); H is a power of two in [2, 1024]; at most MIRRES_RM_MAX_CASCADES cascades.                            */
+#define MIRRES_RM_MAX_CASCADES 8
+/* raymarching.cu:92-145 kernel_near_far_from_aabb: rays_o/d f32[N,3], aabb f32[6] -> nears, fars f32[N]; a miss gives FLT_MAX for both.                      */
+int mirres_rm_near_far(const float* rays_o, const float* rays_d, const float* aabb, long long N, float min_near, float* nears, float* fars, void* stream);
+/* :214-232 kernel_morton3D: coords i32[N,3] -> indices i32[N];  :235-260 kernel_morton3D_invert: the inverse.                                                */
+int mirres_rm_morton3d(const int32_t* coords, long long N, int32_t* indices, void* stream);
+int mirres_rm_morton3d_invert(const int32_t* indices, long long N, int32_t* coords, void* stream);
+/* :268-300 kernel_packbits: grid f32[8 N] (16-byte aligned) -> bitfield u8[N], bit i of byte n = grid[8 n + i] > thresh.                                      */
+int mirres_rm_packbits(const float* grid, long long N, float thresh, uint8_t* bitfield, void* stream);
+/* :303-326 kernel_flatten_rays: rays i32[N,2] (offset, count) -> res i32[M], res[offset + i] = n.                                                             */
+int mirres_rm_flatten_rays(const int32_t* rays, long long N, long long M, int32_t* res, void* stream);
+/* :338-489 kernel_march_rays_train in three launches.  _count: the reference's first pass, rays[n,1] = steps of ray n (rays[n,0] = 0).  _scan: rays[n,0] = the
+ * exclusive prefix sum of rays[:,1] in ray order (clamped at 2^31 - 1), total[0] (device, 64-bit) = M.  _write: the second pass, xyzs/dirs f32[M,3], ts f32[M,2].  */
+int mirres_rm_march_train_count(const float* rays_o, const float* rays_d, const uint8_t* bitfield, float bound, int contract, float dt_gamma, int max_steps,
+                                long long N, int C, int H, const float* nears, const float* fars, const float* noises, int32_t* rays, void* stream);
+int mirres_rm_march_train_scan(int32_t* rays, long long N, long long* total, void* stream);
+int mirres_rm_march_train_write(const float* rays_o, const float* rays_d, const uint8_t* bitfield, float bound, int contract, float dt_gamma, int max_steps,
+                                long long N, int C, int H, const float* nears, const float* fars, const float* noises, const int32_t* rays, long long M,
+                                float* xyzs, float* dirs, float* ts, void* stream);
+/* :501-589 kernel_composite_rays_train_forward: weights f32[M] must arrive zeroed (samples behind an early stop are not written).                             */
+int mirres_rm_composite_train_fwd(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, long long M, long long N, float T_thresh,
+                                  int alpha_mode, float* weights, float* weights_sum, float* depth, float* image, void* stream);
+/* :605-705 kernel_composite_rays_train_backward: grad_sigmas f32[M], grad_rgbs f32[M,3] must arrive zeroed.                                                   */
+int mirres_rm_composite_train_bwd(const float* grad_weights, const float* grad_weights_sum, const float* grad_depth, const float* grad_image,
+                                  const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, const float* weights_sum, const float* depth,
+                                  const float* image, long long M, long long N, float T_thresh, int alpha_mode, float* grad_sigmas, float* grad_rgbs,
+                                  void* stream);
+/* :713-838 kernel_march_rays: the first n_alive entries of rays_alive name rays of the N; xyzs/dirs f32[n_alive n_step,3], ts f32[n_alive n_step,2] arrive zeroed. */
+int mirres_rm_march(long long n_alive, int n_step, const int32_t* rays_alive, const float* rays_t, const float* rays_o, const float* rays_d, long long N,
+                    float bound, int contract, float dt_gamma, int max_steps, int C, int H, const uint8_t* bitfield, const float* nears, const float* fars,
+                    float* xyzs, float* dirs, float* ts, const float* noises, void* stream);
+/* :842-933 kernel_composite_rays: accumulates into weights_sum, depth f32[N], image f32[N,3]; a finished ray's rays_alive entry becomes -1.                   */
+int mirres_rm_composite(long long n_alive, int n_step, long long N, float T_thresh, int alpha_mode, int32_t* rays_alive, float* rays_t, const float* sigmas,
+                        const float* rgbs, const float* ts, float* weights_sum, float* depth, float* image, void* stream);
+/* nerf/renderer.py:1438-1524 mark_untrained_grid in one launch: grid f32[C, H^3] (Morton order); poses f32[B,4,4] camera-to-world; intrinsics f32[4] or, with
+ * per_cam_intrinsics, f32[B,4] (fx, fy, cx, cy); cam_near_far f32[B,2] or NULL (then min_near); aabb f32[6].  The camera-space point is ((x r0 + y r1) + z r2)
+ * without FMA.  Cells no camera covers, or outside the box by more than half a cell, become -1; every other cell is left alone.                               */
+int mirres_rm_grid_mark_untrained(float* grid, int C, int H, float bound, const float* poses, int B, const float* intrinsics, int per_cam_intrinsics,
+                                  const float* cam_near_far, float min_near, const float* aabb, void* stream);
+/* nerf/renderer.py:1540-1577 update_extra_state's grid pass (non-trainable grid) in one launch over all cascades: per cell, in Morton index order, the point
+ * ((2 i / (H - 1) - 1) * (bound_c - half_cell)) + (2 noise - 1) * half_cell, each step rounded to fp32; sigma of `net` (evaluated with field_bound, the code of
+ * mirres_density_points) at it; grid = max(grid * decay, sigma) where both are >= 0.  noise f32[C, H^3, 3].  A cell at -1 costs no query.                      */
+int mirres_rm_grid_update(const mirres_density_t* net, float field_bound, float* grid, int C, int H, float bound, const float* noise, float decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

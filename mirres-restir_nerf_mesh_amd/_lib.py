@@ -158,6 +158,20 @@ SIGNATURES = {
     "mirres_density_layout": (C.c_longlong, [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(DensityNet)]),
     "mirres_density_points": (C.c_int, [C.POINTER(DensityNet), vp, C.c_longlong, f32, vp, vp, vp]),
     "mirres_density_volume": (C.c_int, [C.POINTER(DensityNet), vp, C.c_int, vp, C.c_int, vp, C.c_int, f32, vp, C.c_int, f32, vp, vp]),
+    "mirres_rm_near_far": (C.c_int, [vp, vp, vp, C.c_longlong, f32, vp, vp, vp]),
+    "mirres_rm_morton3d": (C.c_int, [vp, C.c_longlong, vp, vp]),
+    "mirres_rm_morton3d_invert": (C.c_int, [vp, C.c_longlong, vp, vp]),
+    "mirres_rm_packbits": (C.c_int, [vp, C.c_longlong, f32, vp, vp]),
+    "mirres_rm_flatten_rays": (C.c_int, [vp, C.c_longlong, C.c_longlong, vp, vp]),
+    "mirres_rm_march_train_count": (C.c_int, [vp, vp, vp, f32, C.c_int, f32, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "mirres_rm_march_train_scan": (C.c_int, [vp, C.c_longlong, vp, vp]),
+    "mirres_rm_march_train_write": (C.c_int, [vp, vp, vp, f32, C.c_int, f32, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp]),
+    "mirres_rm_composite_train_fwd": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_longlong, f32, C.c_int, vp, vp, vp, vp, vp]),
+    "mirres_rm_composite_train_bwd": (C.c_int, [vp] * 11 + [C.c_longlong, C.c_longlong, f32, C.c_int, vp, vp, vp]),
+    "mirres_rm_march": (C.c_int, [C.c_longlong, C.c_int, vp, vp, vp, vp, C.c_longlong, f32, C.c_int, f32, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mirres_rm_composite": (C.c_int, [C.c_longlong, C.c_int, C.c_longlong, f32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mirres_rm_grid_mark_untrained": (C.c_int, [vp, C.c_int, C.c_int, f32, vp, C.c_int, vp, C.c_int, vp, f32, vp, vp]),
+    "mirres_rm_grid_update": (C.c_int, [C.POINTER(DensityNet), f32, vp, C.c_int, C.c_int, f32, vp, f32, vp]),
     "mirres_ctx_reserve":(C.c_int, [vp, C.c_int]),
     "mirres_render": (C.c_int, [vp, vp, PARGS, vp]),
     "mirres_render_bwd": (C.c_int, [vp, PARGS, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -33,7 +33,7 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
-           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "density_layout",
+           "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "DensityGrid", "density_layout",
            "synthetic_checkpoint", "export_stage0", "occupancy_volume", "remove_selected_verts", "outer_shell", "export_outer_meshes"]
 
 
@@ -540,6 +540,111 @@ class DensityField:
         check(lib().mirres_density_volume(C.byref(self.net), ptr(axes[0]), res[0], ptr(axes[1]), res[1], ptr(axes[2]), res[2], self.bound, ptr(g), S,
                                           float(thresh) if g is not None else 0.0, ptr(out), stream_ptr()), "mirres_density_volume")
         return out
+
+
+class DensityGrid:
+    """The occupancy grid the ray marchers read, and its upkeep (nerf/renderer.py:1438-1595; csrc/raymarch.hip): density_grid f32 [C, H^3] in Morton order,
+    density_bitfield u8 [C * H^3 / 8], mean_density and iter_density, as NeRFRenderer keeps them for --cuda_ray.  C = cascade_of_bound(bound); cascade c covers
+    [-min(2^c, bound), min(2^c, bound)]^3."""
+
+    def __init__(self, bound=1.0, grid_size=128, density_thresh=10.0, min_near=0.2, density_grid=None, density_bitfield=None, aabb_train=None, mean_density=0.0,
+                 sdf=False, trainable_density_grid=False):
+        from . import checkpoint as CK
+        if sdf:
+            raise NotImplementedError("DensityGrid: the --sdf branch of update_extra_state (renderer.py:1567-1569) is not built")
+        if trainable_density_grid:
+            raise NotImplementedError("DensityGrid: --trainable_density_grid (renderer.py:1578-1586) is not built")
+        self.bound = float(bound)
+        H = int(grid_size)
+        if not (self.bound > 0 and np.isfinite(self.bound)):
+            raise ValueError("DensityGrid: bound %r" % (bound,))
+        if H < 2 or H > 1024 or H & (H - 1):
+            raise ValueError("DensityGrid: grid_size %d is not a power of two in [2, 1024]" % H)
+        self.grid_size, self.cascade = H, int(CK.cascade_of_bound(self.bound))
+        if self.cascade > 8:
+            raise ValueError("DensityGrid: bound %g needs %d cascades, at most 8 are supported" % (self.bound, self.cascade))
+        self.density_thresh, self.min_near = float(density_thresh), float(min_near)
+        cells = self.cascade * H ** 3
+        if density_grid is not None:
+            g = torch.as_tensor(density_grid)
+            if g.numel() != cells:
+                raise ValueError("DensityGrid: a density_grid of %s, bound %g and grid_size %d have [%d, %d]" % (tuple(g.shape), self.bound, H, self.cascade, H ** 3))
+        if density_bitfield is not None:
+            b = torch.as_tensor(density_bitfield)
+            if b.dtype != torch.uint8 or b.numel() != cells // 8:
+                raise ValueError("DensityGrid: a density_bitfield of %s %s, expected uint8 [%d]" % (b.dtype, tuple(b.shape), cells // 8))
+        if aabb_train is not None and torch.as_tensor(aabb_train).numel() != 6:
+            raise ValueError("DensityGrid: aabb_train of %s, expected [6]" % (tuple(torch.as_tensor(aabb_train).shape),))
+        dev = _dev()
+        self.density_grid = (torch.zeros(self.cascade, H ** 3, dtype=torch.float32, device=dev) if density_grid is None
+                             else g.detach().to(dev, torch.float32).reshape(self.cascade, H ** 3).contiguous().clone())
+        self.density_bitfield = (torch.zeros(cells // 8, dtype=torch.uint8, device=dev) if density_bitfield is None else b.detach().to(dev).reshape(-1).contiguous().clone())
+        b_ = self.bound
+        self.aabb_train = (torch.tensor([-b_, -b_, -b_, b_, b_, b_], dtype=torch.float32, device=dev) if aabb_train is None
+                           else torch.as_tensor(aabb_train).detach().to(dev, torch.float32).reshape(6).contiguous())
+        self.mean_density, self.iter_density = float(mean_density), 0
+
+    @classmethod
+    def from_checkpoint(cls, ckpt, bound=1.0, **kw):
+        """A stage-0 checkpoint dict (or its `model`): density_grid [C, H^3] and, when present, density_bitfield and aabb_train; mean_density from the top level."""
+        model = ckpt["model"] if "model" in ckpt else ckpt
+        if "density_grid" not in model:
+            raise KeyError("checkpoint has no density_grid")
+        g = torch.as_tensor(model["density_grid"])
+        if g.dim() != 2:
+            raise ValueError("the checkpoint's density_grid of %s is not [cascade, H^3]" % (tuple(g.shape),))
+        H = int(round(g.shape[1] ** (1.0 / 3.0)))
+        if H ** 3 != g.shape[1]:
+            raise ValueError("density_grid: %d values per cascade is not a cube" % g.shape[1])
+        return cls(bound=bound, grid_size=H, density_grid=g, density_bitfield=model.get("density_bitfield"), aabb_train=model.get("aabb_train"),
+                   mean_density=float(ckpt.get("mean_density", 0.0)) if "model" in ckpt else 0.0, **kw)
+
+    def mark_untrained(self, poses, intrinsics, aabb_train=None, min_near=None, cam_near_far=None):
+        """mark_untrained_grid (renderer.py:1438-1524) in one kernel: poses [B, 4, 4] camera-to-world, intrinsics [4] or [B, 4] (fx, fy, cx, cy), cam_near_far [B, 2] or
+        None (then min_near).  Cells no camera covers or outside aabb_train by more than half a cell become -1 -> how many cells are at -1 now marked."""
+        dev = _dev()
+        poses = torch.as_tensor(poses).detach().to(dev, torch.float32)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+            raise ValueError("mark_untrained: poses of %s, expected [B, 4, 4]" % (tuple(poses.shape),))
+        B = int(poses.shape[0])
+        K = torch.as_tensor(intrinsics).detach().to(dev, torch.float32)
+        if tuple(K.shape) not in ((4,), (1, 4), (B, 4)):
+            raise ValueError("mark_untrained: intrinsics of %s, expected [4] or [%d, 4]" % (tuple(K.shape), B))
+        per_cam = int(K.dim() == 2 and K.shape[0] == B and B > 1)
+        nf = None
+        if cam_near_far is not None:
+            nf = torch.as_tensor(cam_near_far).detach().to(dev, torch.float32).contiguous()
+            if tuple(nf.shape) != (B, 2):
+                raise ValueError("mark_untrained: cam_near_far of %s, expected [%d, 2]" % (tuple(nf.shape), B))
+        aabb = self.aabb_train if aabb_train is None else torch.as_tensor(aabb_train).detach().to(dev, torch.float32).reshape(-1).contiguous()
+        if aabb.numel() != 6:
+            raise ValueError("mark_untrained: aabb_train of %d values, expected 6" % aabb.numel())
+        poses, K = poses.contiguous(), K.reshape(-1).contiguous()
+        check(lib().mirres_rm_grid_mark_untrained(ptr(self.density_grid), self.cascade, self.grid_size, self.bound, ptr(poses) if B else None, B, ptr(K), per_cam,
+                                                  ptr(nf), float(self.min_near if min_near is None else min_near), ptr(aabb), stream_ptr()), "mirres_rm_grid_mark_untrained")
+        return int((self.density_grid == -1).sum().item())
+
+    def update(self, field, decay=0.95, noise=None):
+        """update_extra_state (renderer.py:1527-1595) for the non-trainable grid: one fused kernel over all cascades evaluates `field` (a DensityField) at every cell's
+        jittered lattice point and writes max(grid * decay, sigma) where both are >= 0; then mean_density from torch, iter_density += 1, and the bitfield packed at
+        min(mean_density, density_thresh).  noise f32 [C, H^3, 3] in [0, 1) (Morton order), or None for torch.rand."""
+        from . import raymarching
+        if not isinstance(field, DensityField):
+            raise TypeError("DensityGrid.update: field must be a DensityField, got %s" % type(field).__name__)
+        H, Cn = self.grid_size, self.cascade
+        if noise is None:
+            noise = torch.rand(Cn, H ** 3, 3, dtype=torch.float32, device=self.density_grid.device)
+        else:
+            noise = torch.as_tensor(noise)
+            if tuple(noise.shape) != (Cn, H ** 3, 3):
+                raise ValueError("DensityGrid.update: noise of %s, expected [%d, %d, 3]" % (tuple(noise.shape), Cn, H ** 3))
+            noise = noise.detach().to(self.density_grid.device, torch.float32).contiguous()
+        check(lib().mirres_rm_grid_update(C.byref(field.net), field.bound, ptr(self.density_grid), Cn, H, self.bound, ptr(noise), float(decay), stream_ptr()),
+              "mirres_rm_grid_update")
+        self.mean_density = torch.mean(self.density_grid.clamp(min=0)).item()      # -1 cells count as 0 (renderer.py:1588)
+        self.iter_density += 1
+        self.density_bitfield = raymarching.packbits(self.density_grid, min(self.mean_density, self.density_thresh), self.density_bitfield)
+        return None
 
 
 def _synthetic_outer_row(S, k, c, A):
