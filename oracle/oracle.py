@@ -27,15 +27,16 @@ def build(force=False):
 
 
 def build_ref(force=False):
-    """oracle/_ref: the reference's own bilateral-denoiser kernels compiled by hipcc from /root/reference (oracle/Makefile `ref`). Only possible where the
-    reference tree exists (the build container); the GPU box uses the prebuilt oracle/_ref/libref_denoise.so that travelled with the snapshot."""
+    """oracle/_ref: the reference's own kernels compiled by hipcc from the reference tree (oracle/Makefile `ref`): the bilateral denoiser (libref_denoise.so) and the
+    ray-marching operators (libref_raymarch.so).  Only possible where the reference tree exists (the build container); the GPU box uses the prebuilt files that
+    travelled with the snapshot.  make decides what is stale (drivers, shim headers, the reference's sources), so it runs on every call.  -> the list of the files
+    that exist afterwards (None without a reference tree).  When one is missing its consumer skips: tests/test_gpu_bilateral.py's reference-kernel comparison without
+    libref_denoise.so, the whole of tests/test_gpu_ref_raymarch.py without libref_raymarch.so (the build's failure text names the first only)."""
     ref = os.environ.get("MIRRES_REF", "/root/reference")
     if not os.path.isdir(ref):
         return None
-    out = os.path.join(_HERE, "_ref", "libref_denoise.so")
-    if force or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(os.path.join(_HERE, "ref_denoise_driver.hip")):
-        subprocess.run(["make", "-C", _HERE, "ref", "REF=" + ref] + (["-B"] if force else []), check=True, capture_output=True, text=True)   # the tree the isdir test looked at
-    return out
+    subprocess.run(["make", "-C", _HERE, "ref", "REF=" + ref] + (["-B"] if force else []), check=True, capture_output=True, text=True)   # the tree the isdir test looked at
+    return [q for q in (os.path.join(_HERE, "_ref", f) for f in ("libref_denoise.so", "libref_raymarch.so")) if os.path.exists(q)]
 
 
 def ref_denoise_lib():
@@ -47,6 +48,25 @@ def ref_denoise_lib():
     vp = C.c_void_p
     L.ref_bilateral_fwd.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]; L.ref_bilateral_fwd.restype = C.c_int
     L.ref_bilateral_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]; L.ref_bilateral_bwd.restype = C.c_int
+    return L
+
+
+def ref_raymarch_lib():
+    """ctypes handle of oracle/_ref/libref_raymarch.so (GPU code: the reference's raymarching.cu behind oracle/ref_raymarch_driver.hip; every entry takes device
+    pointers, synchronises and returns the HIP error code), or None when it was not built."""
+    p = os.path.join(_HERE, "_ref", "libref_raymarch.so")
+    if not os.path.exists(p):
+        return None
+    L = C.CDLL(p)
+    vp, u, i, f = C.c_void_p, C.c_uint32, C.c_int, C.c_float
+    sig = dict(ref_near_far_from_aabb=[vp, vp, vp, u, f, vp, vp], ref_morton3D=[vp, u, vp], ref_morton3D_invert=[vp, u, vp], ref_packbits=[vp, u, f, vp],
+               ref_flatten_rays=[vp, u, u, vp], ref_march_rays_train=[vp, vp, vp, f, i, f, u, u, u, u, vp, vp, vp, vp, vp, vp, vp, vp],
+               ref_composite_rays_train_forward=[vp, vp, vp, vp, u, u, f, i, vp, vp, vp, vp],
+               ref_composite_rays_train_backward=[vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u, u, f, i, vp, vp],
+               ref_march_rays=[u, u, vp, vp, vp, vp, f, i, f, u, u, u, vp, vp, vp, vp, vp, vp, vp], ref_composite_rays=[u, u, f, i, vp, vp, vp, vp, vp, vp, vp, vp],
+               ref_fast_exp=[vp, vp, u])
+    for name, args in sig.items():
+        fn = getattr(L, name); fn.argtypes = args; fn.restype = C.c_int
     return L
 
 

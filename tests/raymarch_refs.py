@@ -123,9 +123,11 @@ def _mip(mx, top):
     return np.fmin(top, np.fmax(F(0), e)).astype(np.int32)
 
 
-def _march(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t_start, noises, num_steps, eps, max_trips=NO_CAP):
+def _march(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t_start, noises, num_steps, eps, max_trips=NO_CAP, guards=True):
     """Every ray from t_start (+ the noise offset) for at most num_steps[n] samples -> samples f32 [N, cap, 5] (cx, cy, cz, t after the step, dt), counts, the loop
-    passes per ray, t at the end."""
+    passes per ray, t at the end.  guards=False leaves out the three termination guards the reference does not have (rm_ray_ok, the skipping loop's t + dt == t and
+    t >= far tests): the loops as raymarching.cu:396-465 / :759-827 has them, ended by max_trips alone where they would spin.  A ray that provably never ends (t + dt == t in
+    the skipping loop: it spins there, or the outer loop repeats one pass for ever; or tt = +inf) is charged max_trips passes at once, without being walked."""
     o = np.asarray(o, np.float32).reshape(-1, 3); d = np.asarray(d, np.float32).reshape(-1, 3)
     N = o.shape[0]
     bits = np.asarray(bits, np.uint8)
@@ -143,7 +145,7 @@ def _march(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t
         t = np.asarray(t_start, np.float32).copy()
         t = t + clamp(t * g, dt_min, dt_max) * np.asarray(noises, np.float32)
         m = np.fmax(np.abs(d[:, 0]), np.fmax(np.abs(d[:, 1]), np.abs(d[:, 2])))
-        done = ~((d == d).all(1) & (m > 0) & (m < np.inf) & (near == near) & (far == far))
+        done = ~((d == d).all(1) & (m > 0) & (m < np.inf) & (near == near) & (far == far)) if guards else np.zeros(N, bool)
         step = np.zeros(N, np.int64); trips = np.zeros(N, np.int64)
         inner = np.zeros(N, bool); tt = np.zeros(N, np.float32)
         sgn = np.copysign(F(1), d)
@@ -156,13 +158,17 @@ def _march(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t
                 ts = t[li]
                 tn = ts + clamp(ts * g, dt_min, dt_max)
                 adv = ~(tn == ts)
+                if not guards:      # t stands still: the do-while spins below tt, and past it the outer loop repeats the same pass (t and step as before); tt = +inf
+                    spin = ~adv | ((tt[li] == np.inf) & (tn < tt[li]))
+                    trips[li[spin]] = max_trips
+                    adv = ~spin
                 done[li[~adv]] = True                                       # absorbed
                 a = li[adv]
                 t[a] = tn[adv]; trips[a] += 1
                 capped = trips[a] >= max_trips
                 done[a[capped]] = True
                 inner[li] = False
-                inner[a] = ~capped & (tn[adv] < tt[a]) & (tn[adv] < far[a])
+                inner[a] = ~capped & (tn[adv] < tt[a]) & ((tn[adv] < far[a]) if guards else True)
             if lo.size:                                                     # one pass of the outer loop
                 trips[lo] += 1
                 capped = trips[lo] >= max_trips
@@ -223,6 +229,25 @@ def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, contr
     filled = np.arange(n_step)[None, :] < step[:, None]
     dirs = np.where(filled[..., None], d[j][:, None, :], F(0))
     return full[..., :3].reshape(-1, 3).copy(), dirs.reshape(-1, 3).astype(np.float32), full[..., 3:5].reshape(-1, 2).copy(), trips
+
+
+def reference_loops_end(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t_start, noises, num_steps, eps):
+    """The gate in front of every launch of the REFERENCE'S marchers (oracle/_ref/libref_raymarch.so), whose loops have no termination guard: per ray, whether the
+    loops as the reference has them (guards=False) end by themselves within TRIP_CAP passes.  A launch happens only when this is true of every ray."""
+    return _march(o, d, bits, bound, contract, dt_gamma, max_steps, Cn, H, near, far, t_start, noises, num_steps, eps, TRIP_CAP, guards=False)[2] < TRIP_CAP
+
+
+def train_case_loops_end(c):
+    """reference_loops_end for a march_train_case."""
+    return reference_loops_end(c["o"], c["d"], c["bits"], c["bound"], c["contract"], c["dt_gamma"], c["max_steps"], c["C"], c["H"], c["nears"], c["fars"], c["nears"],
+                               c["noises"], c["max_steps"], 0.0)
+
+
+def infer_round_loops_end(c, r):
+    """reference_loops_end for one round of an infer_case: the march_rays form (start at rays_t, 1 / (d + 1e-10f), n_step samples)."""
+    j = r["rays_alive"].astype(np.int64)
+    return reference_loops_end(c["o"][j], c["d"][j], c["bits"], 1.0, False, 0.0, c["max_steps"], 1, c["H"], c["nears"][j], c["fars"][j], r["rays_t"][j],
+                               np.zeros(r["n_alive"], np.float32), r["n_step"], 1e-10)
 
 
 # ---------------------------------------------------------------------------------------------------------------- compositing
@@ -358,7 +383,76 @@ def composite_train_torch64(sigmas, rgbs, ts, rays, T_thresh, alpha_mode):
     return weights, torch.stack(ws), torch.stack(dp), torch.stack(im)
 
 
-def composite_error_bound(sigmas, ts, rays, alpha_mode, values=None):
+def alpha_error_constant(alpha_mode, exp_ulps=2):
+    """A of composite_error_bound: |d alpha| <= A u for alpha = fl(1 - exp(-fl(sigma dt))) with the given error of the exponential (the derivation is there)."""
+    ea, eb = exp_ulps if isinstance(exp_ulps, tuple) else (exp_ulps, 0.0)
+    return 0.0 if alpha_mode else (5.4 if (ea, eb) == (2, 0.0) else 2.0 * ea + (2.0 * eb + 1.0) / np.e + 1.0)
+
+
+def composite_rays_float64(n_step, idx, weights_sum, depth, image, sigmas, rgbs, ts, T_thresh, alpha_mode, exp_ulps=2, rel=1e-5):
+    """One composite_rays call (raymarching.cu:842-924) in float64 on the call's own float32 inputs, for the alive rays `idx` (ids into the per-ray state), with the
+    forward-error bound of a float32 run of it.  -> acc f64 [n, 5] (r, g, b, weights_sum, depth afterwards), stays (the ray was not ended), t (the last sample's t),
+    near (1 - weights_sum came within a relative `rel` of T_thresh at some sample the ray looked at: its end may differ in float32), bound f64 [n, 5].
+    The bound, first order in u = 2^-24, for inputs with 0 <= alpha <= 1 and 0 <= weights_sum <= 1.  Per sample k = 0, 1, ... of the call: |d alpha| <= A u
+    (alpha_error_constant).  T = fl(1 - ws): |dT| <= |dws| + u.  w = fl(alpha T): |dw| <= A u T + alpha (|dws| + u) + u w.  ws' = fl(ws + w) = (1 - alpha) ws + alpha
+    in exact arithmetic, so an error of ws enters ws' with the factor 1 - alpha <= 1: |dws'| <= |dws| + A u T + alpha u + u w + u ws' <= |dws| + (A + 3) u, i.e.
+    |dws_k| <= k (A + 3) u =: E_k before sample k (the state the call starts from is shared, so E_0 = 0).  A sum acc' = fl(acc + fl(w v)) (v = t: depth, v = a
+    colour channel): |d acc'| <= |d acc| + |v| |dw| + u |w v| + u |acc'|.  Summed over the samples the ray used, with u' = u / (1 - 8 n u) for the higher orders:
+      bound_ws = n (A + 3) u',   bound_v = u' sum_k [ |v_k| (A T_k + alpha_k (E_k / u + 1) + w_k) + |w_k v_k| + |acc_k'| ],  evaluated on the float64 values."""
+    idx = np.asarray(idx, np.int64); n = idx.shape[0]
+    im = np.asarray(image, np.float64).reshape(-1, 3)
+    acc = np.stack([im[idx, 0], im[idx, 1], im[idx, 2], np.asarray(weights_sum, np.float64)[idx], np.asarray(depth, np.float64)[idx]], 1)
+    sig = np.asarray(sigmas, np.float64).reshape(n, n_step); rgb = np.asarray(rgbs, np.float64).reshape(n, n_step, 3); ts = np.asarray(ts, np.float64).reshape(n, n_step, 2)
+    A = alpha_error_constant(alpha_mode, exp_ulps)
+    u1 = U / (1.0 - 8.0 * n_step * U)
+    going = np.ones(n, bool); step = np.zeros(n, np.int64); near = np.zeros(n, bool); t = np.zeros(n); used = np.zeros(n)
+    bound = np.zeros((n, 5))
+    with np.errstate(all="ignore"):
+        for k in range(n_step):
+            going &= ts[:, k, 0] != 0
+            T = 1.0 - acc[:, 3]
+            near |= going & (np.abs(T - T_thresh) <= rel * T_thresh)
+            alpha = sig[:, k] if alpha_mode else 1.0 - np.exp(-sig[:, k] * ts[:, k, 1])
+            w = np.where(going, alpha * T, 0.0)
+            dw = np.where(going, A * T + alpha * (used * (A + 3.0) + 1.0) + w, 0.0)      # |dw| / u
+            v = np.stack([rgb[:, k, 0], rgb[:, k, 1], rgb[:, k, 2], np.ones(n), ts[:, k, 0]], 1)
+            acc += w[:, None] * v
+            t = np.where(going, ts[:, k, 0], t)
+            bound += np.where(going[:, None], u1 * (np.abs(v) * dw[:, None] + np.abs(w[:, None] * v) + np.abs(acc)), 0.0)
+            used += going
+            going &= ~(T < T_thresh)
+            step += going
+    bound[:, 3] = used * (A + 3.0) * u1
+    return acc, step >= n_step, t, near, bound
+
+
+def composite_rays_sets(n_step=16):
+    """Stand-alone composite_rays inputs cut from the compositing sets: every ray of train_composite_inputs with at least n_step samples gives its first n_step (both
+    alpha modes), and the three constant-sigma rays 50 of theirs (the third has 7: the rest of its slots are ts = 0 rows, as the marcher leaves them).  Every seventh
+    ray of the random sets gets ts = 0 rows from some slot on.  The per-ray state starts from non-zero sums; rays_alive is a permutation into a larger state.
+    -> [(name, alpha_mode, n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, ts, weights_sum, depth, image)]"""
+    out = []
+    for name, am, (sig, rgb, ts, rays, M), ns in (("random-0", 0, train_composite_inputs(False), n_step), ("random-1", 1, train_composite_inputs(True), n_step),
+                                                  ("constant", 0, constant_sigma_rays(), 50)):
+        rng = np.random.default_rng(91 + am)
+        off, cnt, ok = _spans(rays, M)
+        pick = np.nonzero(ok & ((cnt >= ns) | (name == "constant")))[0]
+        n = pick.shape[0]
+        s2 = np.zeros((n, ns), np.float32); c2 = np.zeros((n, ns, 3), np.float32); t2 = np.zeros((n, ns, 2), np.float32)
+        for i, r in enumerate(pick):
+            m = min(ns, int(cnt[r]))
+            s2[i, :m] = sig[off[r]:off[r] + m]; c2[i, :m] = rgb[off[r]:off[r] + m]; t2[i, :m] = ts[off[r]:off[r] + m]
+            if name != "constant" and i % 7 == 3:
+                t2[i, int(rng.integers(0, ns)):] = 0
+        N = n + 5
+        alive = rng.permutation(N)[:n].astype(np.int32)
+        state = (rng.uniform(0.1, 0.5, N).astype(np.float32), rng.uniform(0, 0.3, N).astype(np.float32), rng.uniform(0, 1, N).astype(np.float32),
+                 rng.uniform(0, 1, (N, 3)).astype(np.float32))
+        out.append((name, am, n, ns, alive, state[0], s2.reshape(-1), c2.reshape(-1, 3), t2.reshape(-1, 2), state[1], state[2], state[3]))
+    return out
+
+
+def composite_error_bound(sigmas, ts, rays, alpha_mode, values=None, exp_ulps=2):
     """Forward-error bound of the float32 compositing against exact arithmetic on the same inputs, per ray, for sum_k w_k v_k (v = 1: weights_sum; v = t: depth; v = a
     colour channel), first order in u = 2^-24 with the higher orders folded into u' = u / (1 - 8 n u).  Derivation, per sample k (0-based) of a ray of n samples:
       x = fl(sigma dt): relative u.  e = mrf_exp(-x): within 2 ulp = 4 u relative of exp(-x), and exp(-x) moves by x u relative when x does: |de| <= (4 e + x e) u
@@ -366,11 +460,15 @@ def composite_error_bound(sigmas, ts, rays, alpha_mode, values=None):
       q = fl(1 - alpha): |dq| <= (A + 1) u.  T_k = the product of k such factors, each <= 1, one rounding per product: |dT_k| <= k (A + 2) u.
       w = fl(alpha T): |dw_k| <= A u T_k + alpha_k k (A + 2) u + u w_k.
       term = fl(w v): |d term| <= |v| |dw_k| + u |w v|;  the n sequential additions: gamma_n sum |w v| <= n u sum |w v|.
-    Total: u' * sum_k [ |v_k| (A T_k + (A + 2) k alpha_k + w_k) + |w_k v_k| ] + n u' sum_k |w_k v_k|, evaluated on the float64 values."""
+    Total: u' * sum_k [ |v_k| (A T_k + (A + 2) k alpha_k + w_k) + |w_k v_k| ] + n u' sum_k |w_k v_k|, evaluated on the float64 values.
+    exp_ulps: the exponential's error.  A number K: within K ulp = 2 K u relative everywhere, so |de| <= (2 K e + x e) u <= (2 K + 1/e) u and A = 2 K + 1/e + 1
+    (K = 2: 5.37, kept as today's 5.4).  A pair (a, b): an error that may grow with the argument, within (a + b x) ulp at exp(-x) — an exponential formed as
+    exp2(x log2 e) carries the rounding of the product, an absolute x log2(e) u in the exponent, into a relative error proportional to x —
+    |de| <= (2 a + (2 b + 1) x) e^-x u <= (2 a + (2 b + 1) / e) u, since e^-x <= 1 and x e^-x <= 1/e: A = 2 a + (2 b + 1) / e + 1."""
     sig = np.asarray(sigmas, np.float64); ts = np.asarray(ts, np.float64).reshape(-1, 2)
     M = sig.shape[0]
     offset, count, ok = _spans(rays, M)
-    A = 0.0 if alpha_mode else 5.4
+    A = alpha_error_constant(alpha_mode, exp_ulps)
     out = np.zeros(len(count))
     for n in np.nonzero(ok)[0]:
         sl = slice(int(offset[n]), int(offset[n] + count[n]))
@@ -383,6 +481,60 @@ def composite_error_bound(sigmas, ts, rays, alpha_mode, values=None):
         u1 = U / (1.0 - 8.0 * nn * U)
         out[n] = u1 * np.sum(v * (A * Tex + (A + 2.0) * k * alpha + w) + w * v) + nn * u1 * np.sum(w * v)
     return out
+
+
+def transmittance_near_threshold(sigmas, ts, rays, T_thresh, alpha_mode, rel=1e-5):
+    """Per ray: does the float64 transmittance after some sample, up to and including the one that ends the ray, come within a relative `rel` of T_thresh?  Such a
+    ray may use one sample more or fewer in float32 than in exact arithmetic, whichever exponential is used; every other ray uses the same number."""
+    sig = np.asarray(sigmas, np.float64); ts = np.asarray(ts, np.float64).reshape(-1, 2)
+    offset, count, ok = _spans(rays, sig.shape[0])
+    near = np.zeros(len(count), bool)
+    with np.errstate(all="ignore"):
+        for n in np.nonzero(ok)[0]:
+            sl = slice(int(offset[n]), int(offset[n] + count[n]))
+            alpha = sig[sl] if alpha_mode else 1.0 - np.exp(-sig[sl] * ts[sl, 1])
+            Tin = np.cumprod(1.0 - alpha)
+            cut = np.nonzero(Tin < T_thresh)[0]
+            Tin = Tin[:cut[0] + 1] if cut.size else Tin
+            near[n] = bool((np.abs(Tin - T_thresh) <= rel * T_thresh).any())
+    return near
+
+
+def train_composite_inputs(alpha_mode):
+    """512 rays, M just under 20 000: lengths 0, 1, 2, 63, 64, 65 and the cap 1024, rays cut by T_thresh at the first step, in the middle and never, one ray with
+    offset + n > M, sigma = 0 and sigma = +inf samples."""
+    rng = np.random.default_rng(77 + int(alpha_mode))
+    counts = np.concatenate([[0, 1, 2, 63, 64, 65, 1024], rng.integers(1, 70, 504), [40]])
+    assert counts.shape[0] == 512
+    offs = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    M = int(counts[:-1].sum()) + 7
+    assert M <= 20000
+    dt = rng.uniform(0.002, 0.02, M)
+    alpha = rng.uniform(0.0, 0.6, M)
+    alpha[offs[6]:offs[6] + 1024] = rng.uniform(0, 0.004, 1024)               # the cap-length ray is never cut: 0.996^1024 > 1e-2
+    alpha[offs[5]:offs[5] + 65] = 0.0; alpha[offs[5] + 30] = 0.99999            # cut in the middle
+    alpha[offs[4]] = 0.99999                                                   # cut at the first step
+    alpha[offs[3]:offs[3] + 63] = 0.01                                        # never cut
+    sig = alpha.copy() if alpha_mode else -np.log1p(-alpha) / dt
+    sig[offs[10] + 1] = 0.0
+    if not alpha_mode:
+        sig[offs[11]] = np.inf
+    ts = np.stack([0.5 + np.cumsum(dt) * 0.01, dt], 1)
+    rgb = rng.uniform(0, 1, (M, 3))
+    rays = np.stack([offs, counts], 1).astype(np.int32)
+    return sig.astype(np.float32), rgb.astype(np.float32), ts.astype(np.float32), rays, M
+
+
+def constant_sigma_rays():
+    """The three rays of tests/test_raymarch_host.py::test_compositing_constant_sigma_closed_form as one input set -> sigmas, rgbs, ts, rays, M."""
+    sets = [(3.0, 0.01, 50), (40.0, 0.004, 200), (0.5, 0.02, 7)]
+    sig = np.concatenate([np.full(n, s, np.float32) for s, dt, n in sets])
+    ts = np.concatenate([np.stack([0.5 + dt * np.arange(1, n + 1), np.full(n, dt)], 1) for s, dt, n in sets]).astype(np.float32)
+    counts = np.array([n for _, _, n in sets])
+    rays = np.stack([np.concatenate([[0], np.cumsum(counts)[:-1]]), counts], 1).astype(np.int32)
+    M = int(counts.sum())
+    rgb = np.random.default_rng(12).uniform(0, 1, (M, 3)).astype(np.float32)
+    return sig, rgb, ts, rays, M
 
 
 # ---------------------------------------------------------------------------------------------------------------- the occupancy grid
@@ -505,6 +657,35 @@ def march_train_case(kind, shape_i, param_i, N, hostile=True):
     return case
 
 
+# ---------------------------------------------------------------------------------------------------------------- tests/golden/ref_raymarch.npz
+def golden_cases():
+    """The march_rays_train cases recorded from the reference's kernels: every grid and shape, the parameter sets with max_steps = 64, 65 rays, none hostile."""
+    return [(k, s, p) for k in range(len(GRID_KINDS)) for s in range(len(GRID_SHAPES)) for p in range(len(MARCH_PARAMS)) if MARCH_PARAMS[p]["max_steps"] == 64]
+
+
+def near_far_inputs():
+    """The 4096 rays of tests/test_gpu_raymarch.py::test_near_far_bit_equal: zero components, -0.0, a miss, origins inside -> rays_o, rays_d, aabb."""
+    N = 4096
+    rng = np.random.default_rng(2)
+    o = rng.uniform(-3, 3, size=(N, 3)).astype(np.float32)
+    o[:1024] = rng.uniform(-0.9, 0.9, size=(1024, 3))
+    d = rng.normal(size=(N, 3)).astype(np.float32); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    for k in range(3):
+        d[100 + k::97, k] = 0.0
+    d[7, 1] = -0.0; d[8] = [-0.0, 0.0, 1.0]
+    o[9] = [5, 5, 5]; d[9] = [1, 0, 0]
+    return o, d, np.array([-1, -1, -1, 1, 1, 1], np.float32)
+
+
+def digest(a):
+    """SHA-256 of an array's bytes, every NaN first made the same quiet NaN -> u8 [32]."""
+    import hashlib
+    a = np.ascontiguousarray(a).copy()
+    if a.dtype == np.float32:
+        a[np.isnan(a)] = np.float32(np.nan)
+    return np.frombuffer(hashlib.sha256(a.tobytes()).digest(), np.uint8)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the inference loop's shared inputs
 def sigma_of(xyzs):
     """A fixed function of position: a soft ball that turns opaque fast.  numpy float32 here; tests/test_gpu_raymarch.py applies the same operations in torch."""
@@ -516,15 +697,15 @@ INFER_COLOUR = np.array([0.9, 0.5, 0.2], np.float32)
 
 
 @functools.lru_cache(maxsize=None)
-def infer_case(N=1024, H=16, max_steps=256, T_thresh=1e-2):
+def infer_case(N=1024, H=16, max_steps=256, T_thresh=1e-2, hostile=True):
     """The loop of nerf/renderer.py:784-828 on the host, computed once per process: a ball of occupied cells (centres within 0.85) around sigma_of's smaller ball,
-    make_rays' rays WITH the hostile ones, constant colours.  -> the inputs and, per round, what went into march_rays (n_alive, n_step, rays_alive, rays_t) and what
+    make_rays' rays WITH the hostile ones (unless hostile=False), constant colours.  -> the inputs and, per round, what went into march_rays (n_alive, n_step, rays_alive, rays_t) and what
     came out of it and of composite_rays (xyzs, dirs, ts, loop passes, rays_alive and rays_t afterwards), then the final weights_sum, depth, image."""
     cells = np.stack(np.meshgrid(*[np.arange(H)] * 3, indexing="ij"), -1).reshape(-1, 3)
     occ = np.zeros(H ** 3, np.float32)
     occ[morton3D(cells)] = (np.linalg.norm((cells + 0.5) / H * 2 - 1, axis=1) < 0.85).astype(np.float32)
     bits = packbits(occ, 0.5)
-    o, d, nears, fars, _ = make_rays(N, 1.0, H, seed=40, hostile=True)
+    o, d, nears, fars, _ = make_rays(N, 1.0, H, seed=40, hostile=hostile)
     ws, dp, im = np.zeros(N, np.float32), np.zeros(N, np.float32), np.zeros((N, 3), np.float32)
     rounds = []
     rays_alive, rays_t, step = np.arange(N, dtype=np.int32), nears.copy(), 0

@@ -60,16 +60,8 @@ def test_integer_helpers_bit_equal(RM):
 
 
 def test_near_far_bit_equal(RM):
-    N = 4096
-    rng = np.random.default_rng(2)
-    o = rng.uniform(-3, 3, size=(N, 3)).astype(np.float32)
-    o[:1024] = rng.uniform(-0.9, 0.9, size=(1024, 3))                        # origins inside
-    d = rng.normal(size=(N, 3)).astype(np.float32); d /= np.linalg.norm(d, axis=1, keepdims=True)
-    for k in range(3):
-        d[100 + k::97, k] = 0.0                                              # a zero component on each axis
-    d[7, 1] = -0.0; d[8] = [-0.0, 0.0, 1.0]
-    o[9] = [5, 5, 5]; d[9] = [1, 0, 0]                                       # a miss
-    aabb = np.array([-1, -1, -1, 1, 1, 1], np.float32)
+    o, d, aabb = R.near_far_inputs()                                         # zero components on each axis, -0.0, a miss, origins inside
+    N = o.shape[0]
     near, far = RM.near_far_from_aabb(dev(o), dev(d), dev(aabb), 0.2)
     wn, wf = R.near_far_from_aabb(o, d, aabb, 0.2)
     assert same(host(near), wn) and same(host(far), wf)
@@ -175,29 +167,7 @@ def test_inference_loop_bit_equal(RM):
 
 
 # ---------------------------------------------------------------------------------------------------------------- composite_rays_train
-def train_composite_inputs(alpha_mode):
-    """512 rays, M just under 20 000: lengths 0, 1, 2, 63, 64, 65 and the cap 1024, rays cut by T_thresh at the first step, in the middle and never, one ray with
-    offset + n > M, sigma = 0 and sigma = +inf samples."""
-    rng = np.random.default_rng(77 + int(alpha_mode))
-    counts = np.concatenate([[0, 1, 2, 63, 64, 65, 1024], rng.integers(1, 70, 504), [40]])
-    assert counts.shape[0] == 512
-    offs = np.concatenate([[0], np.cumsum(counts)[:-1]])
-    M = int(counts[:-1].sum()) + 7
-    assert M <= 20000
-    dt = rng.uniform(0.002, 0.02, M)
-    alpha = rng.uniform(0.0, 0.6, M)
-    alpha[offs[6]:offs[6] + 1024] = rng.uniform(0, 0.004, 1024)               # the cap-length ray is never cut: 0.996^1024 > 1e-2
-    alpha[offs[5]:offs[5] + 65] = 0.0; alpha[offs[5] + 30] = 0.99999            # cut in the middle
-    alpha[offs[4]] = 0.99999                                                   # cut at the first step
-    alpha[offs[3]:offs[3] + 63] = 0.01                                        # never cut
-    sig = alpha.copy() if alpha_mode else -np.log1p(-alpha) / dt
-    sig[offs[10] + 1] = 0.0
-    if not alpha_mode:
-        sig[offs[11]] = np.inf
-    ts = np.stack([0.5 + np.cumsum(dt) * 0.01, dt], 1)
-    rgb = rng.uniform(0, 1, (M, 3))
-    rays = np.stack([offs, counts], 1).astype(np.int32)
-    return sig.astype(np.float32), rgb.astype(np.float32), ts.astype(np.float32), rays, M
+train_composite_inputs = R.train_composite_inputs      # shared with tests/test_gpu_ref_raymarch.py and the host tests
 
 
 @pytest.mark.parametrize("alpha_mode", [False, True])

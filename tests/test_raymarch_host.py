@@ -374,6 +374,103 @@ def test_host_build_composites_like_the_restatement(host):
         assert ha[4] == -1 and ha[2] == -1 and (ha >= 0).any()
 
 
+# ---------------------------------------------------------------------------------------------------------------- what may reach the reference's own kernels
+@pytest.mark.parametrize("kind", R.GRID_KINDS)
+def test_reference_gate_passes_every_case_without_hostile_rays_and_stops_the_hostile_ones(kind):
+    """tests/test_gpu_ref_raymarch.py launches the reference's marchers, whose loops have no termination guard, only on inputs for which R.reference_loops_end — the
+    restatement with the product-only guards off — shows every ray to end within TRIP_CAP passes.  Without the hostile rays that holds for every case of
+    GRID_KINDS x GRID_SHAPES x MARCH_PARAMS at 65 rays, so the device test leaves none out.
+    With them, the gate rejects hostile rows and nothing else: the zero direction (row 0: the distance to the next voxel is +inf) and the origin at 1e7 (row 2:
+    t + dt == t) wherever they meet an empty cell — both on an empty grid marched without contraction, neither on a full grid, where they take max_steps samples
+    and end, in the reference too.  The NaN near (row 1) is never rejected: `NaN < far` is false, so the reference's loop ends before its first pass (no sample);
+    it is kept from the reference by hostile=False all the same."""
+    for shape_i in range(len(R.GRID_SHAPES)):
+        for pi in range(len(R.MARCH_PARAMS)):
+            assert R.train_case_loops_end(R.march_train_case(kind, shape_i, pi, 65, False)).all(), (kind, shape_i, pi)
+    for shape_i, pi in ((0, 0), (1, 5), (2, 10), (3, 15), (0, 3), (3, 8)):
+        c = R.march_train_case(kind, shape_i, pi, 65, True)
+        rejected = np.nonzero(~R.train_case_loops_end(c))[0].tolist()
+        assert set(rejected) <= {0, 2} and c["rays"][1, 1] == 0, (kind, shape_i, pi, rejected)
+        if kind == "full":
+            assert rejected == [], (shape_i, pi, rejected)
+        if kind == "empty" and not R.MARCH_PARAMS[pi]["contract"]:
+            assert rejected == [0, 2], (shape_i, pi, rejected)
+
+
+def test_reference_gate_on_the_other_ray_counts_and_the_inference_loop():
+    """The remaining reference launches of tests/test_gpu_ref_raymarch.py pass the gate; the device tests' inference case WITH the hostile rays does not (row 2)."""
+    for N in (1, 63, 64, 2048):
+        for pi in (0, 15):
+            assert R.train_case_loops_end(R.march_train_case("random", 1, pi, N, False)).all()
+    c = R.infer_case(hostile=False)
+    assert all(R.infer_round_loops_end(c, r).all() for r in c["rounds"]) and len(c["rounds"]) >= 4
+    ch = R.infer_case()
+    ends = R.infer_round_loops_end(ch, ch["rounds"][0])
+    assert not ends[2] and ends[R.N_HOSTILE:].all()
+
+
+def test_restatement_equals_what_the_reference_kernels_wrote():
+    """tests/golden/ref_raymarch.npz holds what the reference's own march_rays_train and near_far_from_aabb kernels computed on an MI355X (tests/golden/
+    gen_ref_raymarch.py): samples per ray and a SHA-256 of xyzs / dirs / ts in ray order for every 65-ray case with max_steps 64.  The restatement — which the host
+    build of device_march.hpp and the device kernels are held to bit for bit — must reproduce them; this runs where neither a GPU nor the reference tree exists."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "ref_raymarch.npz"))
+    cases = R.golden_cases()
+    assert np.array_equal(g["cases"], np.array(cases, np.int32)) and len(cases) == 128
+    for i, (k, s, p) in enumerate(cases):
+        c = R.march_train_case(R.GRID_KINDS[k], s, p, 65, False)
+        assert np.array_equal(c["rays"][:, 1], g["counts"][i]), cases[i]
+        for j, name in enumerate(("xyzs", "dirs", "ts")):
+            assert np.array_equal(R.digest(c[name]), g["sha"][i, j]), (cases[i], name)
+    assert g["counts"].sum() > 100000
+    o, d, aabb = R.near_far_inputs()
+    near, far = R.near_far_from_aabb(o, d, aabb, 0.2)
+    assert np.array_equal(R.digest(near), g["near_far_sha"][0]) and np.array_equal(R.digest(far), g["near_far_sha"][1])
+
+
+@pytest.mark.parametrize("T_thresh", [1e-4, 1e-2])
+def test_compositing_inputs_of_the_reference_comparison_stay_clear_of_the_threshold(T_thresh):
+    """tests/test_gpu_ref_raymarch.py compares sample counts exactly except for rays whose float64 transmittance comes within a relative 1e-5 of T_thresh; by the
+    float64 computation alone that leaves out at most 2 % of the rays of each input set."""
+    sets = [R.train_composite_inputs(False) + (False,), R.train_composite_inputs(True) + (True,), R.constant_sigma_rays() + (False,)]
+    for sig, rgb, ts, rays, M, am in sets:
+        near = R.transmittance_near_threshold(sig, ts, rays, T_thresh, am)
+        print("alpha_mode %s, T_thresh %g: %d of %d rays near the threshold" % (am, T_thresh, near.sum(), rays.shape[0]))
+        assert near.sum() <= 0.02 * rays.shape[0]
+
+
+@pytest.mark.parametrize("T_thresh", [1e-4, 1e-2])
+def test_composite_rays_float64_and_its_bound_on_the_stand_alone_sets(T_thresh):
+    """R.composite_rays_sets, the inputs of the device comparison of composite_rays with the reference kernel: by float64 alone at most 2 % of the rays come near
+    T_thresh; away from it the float32 restatement ends the same rays, leaves the same rays_t and stays within composite_rays_float64's derived bound; rays end by
+    opacity, by an empty slot, and go on."""
+    for name, am, n, ns, alive, rays_t, sig, rgb, ts, ws, dp, im in R.composite_rays_sets():
+        acc, stays, t64, near, bound = R.composite_rays_float64(ns, alive, ws, dp, im, sig, rgb, ts, T_thresh, bool(am))
+        assert near.sum() <= 0.02 * n and 0 < stays.sum() < n
+        a2, t2, ws2, dp2, im2 = R.composite_rays(n, ns, alive, rays_t, sig, rgb, ts, ws, dp, im, T_thresh, bool(am))
+        ok = ~near
+        assert np.array_equal(a2[:n][ok] >= 0, stays[ok]) and same(t2[alive][ok & stays], t64[ok & stays].astype(np.float32)) and same(t2[alive][~stays], rays_t[alive][~stays])
+        got = np.stack([im2[alive, 0], im2[alive, 1], im2[alive, 2], ws2[alive], dp2[alive]], 1).astype(np.float64)
+        err = np.abs(got - acc)
+        print("%s, T_thresh %g: %d of %d rays stay; largest error %s, bound %s" % (name, T_thresh, stays.sum(), n, err[ok].max(0), bound[ok].max(0)))
+        assert (err[ok] <= bound[ok]).all() and np.isfinite(bound).all()
+        wider = R.composite_rays_float64(ns, alive, ws, dp, im, sig, rgb, ts, T_thresh, bool(am), exp_ulps=(2.0, 1.0))[4]
+        assert (wider >= bound).all() and ((wider > bound).any() != bool(am))
+        if name != "constant":
+            empty_slot = (ts.reshape(n, ns, 2)[:, :, 0] == 0).any(1)
+            assert empty_slot.sum() > 20 and not stays[empty_slot].any()
+
+
+def test_error_bound_constant_for_another_exponential():
+    """composite_error_bound's exp_ulps: the default is today's constant; a larger or growing error widens the bound, never narrows it."""
+    sig, rgb, ts, rays, M = composite_inputs(33, False, N=16)
+    b2 = R.composite_error_bound(sig, ts, rays, False)
+    assert np.array_equal(b2, R.composite_error_bound(sig, ts, rays, False, exp_ulps=2))
+    b3, b21 = R.composite_error_bound(sig, ts, rays, False, exp_ulps=3), R.composite_error_bound(sig, ts, rays, False, exp_ulps=(2.0, 1.0))
+    live = b2 > 0
+    assert live.sum() >= 10 and (b3[live] > b2[live]).all() and (b21[live] > b2[live]).all() and (b3[~live] == 0).all()
+    assert np.array_equal(R.composite_error_bound(sig, ts, rays, True), R.composite_error_bound(sig, ts, rays, True, exp_ulps=(9.0, 9.0)))      # alpha mode: no exponential
+
+
 # ---------------------------------------------------------------------------------------------------------------- the wrappers' refusals
 def test_wrappers_refuse_bad_arguments_before_touching_a_device():
     from mirres_restir_nerf_mesh_amd import raymarching as RM
