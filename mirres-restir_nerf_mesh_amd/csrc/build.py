@@ -12,7 +12,7 @@ OUT = os.path.join(os.path.dirname(HERE), "libmirres.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the traversal / reservoir decisions must not depend on the compiler's FMA choices (DESIGN.md §FP policy)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable",
+         "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable",
          "-I", os.path.join(HERE, "..", "..", "include")]
 
 # No packed-fp32 VALU code (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32, formed by the SLP and the loop vectoriser) anywhere in the library.
@@ -23,9 +23,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # The flags stay for a measured reason, not a hardware claim: a build WITH packed fp32 is 5-6 % slower on the frame (1014 vs 1070 Msamples/s, round 3), and the
 # hash-grid encoder's two-step fp16 rounding is pinned against contraction choices either way. tests/test_abi.py checks that no object contains v_pk_*_f32.
 # MIRRES_ALLOW_PK=1 (experiments only, with MIRRES_BUILD_TAG): leaves both vectorisers on, i.e. lets packed-fp32 instructions into the kernels again
-PER_FILE = {f: ([] if os.environ.get("MIRRES_ALLOW_PK") == "1" else ["-fno-slp-vectorize", "-fno-vectorize"]) for f in ("passes.hip", "shading.hip", "bvh_trace.hip", "bvh_build.hip", "eaw.hip", "render.hip", "backward.hip", "normal.hip", "matnet.hip", "dump.hip", "raster.hip", "antialias.hip", "selfcheck.hip", "comm.hip", "bake.hip", "texmat.hip", "albedo.hip", "mcubes.hip", "decimate.hip", "density.hip", "raymarch.hip")}
+NO_PK = [] if os.environ.get("MIRRES_ALLOW_PK") == "1" else ["-fno-slp-vectorize", "-fno-vectorize"]
+# Per-file additions: fixed flags, then the environment variable whose words are appended (experiment builds, with MIRRES_BUILD_TAG)
 # matnet.hip: MFMA accumulators in VGPRs (no v_accvgpr_read between the layers of the register-chained MLP: -15 % VALU in k_mlp_mfma)
-PER_FILE["matnet.hip"] += ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+PER_FILE = {"matnet.hip": (["-mllvm", "-amdgpu-mfma-vgpr-form"], "MIRRES_MATNET_FLAGS"),
+            "bvh_trace.hip": ([], "MIRRES_TRACE_FLAGS"),
+            "passes.hip": ([], "MIRRES_PASSES_FLAGS")}
 
 
 def _newer(a, deps):
@@ -52,7 +55,8 @@ def build(force=False, verbose=True):
 
     def cc(job):
         src, obj = job
-        cmd = [HIPCC] + FLAGS + os.environ.get("MIRRES_EXTRA_FLAGS", "").split() + PER_FILE.get(os.path.basename(src), []) + (os.environ.get("MIRRES_MATNET_FLAGS", "").split() if os.path.basename(src) == "matnet.hip" else []) + (os.environ.get("MIRRES_TRACE_FLAGS", "").split() if os.path.basename(src) == "bvh_trace.hip" else []) + (os.environ.get("MIRRES_PASSES_FLAGS", "").split() if os.path.basename(src) == "passes.hip" else []) + ["-c", src, "-o", obj]
+        own, env = PER_FILE.get(os.path.basename(src), ([], ""))
+        cmd = [HIPCC] + FLAGS + os.environ.get("MIRRES_EXTRA_FLAGS", "").split() + NO_PK + own + os.environ.get(env, "").split() + ["-c", src, "-o", obj]
         if verbose:
             print("[mirres build]", os.path.basename(src), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -393,12 +393,9 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_persist(BvhView B, con
 // For an any-hit query `closest` stays t_max until the first accepted triangle, so (1) the reference's result is the OR over all leaves
 // whose OWN box passes the slab test of "triangle_hit accepts": a leaf's ancestors always pass when the leaf does (their boxes are
 // fmin/fmax unions and (b - o) * inv is monotone in b under IEEE rounding), hence (2) any visiting order and any pruning by ancestor
-// boxes yields the same boolean. The stack holds bare 4-byte references in LDS (16 per lane, scratch beyond); no pop-time re-test is needed.
-#ifndef MR_ANY_POOL
-#define MR_ANY_POOL 1      // the per-wave pool of prepared rays (below); 0: the refill of rounds 2-6 (idle lanes form their own rays), threshold MR_REFILL
-#endif
+// boxes yields the same boolean. The stack holds bare 4-byte references in LDS (MR_ANY_LDS per lane, scratch beyond); no pop-time re-test is needed.
 #ifndef MR_ANY_LDS
-#define MR_ANY_LDS (MR_ANY_POOL ? 12 : 16)      // the pool's LDS comes out of the stack's: 12 rows were within 0.5 % of 16 before the pool (profiles/r04_ab_any_lds_stack.txt)
+#define MR_ANY_LDS 12      // rows of the stack kept in LDS. The ray pool's LDS comes out of the stack's: 12 rows measured within 0.5 % of 16 (profiles/r04_ab_any_lds_stack.txt)
 #endif
 // Depth of the shadow-ray kernel's private stack (LDS part + scratch). A 4-wide node defers at most three references and the 4-wide collapse is never
 // deeper than the LBVH it was collapsed from, whose depth is bounded by the bits of the augmented sort key: 30 Morton bits + ceil(log2 T) position bits
@@ -504,16 +501,14 @@ MR_DEV v3 oct_decode_lean(v2 f) {     // oct_decode (device_math.hpp, helperDi.s
     n.y += (n.y >= 0.0f ? -t : t);
     return normalize_lean(n);
 }
-// ---------------------------------------------------------------- the per-wave pool of prepared rays (MR_ANY_POOL)
-// The old refill formed a ray — two dependent gathers for a pixel pair, the normalisation, three reciprocals, the root slab: 145 VALU instructions — in the idle
-// lanes only, 25-30 of 64, about once per five iterations; being that dear it kept the threshold at 40 busy lanes. With the pool ALL 64 lanes, busy ones included
-// (their traversal state stays in registers), each set up one ray of the wave's chunk at full width; the rays that are alive and pass the root box are compacted
-// (ballot + prefix popcount) into an LDS array private to the wave, and an idle lane picks the next entry up with ten LDS reads. Dead rays and root misses never
-// occupy a lane. The arithmetic per ray is the old refill's, expression for expression; only where it runs and which lane walks which ray change.
+// ---------------------------------------------------------------- the per-wave pool of prepared rays
+// Forming a ray — two dependent gathers for a pixel pair, the normalisation, three reciprocals, the root slab — is 145 VALU instructions: too dear to run in the
+// 25-30 idle lanes of a wave only. So ALL 64 lanes, busy ones included (their traversal state stays in registers), each set up one ray of the wave's chunk at full
+// width; the rays that are alive and pass the root box are compacted (ballot + prefix popcount) into an LDS array private to the wave, and an idle lane picks the
+// next entry up with ten LDS reads. Dead rays and root misses never occupy a lane. Which lane walks which ray does not enter any ray's arithmetic.
 // Layout: structure of arrays, pool[field * 64 + entry] — entries are written by consecutive ranks and read by consecutive ranks: no bank conflicts.
-// (MR_ANY_POOL itself is defined above MR_ANY_LDS, whose default depends on it.)
 #ifndef MR_ANY_REFILL
-#define MR_ANY_REFILL (MR_ANY_POOL ? 48 : MR_REFILL)      // the shadow-ray kernel picks rays up while fewer than this many lanes are busy
+#define MR_ANY_REFILL 48      // the shadow-ray kernel picks rays up while fewer than this many lanes are busy (profiles/ray_pool_sweep.txt)
 #endif
 struct PreparedRay { float ox, oy, oz, dx, dy, dz, ix, iy, iz, t_min, t_max; uint32_t idx; };
 // INTERVAL: the entry carries the ray's own [t_min, t_max] (plain ray queues); the pixel-pair source's interval is a constant
@@ -546,7 +541,10 @@ MR_DEV int pool_fill(uint32_t* __restrict__ pool, bool live, const PreparedRay& 
     __builtin_amdgcn_wave_barrier();     // the entries are read by other lanes of this wave: keep the stores ahead of the reads (LDS serves a wave in order)
     return __popcll(lv);
 }
-// Ray `idx` of a shadow-ray queue, set up exactly as the refill of rounds 2-6 did it (SRC, MR_ANY_LEANREFILL: see k_trace_any4q). False: the ray is dead.
+// Ray `idx` of a shadow-ray queue (SRC: see k_trace_any4q). False: the ray is dead.
+// MR_ANY_LEANREFILL: the pixel-pair source forms its own rays (an oct-decoded direction: components are 0 or at least 2^-25 in magnitude, the squared length lies in
+// [1/3, 3]), so every operand of the normalisation and of the three reciprocals is inside the range in which the short sequences return the IEEE bits
+// (device_math.hpp: proved by exhaustion, mirres_selfcheck_arith). Rays that come through the API keep the compiler's division / square root.
 template <int SRC>
 MR_DEV bool prepare_any_ray(const Ray* __restrict__ rays, const RaySrc& src, uint32_t idx, PreparedRay& r) {
     float4 a, b; bool dead = false;
@@ -607,11 +605,9 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                                                                unsigned long long* __restrict__ stats, RaySrc src = RaySrc{nullptr, nullptr, 0.f, 0}) {
     __shared__ uint32_t lds[(MR_ANY_LDS + (MR_ANY_SEL ? 1 : 0)) * MR_TRACE_BLOCK];   // MR_ANY_SEL: one spare row for the last unconditional store of the branch-free child selection
     __shared__ __attribute__((aligned(16))) uint4 s_top[TOPN > 0 ? TOPN * 4 : 1];
-#if MR_ANY_POOL
     __shared__ uint32_t s_pool[pool_dwords<SRC == 0>() * MR_TRACE_BLOCK];
     uint32_t* const pool = s_pool + (threadIdx.x >> 6) * (pool_dwords<SRC == 0>() * 64);   // private to the wave
     int pool_head = 0, pool_n = 0;                                                          // wave-uniform: entries [pool_head, pool_head + pool_n) wait for a lane
-#endif
     if (TOPN > 0) {
         const uint4* src = reinterpret_cast<const uint4*>(TOPN > 85 ? B.top341q : B.top85q);
         for (int i = threadIdx.x; i < TOPN * 4; i += MR_TRACE_BLOCK) s_top[i] = src[i];
@@ -621,7 +617,6 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
     uint32_t* const lds_stack = lds + threadIdx.x;
     const uint32_t n = d_count ? *d_count : n_fixed;
     const int lane = lane_id();
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     uint32_t chunk = n / (gridDim.x * (MR_TRACE_BLOCK / 64) * MR_CHUNK_DIV);
     chunk = chunk < 64 ? 64 : (chunk > MR_CHUNK_MAX ? MR_CHUNK_MAX : (chunk & ~63u));
     const uint32_t q_per = (((n + MR_NQ - 1) / MR_NQ) + 63u) & ~63u;                                  // rays per sub-queue
@@ -638,7 +633,6 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
     unsigned long long c_boxes = 0, c_nodes = 0, c_leaves = 0; int c_maxsp = 0;
     unsigned long long w_iters = 0, w_leaf_iters = 0, w_leaf_lanes = 0;      // COUNT: wave iterations, those that ran the leaf branch, leaf visits (wave-uniform; lane 0 reports)
     while (true) {
-#if MR_ANY_POOL
         // The pool's bookkeeping and the queue state are the same in every lane, but they are carried round a loop that lanes also leave and re-enter under exec
         // masks, and the compiler then keeps them in vector registers and turns every test of them into a vector compare and an exec-mask region.
         // Reading them from the first lane puts them back into scalar registers.
@@ -658,9 +652,6 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
             pool_head += took; pool_n -= took;
         }
         const uint64_t need = __ballot(!have);      // lanes still idle: the pool is empty now
-#else
-        const uint64_t need = __ballot(!have);
-#endif
         if (need && exhausted) {
             // ---- the tail of the launch: the queue is empty and the wave waits for its longest rays. A shadow ray's answer is an OR over subtrees, so
             // a lane with deferred entries hands its OLDEST one (the bottom of its stack: usually the largest subtree) to an idle lane, which searches
@@ -668,11 +659,7 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
             const uint64_t donors = __ballot(have && sp > sbase && sbase < MR_ANY_LDS);
             if (donors) {
                 const int nd = __popcll(donors), ni = __popcll(need);
-#if MR_ANY_POOL
                 const int my_idle = rank_below(need), my_don = rank_below(donors);
-#else
-                const int my_idle = __popcll(need & lt_mask), my_don = __popcll(donors & lt_mask);
-#endif
                 const bool take = !have && my_idle < nd;
                 const bool give = have && sp > sbase && sbase < MR_ANY_LDS && my_don < ni;
                 uint64_t m = donors;
@@ -695,11 +682,8 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
             }
         }
         if (need && !exhausted) {
-#if MR_ANY_POOL
             chunk_next = __builtin_amdgcn_readfirstlane(chunk_next); chunk_end = __builtin_amdgcn_readfirstlane(chunk_end);
-#endif
             if (chunk_next >= chunk_end) exhausted = !grab_chunk(work_head, n, q_per, chunk, q_cur, q_fail, q_known, chunk_next, chunk_end, lane);
-#if MR_ANY_POOL
             if (!exhausted) {
                 // ---- prepare: the pool is empty (the idle lanes have just drained it) and the chunk has rays left. Every lane, busy or not, sets up one ray
                 // (the lanes past the end of a sub-queue's last chunk repeat its last ray and drop it: no divergent region around the set-up, whose
@@ -717,53 +701,6 @@ __global__ void __launch_bounds__(MR_TRACE_BLOCK) k_trace_any4q(BvhView B, const
                 chunk_next = (chunk_next + 64u < chunk_end) ? chunk_next + 64u : chunk_end;
                 continue;      // back to the pick-up (or, when none of the 64 was live, to the next 64)
             }
-#else
-            if (!exhausted) {
-                const uint32_t idx0 = chunk_next + (uint32_t)__popcll(need & lt_mask);
-                const uint32_t idx = idx0;
-                if (!have && idx0 < chunk_end) {
-                    float4 a, b; bool dead = false;
-                    if (SRC == 1) {
-                        const uint2 it = reinterpret_cast<const uint2*>(rays)[idx >> 1];      // pair (a, b): even ray a -> b's light, odd ray b -> a's light
-                        const uint32_t op = (idx & 1u) ? it.y : it.x, lp = (idx & 1u) ? it.x : it.y;
-                        const float4 P = src.grec[4 * (size_t)op + 3], L = src.rrec[2 * (size_t)lp];
-                        dead = src.skip_dead && L.w == 0.f;   // engine.hpp RaySrc: the light sample's carried luminance is 0 — nobody can see this ray's answer
-#if MR_ANY_LEANREFILL
-                        const v3 dir = oct_decode_lean(V2(L.y, L.z));
-#else
-                        const v3 dir = oct_decode(V2(L.y, L.z));
-#endif
-                        v3 o = V3(P.x, P.y, P.z) + src.vis_near * dir;          // put_ray (passes.hip): the same two expressions
-                        a.x = o.x; a.y = o.y; a.z = o.z; a.w = 0.f; b.x = dir.x; b.y = dir.y; b.z = dir.z; b.w = 1e7f;
-                    } else { a = reinterpret_cast<const float4*>(rays + idx)[0]; b = reinterpret_cast<const float4*>(rays + idx)[1]; }
-                    ridx = idx; ro = V3(a.x, a.y, a.z); t_min = a.w; t_max = b.w;
-#if MR_ANY_LEANREFILL
-                    // Round 6: the pixel-pair source forms its own rays (an oct-decoded direction: components are 0 or at least 2^-25 in magnitude, the squared length lies in
-                    // [1/3, 3]), so every operand of the normalisation and of the three reciprocals is inside the range in which the short sequences return the IEEE bits
-                    // (device_math.hpp: proved by exhaustion, mirres_selfcheck_arith). Rays that come through the API keep the compiler's division / square root.
-                    if (SRC == 1) d = normalize_lean(V3(b.x, b.y, b.z)); else d = normalize(V3(b.x, b.y, b.z));
-#else
-                    d = normalize(V3(b.x, b.y, b.z));
-#endif
-                    ox = ro.x; oy = ro.y; oz = ro.z;
-                    { float dx = d.x, dy = d.y, dz = d.z;
-                      if (dx == 0.f) dx = 0.000001f; if (dy == 0.f) dy = 0.000001f; if (dz == 0.f) dz = 0.000001f;
-#if MR_ANY_LEANREFILL
-                      if (SRC == 1) { ix = lean_rcp(dx); iy = lean_rcp(dy); iz = lean_rcp(dz); } else
-#endif
-                      { ix = 1.0f / dx; iy = 1.0f / dy; iz = 1.0f / dz; } }
-                    sp = 0; sbase = 0;
-                    rc = ray_margins(scene_bs, ox, oy, oz, ix, iy, iz);
-                    hit_out[idx] = 0;          // set to 1 by whichever lane finds an occluder (the owner or, in the tail, a helper)
-                    const float o3[3] = {ox, oy, oz}, i3[3] = {ix, iy, iz};
-                    Slab s0 = slab(B.root_box, B.root_box + 3, o3, i3, t_min);
-                    if (COUNT) c_boxes++;
-                    if (!dead && s0.tf > s0.tn && t_max > s0.tn) { cur = TOPN > 0 ? MR_TOPBIT : 0; have = true; }
-                }
-                const uint32_t want = (uint32_t)__popcll(need);
-                chunk_next = (chunk_next + want < chunk_end) ? chunk_next + want : chunk_end;
-            }
-#endif
         }
         if (!__ballot(have)) { if (exhausted) break; else continue; }
         do {
@@ -1201,7 +1138,7 @@ static int any_top() {
     static const int topq = [] { const char* e = getenv("MIRRES_TOPQ"); const int v = e ? atoi(e) : 0; return (v == 85 || v == 341) ? v : 0; }();
     return topq;
 }
-// the spatial pass's queue of (origin pixel, light pixel) pairs: same kernel, rays formed at the refill. head_set: a unit of the band pipeline (HS_CHAIN_ANY, HS_BAND1,
+// the spatial pass's queue of (origin pixel, light pixel) pairs: same kernel, rays formed where the pool is filled (prepare_any_ray). head_set: a unit of the band pipeline (HS_CHAIN_ANY, HS_BAND1,
 // HS_BAND2); < 0: the lane's own
 int trace_any_items_queue(const mirres_bvh* bvh, const uint2* items, const RaySrc& src, const uint32_t* d_count, size_t capacity, int32_t* hit,
                           unsigned long long* stats, hipStream_t s, int lane, int timed, bool heads_clean, int head_set) {

@@ -119,11 +119,7 @@ MR_DEV void gather_cell(const __half2* __restrict__ g, const uint32_t ci[8], boo
 #pragma unroll
     for (int c = 0; c < 8; c += 2) {
         const uint32_t i0 = ci[c], i1 = ci[c + 1];
-#ifndef MR_PAIR_MODE
-#define MR_PAIR_MODE 3
-#endif
-        if ((hashed && !(MR_PAIR_MODE & 2)) || (!hashed && !(MR_PAIR_MODE & 1))) { v[c] = g[i0]; v[c + 1] = g[i1]; }
-        else if (hashed) {
+        if (hashed) {
             const uint2 pr = *reinterpret_cast<const uint2*>(g + (i0 & ~1u));
             const bool odd = (i0 & 1u) != 0u;
             v[c] = as_half2(odd ? pr.y : pr.x);

@@ -28,6 +28,10 @@ static_assert(HS_BAND2 < MR_WSETS && HS_FAST2 + 2 < HS_PT2_ANY && HS_FAST + 2 < 
 // MR_SAH_LEVELS levels rebuilt above them. The shadow-ray kernel's private stack (bvh_trace.hip MR_ANY_STACK) is sized from these two.
 #define MR_SAH_PREFIX 24
 #define MR_SAH_LEVELS 40
+// Block size of the ray-generating kernels k_new_dir_gen, k_bounce_gen (shading.hip) and k_vis_gen (passes.hip); how it was picked: passes.hip
+#ifndef MR_GEN_BLOCK
+#define MR_GEN_BLOCK 512    // ray-generating kernels: one queue atomic per block
+#endif
 
 namespace mr {
 

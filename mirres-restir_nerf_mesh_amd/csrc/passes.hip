@@ -23,9 +23,7 @@ int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32
 // only when a CU has room for ALL its waves: with 1024 threads (four waves per SIMD per block) a CU held ONE block — four of the six possible waves,
 // and nothing at all beside another stream's block. 512 / 256 threads fill the six: k_initial_gen 10.3 -> 7.3 ms per 32-sample batch, k_bounce_gen
 // 4.9 -> 4.0 ms, frame 974 -> 1029 Msamples/s (round 2; per-kernel sizes picked on the frame: 256 / 512 / 512).
-#ifndef MR_GEN_BLOCK
-#define MR_GEN_BLOCK 512    // ray-generating kernels: one queue atomic per block
-#endif
+// MR_GEN_BLOCK (k_vis_gen here, the generators of shading.hip): engine.hpp
 #ifndef MR_IGEN_BLOCK
 #define MR_IGEN_BLOCK 256
 #endif
@@ -36,9 +34,6 @@ int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32
 
 // 2-D tile -> pixel mapping for the kernels that gather from neighbouring pixels (spatial pass: +-30 px): a square tile of threads touches a
 // (T+60)^2 window instead of the (blockDim+60) x 61 strip a row-major block touches, which is what the L1/L2 hit rate of the gathers follows.
-#ifndef MR_TILE_MAP
-#define MR_TILE_MAP 2
-#endif
 #ifndef MR_CHUNK_PX
 #define MR_CHUNK_PX 128
 #endif
@@ -46,36 +41,21 @@ int trace_any_queue_counted(const mirres_bvh* bvh, const Ray* rays, const uint32
 #define MR_SRES_TILE 8      // one wave per workgroup. 16 (rounds 2-4) was the better shape while the kernel held 140 registers without the fused temporal merge; at 159 (three waves
                             // per SIMD) the finer granularity wins: +2.2 % (icosphere) / +0.7 % (lego-like) on the frame (profiles/r04_ab_spatial_shapes.txt)
 #endif
-// MR_TILE_MAP 0: row-major tiles. 1: eight contiguous bands of tile rows, one per XCD. 2: 128 x 128 px chunks of tiles dealt to the XCDs in turn.
+// MR_CHUNK_PX x MR_CHUNK_PX px chunks of tiles are dealt to the XCDs in turn.
 // (Workgroups go to the eight XCDs round-robin by block index and every XCD has its own L2.)
 MR_DEV int tile_pixel(int fx, int fy, int tw, int N) {
     const int tiles_x = (fx + tw - 1) / tw, tiles_y = (fy + tw - 1) / tw;
-    int tx, ty;
-#if MR_TILE_MAP == 0
-    tx = blockIdx.x % tiles_x; ty = blockIdx.x / tiles_x;
-#elif MR_TILE_MAP == 1
-    const int t = (int)(blockIdx.x & 7u) * ((tiles_x * tiles_y + 7) >> 3) + (int)(blockIdx.x >> 3);
-    if (t >= tiles_x * tiles_y) return N;
-    tx = t % tiles_x; ty = t / tiles_x;
-#else
     const int ch = MR_CHUNK_PX / tw, chunks_x = (tiles_x + ch - 1) / ch;
     const int j = (int)(blockIdx.x >> 3), chunk = (int)(blockIdx.x & 7u) + 8 * (j / (ch * ch)), w = j % (ch * ch);
-    tx = (chunk % chunks_x) * ch + w % ch; ty = (chunk / chunks_x) * ch + w / ch;
+    const int tx = (chunk % chunks_x) * ch + w % ch, ty = (chunk / chunks_x) * ch + w / ch;
     if (tx >= tiles_x || ty >= tiles_y) return N;
-#endif
     const int x = tx * tw + (int)(threadIdx.x % tw), y = ty * tw + (int)(threadIdx.x / tw);
     return (x < fx && y < fy) ? y * fx + x : N;   // N = "no pixel"
 }
 static int tile_grid(int fx, int fy, int tw) {
     const int tiles_x = (fx + tw - 1) / tw, tiles_y = (fy + tw - 1) / tw;
-#if MR_TILE_MAP == 0
-    return tiles_x * tiles_y;
-#elif MR_TILE_MAP == 1
-    return 8 * ((tiles_x * tiles_y + 7) / 8);
-#else
     const int ch = MR_CHUNK_PX / tw, chunks = ((tiles_x + ch - 1) / ch) * ((tiles_y + ch - 1) / ch);
     return 8 * ((chunks + 7) / 8) * ch * ch;
-#endif
 }
 
 // G-buffer / reservoir views. The ABI layout is the reference's SoA (one array per field). mirres_render's internal buffers use packed records so
@@ -444,19 +424,10 @@ MR_DEV float pairwise_mis(float q0, float q1, float N0, float N1) { return (q1 =
 #endif
 MR_DEV int tile_pixel_v(int fx, int fy, int tw, int N, int vt) {   // tile_pixel for a virtual thread index vt in [0, tw * tw)
     const int tiles_x = (fx + tw - 1) / tw, tiles_y = (fy + tw - 1) / tw;
-    int tx, ty;
-#if MR_TILE_MAP == 0
-    tx = blockIdx.x % tiles_x; ty = blockIdx.x / tiles_x;
-#elif MR_TILE_MAP == 1
-    const int t = (int)(blockIdx.x & 7u) * ((tiles_x * tiles_y + 7) >> 3) + (int)(blockIdx.x >> 3);
-    if (t >= tiles_x * tiles_y) return N;
-    tx = t % tiles_x; ty = t / tiles_x;
-#else
     const int ch = MR_CHUNK_PX / tw, chunks_x = (tiles_x + ch - 1) / ch;
     const int j = (int)(blockIdx.x >> 3), chunk = (int)(blockIdx.x & 7u) + 8 * (j / (ch * ch)), w = j % (ch * ch);
-    tx = (chunk % chunks_x) * ch + w % ch; ty = (chunk / chunks_x) * ch + w / ch;
+    const int tx = (chunk % chunks_x) * ch + w % ch, ty = (chunk / chunks_x) * ch + w / ch;
     if (tx >= tiles_x || ty >= tiles_y) return N;
-#endif
     const int x = tx * tw + (vt % tw), y = ty * tw + (vt / tw);
     return (x < fx && y < fy) ? y * fx + x : N;   // N = "no pixel"
 }
@@ -573,17 +544,6 @@ __global__ void __launch_bounds__(MR_SGEN_BLOCK / MR_SGEN_PX) k_spatial_gen(mirr
     }
 }
 
-#ifndef MR_SRES_HIT2
-#define MR_SRES_HIT2 1
-#endif
-#ifndef MR_SRES_WAVES
-#define MR_SRES_WAVES 0      // experiment: waves per SIMD the register allocator must make room for (0 = its own choice: 140 VGPRs, three waves)
-#endif
-#if MR_SRES_WAVES
-#define MR_SRES_ATTR __attribute__((amdgpu_waves_per_eu(MR_SRES_WAVES, MR_SRES_WAVES)))
-#else
-#define MR_SRES_ATTR
-#endif
 // the spatial merge of ONE pixel (SpatialResampling.slang:200-322) from the generator's acceptance mask and the traced hit bits; false: the pixel is background (or,
 // under strip sharding, not this rank's): its output reservoir is empty
 template <int MR_MAX_NB>
@@ -628,12 +588,9 @@ MR_DEV bool spatial_pixel(const mirres_config_t& C, const EnvD& E, const GBufD& 
         ++validNeighbors;
         const v3 ndir = oct_decode(V2(nbr.light_data.y, nbr.light_data.z));
         const float nlum = sample_lum(E, nbr, ndir);
-#if MR_SRES_HIT2   // the two answers of a pair are neighbours in the hit array and a pixel's first slot is even: one 8-byte load instead of two 4-byte ones
+        // the two answers of a pair are neighbours in the hit array and a pixel's first slot is even: one 8-byte load instead of two 4-byte ones
         const int2 hh = reinterpret_cast<const int2*>(hit)[hs >> 1];
         const float canonicalVis = hh.x ? 0.f : 1.f, candidateVis = hh.y ? 0.f : 1.f;
-#else
-        const float canonicalVis = hit[hs] ? 0.f : 1.f, candidateVis = hit[hs + 1] ? 0.f : 1.f;
-#endif
         hs += 2;
         // streamingResampleStepMisUnbiased (res.slang:173-213)
         float candTarget = target_lum(nctx, nlum, ndir);
@@ -671,7 +628,7 @@ MR_DEV ResV stored_res(const Ris& s, bool fg) {
 // re-read, no launch) or, when (float)x + u rounds up (a few hundred pixels of a 1600 x 1600 frame per sample), its right / lower neighbour, whose spatial merge this
 // thread then recomputes from the same inputs (the neighbour's own thread may not have stored it yet). NR = the next sample's initial reservoirs, merged in place.
 template <int MR_MAX_NB, bool FUSE>
-__global__ void MR_SRES_ATTR __launch_bounds__(MR_SRES_TILE * MR_SRES_TILE) k_spatial_resolve(mirres_config_t C, EnvD E, GBufD G, ResD R, ResD PR, const float* __restrict__ noff,
+__global__ void __launch_bounds__(MR_SRES_TILE * MR_SRES_TILE) k_spatial_resolve(mirres_config_t C, EnvD E, GBufD G, ResD R, ResD PR, const float* __restrict__ noff,
                                                               uint32_t frameIndex, int fx, int fy, int N, int y_off, const float* __restrict__ occ_own,
                                                               const int32_t* __restrict__ slot, const uint32_t* __restrict__ mask_in, const int32_t* __restrict__ hit,
                                                               uint32_t* __restrict__ reset_counter, uint32_t* __restrict__ reset_heads, ResD NR, uint32_t next_frame, RowSet rows,

@@ -19,9 +19,6 @@ int trace_closest_queue_counted(const mirres_bvh* bvh, const Ray* rays, const ui
                                 unsigned long long* stats, hipStream_t s, int32_t* prim);
 
 #define MR_BLOCK 256
-#ifndef MR_GEN_BLOCK
-#define MR_GEN_BLOCK 512    // ray-generating kernels: one queue atomic per block
-#endif
 #ifndef MR_BGEN_BLOCK
 #define MR_BGEN_BLOCK MR_GEN_BLOCK
 #endif
@@ -159,9 +156,6 @@ __global__ void __launch_bounds__(MR_BLOCK) k_new_dir_resolve(mirres_path_t P, i
 }
 
 // ---------------------------------------------------------------- process_path_tracing_divided_no_grad (FinalShading.slang:641-1009)
-#ifdef MR_BGEN_WAVES
-__attribute__((amdgpu_waves_per_eu(MR_BGEN_WAVES, MR_BGEN_WAVES)))
-#endif
 __global__ void __launch_bounds__(MR_BGEN_BLOCK) k_bounce_gen(mirres_path_t P, EnvD E, int max_bounce, float vis_near, uint32_t frameIndex, uint32_t bounce_count,
                                                          int fx, int N, int NV, int first_is_zero, int y_off, int sparse, float* __restrict__ color, float* __restrict__ diff_color, float* __restrict__ spec_color,
                                                          Ray* __restrict__ qa, uint32_t* __restrict__ qa_count, Ray* __restrict__ qc, uint32_t* __restrict__ qc_count,

@@ -1,4 +1,4 @@
-"""GPU: the shadow-ray kernel's per-wave pool of prepared rays (bvh_trace.hip, MR_ANY_POOL). The pool changes which lane walks which ray and where a ray
+"""GPU: the shadow-ray kernel's per-wave pool of prepared rays (bvh_trace.hip, pool_fill / pool_get). The pool changes which lane walks which ray and where a ray
 is set up, never a ray's answer: the production any-hit (mirres_bvh_trace mode 0) is compared hit for hit with the reference-order kernel (mode 1) on ray
 counts around every edge of the chunk / sub-queue / pool arithmetic and on ray sets that leave the pool empty, nearly empty, or drained every iteration;
 the pixel-pair source is checked through whole small frames against the CPU oracle."""
