@@ -131,6 +131,10 @@ struct ChainSet {
     mr::Ray* q = nullptr; int32_t* hit = nullptr; uint32_t* counter = nullptr; int32_t* slot = nullptr; uint32_t* mask = nullptr;
     int head_set = HS_CHAIN_ANY; bool clean = false;      // clean: the set's last resolve left the ray counter and the work heads zeroed
 };
+// Neighbour acceptance of one sample, made ahead of the chain by the batched k_spatial_accept (passes.hip; MIRRES_SPATIAL_PREGEN): what k_spatial_gen would have
+// left in the queue set, in the batch pool. The sample's spatial pass is then the traversal launch on `q` / `counter` and the resolve on `slot` / `mask`.
+#define MR_PRE_CSTRIDE 32   // words between the ray counters of consecutive samples: one 128-byte line each (the samples' appends run side by side)
+struct SpatialPre { const mr::Ray* q; uint32_t* counter; const int32_t* slot; const uint32_t* mask; };
 struct SpatialBand { int y0, y1, gen_y1; };   // the resolve covers rows [y0, y1), the generator [y0, gen_y1) (one more row: the fused temporal merge of the band's
                                               // last row may recompute the spatial merge of the pixel below, whose rays must be in THIS unit's queue); {0, fy, fy}: the frame
 struct FrameView {   // what is constant for one mirres_render call and its launches need, passed to them as an argument; the stepwise ABI passes a default-constructed one
@@ -175,6 +179,8 @@ struct mirres_ctx {
     // event per unit of a batch. `clean` is never set here: a frame works on copies of its own, so nothing it learns outlives it
     ChainSet chain_sets[3]; void* chain_mem[2] = {nullptr, nullptr}; hipStream_t chain_streams[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev_band;
+    // mirres_debug_spatial_pregen: whether the last frame's chain ran on pre-generated acceptance, and the ray counters of its first batch (copied when they were complete)
+    int pregen_last = 0, pregen_k = 0; uint32_t* pregen_counts = nullptr;   // [64 * MR_PRE_CSTRIDE] device, allocated on first use
     // per-ray triangle ids of the continuation rays (PtQueues::cl_prim): allocated on the first textured frame or mirres_path_t::new_prim request, never for a material field
     int32_t* ray_prim = nullptr; size_t ray_prim_cap = 0;
 };
@@ -208,6 +214,8 @@ inline int knob_pt_batch() { const char* e = getenv("MIRRES_PT_BATCH"); const in
 inline int knob_streams() { const char* e = getenv("MIRRES_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 5 ? 5 : n); }   // streams of a frame, 1..5: 2 (profiles/r04_ab_gs_bits.txt)
 inline int knob_bands() { const char* e = getenv("MIRRES_BANDS"); return e ? atoi(e) : 1; }   // bands of the chain's band pipeline: 1 = off (profiles/r06_ab_bands.txt)
 inline int knob_chain_streams() { const char* e = getenv("MIRRES_CHAIN_STREAMS"); const int n = e ? atoi(e) : 2; return n < 1 ? 1 : (n > 3 ? 3 : n); }   // chain streams of the band pipeline, 1..3: 2 (profiles/r06_ab_bands.txt)
+inline bool knob_spatial_pregen() { const char* e = getenv("MIRRES_SPATIAL_PREGEN"); return !(e && e[0] == '0'); }   // neighbour acceptance per batch, off the chain: on; 0 = k_spatial_gen in the chain (profiles/spatial_pregen_ab.txt)
+inline int knob_pregen_spt(int K) { const char* e = getenv("MIRRES_PREGEN_SPT"); const int n = e ? atoi(e) : K; return n < 1 ? 1 : (n > K ? K : n); }   // samples per thread of k_spatial_accept, 1..K: K, a thread owns one pixel for the whole batch (profiles/spatial_pregen_ab.txt)
 inline size_t knob_pool_limit() { const char* e = getenv("MIRRES_POOL_LIMIT_MB"); return e ? (size_t)atoll(e) << 20 : 0; }   // largest batch pool in bytes, 0 = no limit (a test switch: no profile)
 inline int knob_min_batches() { const char* e = getenv("MIRRES_MIN_BATCHES"); return e ? (atoi(e) > 0 ? atoi(e) : 1) : 0; }   // batches per frame at least; 0 = unset, choose_k's rule (profiles/r06_ab_train_batch.txt)
 inline bool knob_dbg_sum() { return getenv("MIRRES_DBG_SUM") != nullptr; }   // per-stage checksums on stderr (development aid: no profile)
@@ -259,7 +267,11 @@ int launch_temporal(mirres_ctx* ctx, const FrameView& fv, const mirres_env_t* en
 // the spatial pass of rows `band` (further restricted by `rows`) on the queue set `set`
 int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainSet& set, const SpatialBand& band, const RowSet& rows, const mirres_env_t* env,
                    const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res, const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s,
-                   const mirres_res_t* next_res, uint32_t next_frame);
+                   const mirres_res_t* next_res, uint32_t next_frame, const SpatialPre* pre = nullptr);
+// neighbour acceptance of the K samples of a batch in one launch (whole frame, pixel-pair queue): sample k's pairs at q + k * q_stride (pairs), its ray counter at
+// counters[k * MR_PRE_CSTRIDE], its slots / masks at slot[k * N], mask[k * N]. frame0 = the first sample's frame index; that sample has no temporal pass (pass index 3) iff first_is_zero
+int launch_spatial_accept(mirres_ctx* ctx, const FrameView& fv, int K, uint32_t frame0, uint32_t frame_step, bool first_is_zero, uint2* q, size_t q_stride, uint32_t* counters,
+                          int32_t* slot, uint32_t* mask, hipStream_t s);
 int comm_exchange_halos(void* comm, float* rec, int fx, int n, const int* peer, const int* s0, const int* s1, const int* r0, const int* r1, hipStream_t s);   // comm.hip
 int trace_any_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, int32_t* hit, hipStream_t s, int lane = 0, bool heads_clean = false);   // heads_clean: ChainSet::clean of the set the launch works on, never guessed
 int trace_closest_q(mirres_ctx* ctx, mirres_bvh* bvh, const Ray* rays, const uint32_t* count, size_t cap, HitRec* out, hipStream_t s, int lane = 0, int32_t* prim = nullptr);

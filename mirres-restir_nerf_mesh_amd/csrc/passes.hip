@@ -544,6 +544,71 @@ __global__ void __launch_bounds__(MR_SGEN_BLOCK / MR_SGEN_PX) k_spatial_gen(mirr
     }
 }
 
+// The acceptance of k_spatial_gen<., true> for the K samples of a batch in ONE launch, off the per-sample chain (mirres_render, whole frames; MIRRES_SPATIAL_PREGEN).
+// Of the four tests, in bounds / normal and depth similar / neighbour is foreground depend on the G-buffer, the offset table and the pixel's RNG stream alone, all known
+// when the batch starts; only "neighbour reservoir M != 0" reads the previous sample's output. That one test moves into the merge (spatial_pixel): all four precede any
+// draw, so their order among themselves cannot change a bit. A pair whose neighbour turns out to hold M == 0 keeps its two ray slots and is skipped by the merge.
+// blockIdx.y * spt .. + spt = the samples of this block (the pixel's own record is loaded once for them); per sample one block_append on that sample's counter.
+// A sample's queue segment holds min(neighbor_count, MR_MAX_NB) pairs for every pixel of the frame: it cannot overflow.
+template <int MR_MAX_NB>
+__global__ void __launch_bounds__(MR_SGEN_BLOCK) k_spatial_accept(mirres_config_t C, const float4* __restrict__ grec, const float* __restrict__ noff, uint32_t frame0, uint32_t frame_step,
+                                                                  int first_is_zero, int fx, int fy, int N, int y_off, const float* __restrict__ occ_own, uint2* __restrict__ q,
+                                                                  size_t q_stride, uint32_t* __restrict__ counters, int32_t* __restrict__ slot_out, uint32_t* __restrict__ mask_out,
+                                                                  int K, int spt) {
+    const int k = min(C.neighbor_count, MR_MAX_NB);
+    const int pi = tile_pixel_v(fx, fy, MR_SGEN_TILE, N, (int)threadIdx.x);
+    float4 own = make_float4(0.f, 0.f, 0.f, 0.f); float occ = 0.f;
+    if (pi < N) { own = grec[4 * (size_t)pi]; occ = occ_own ? occ_own[pi] : grec[4 * (size_t)pi + 1].w; }
+    const bool fg = pi < N && !(occ < 0.1f);
+    const int x = pi % fx, y = pi / fx;
+    const v3 n = V3(own.x, own.y, own.z); const float depth = own.w;
+    const int k0 = (int)blockIdx.y * spt, k1 = min(K, k0 + spt);
+    for (int sk = k0; sk < k1; sk++) {      // uniform over the block (block_append synchronises it)
+        uint32_t mask = 0, cnt = 0;
+        int nb[MR_MAX_NB];
+#pragma unroll
+        for (int i = 0; i < MR_MAX_NB; i++) nb[i] = -1;
+        if (fg) {
+            const uint32_t frameIndex = frame0 + frame_step * (uint32_t)sk + ((sk == 0 && first_is_zero) ? 3u : 4u);
+            uint32_t sg = seed_generator((uint32_t)x, (uint32_t)(y + y_off), frameIndex);
+            const uint32_t startIndex = (uint32_t)(rnd(sg) * C.neighbor_offset_count);
+            float4 nd[MR_MAX_NB]; float nocc[MR_MAX_NB];
+#pragma unroll
+            for (int i = 0; i < MR_MAX_NB; i++) {
+                if (i < k) {
+                    const uint32_t ni = (startIndex + (uint32_t)i) & (uint32_t)(C.neighbor_offset_count - 1);
+                    const int nx = x + (int)(noff[2 * ni] * C.gather_radius), ny = y + (int)(noff[2 * ni + 1] * C.gather_radius);
+                    if (nx >= 0 && ny >= 0 && nx < fx && ny < fy) nb[i] = ny * fx + nx;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < MR_MAX_NB; i++) if (nb[i] >= 0) { nd[i] = grec[4 * (size_t)nb[i]]; nocc[i] = grec[4 * (size_t)nb[i] + 1].w; }
+#pragma unroll
+            for (int i = 0; i < MR_MAX_NB; i++) {
+                bool ok = nb[i] >= 0;
+                if (ok) {
+                    const v3 nn = V3(nd[i].x, nd[i].y, nd[i].z);
+                    ok = dot(n, nn) >= 0.5f && fabsf(depth - nd[i].w) <= 0.1f * depth;   // isValidNeighbor (res.slang:63-68)
+                    ok = ok && !(nocc[i] < 0.1f);
+                }
+                if (ok) { mask |= 1u << i; cnt++; } else nb[i] = -1;
+            }
+        }
+        const uint32_t s = block_append(counters + (size_t)sk * MR_PRE_CSTRIDE, cnt > 0, 2 * cnt);
+        if (pi < N) {
+            const size_t sv = (size_t)sk * (size_t)N + (size_t)pi;
+            slot_out[sv] = mask ? (int32_t)s : -1;
+            mask_out[sv] = mask;
+            if (mask) {
+                uint2* const qi = q + (size_t)sk * q_stride + (s >> 1);     // s is even: one pair per two rays
+                int j = 0;
+#pragma unroll
+                for (int i = 0; i < MR_MAX_NB; i++) if (mask & (1u << i)) qi[j++] = make_uint2((uint32_t)pi, (uint32_t)nb[i]);
+            }
+        }
+    }
+}
+
 // the spatial merge of ONE pixel (SpatialResampling.slang:200-322) from the generator's acceptance mask and the traced hit bits; false: the pixel is background (or,
 // under strip sharding, not this rank's): its output reservoir is empty
 template <int MR_MAX_NB>
@@ -584,6 +649,9 @@ MR_DEV bool spatial_pixel(const mirres_config_t& C, const EnvD& E, const GBufD& 
         if (!((uint32_t)i < k && (mask & (1u << i)))) continue;
         const v3 nn = gnb[i].n;
         const ResV nbr = rnb[i];
+        // the reference's third test (:236-258), "neighbour reservoir M != 0": k_spatial_gen has made it already (its masks never show such a neighbour);
+        // k_spatial_accept cannot, so the pair has its ray slots and is passed over here — no draw, no count, as if the mask had not named it
+        if (nbr.M == 0) { hs += 2; continue; }
         const rtarget::Ctx nctx = rtarget::make_ctx(nn, gnb[i].rd, gnb[i].brdf);
         ++validNeighbors;
         const v3 ndir = oct_decode(V2(nbr.light_data.y, nbr.light_data.z));
@@ -852,14 +920,14 @@ int launch_temporal(mirres_ctx* ctx, const FrameView& fv, const mirres_env_t* en
 // spatial pass; next_res != NULL (mirres_render's chain, packed reservoirs): the temporal merge of the next sample is fused into the resolve kernel (k_spatial_resolve<., true>)
 int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainSet& set, const SpatialBand& band, const RowSet& rows, const mirres_env_t* env,
                    const mirres_gbuf_t* g, const mirres_res_t* res, const mirres_res_t* prev_res, const float* neighbor_offsets, uint32_t frameIndex, hipStream_t s,
-                   const mirres_res_t* next_res, uint32_t next_frame) {
+                   const mirres_res_t* next_res, uint32_t next_frame, const SpatialPre* pre) {
     if (!ctx || !bvh || !env || !g || !res || !prev_res) { set_error("mirres_restir_spatial: null"); return MIRRES_E_ARG; }
     const int N = (int)ctx->N;
     const float* noff = neighbor_offsets ? neighbor_offsets : ctx->noff;
     // the pass works on rows [y0, y1) with the queue, hit bits, per-pixel slots and work heads of `set` (a unit of the band pipeline, render.hip: its chain stream's set)
     const int by0 = band.y0, gen_rows = band.gen_y1 - band.y0, res_rows = band.y1 - band.y0;
     const bool clean = fv.fold && set.clean;                    // inside mirres_render's chain (its own stream, its own work heads): the set's last resolve zeroed them
-    if (!clean) MR_HIP(hipMemsetAsync(set.counter, 0, sizeof(uint32_t), s));
+    if (!clean && !pre) MR_HIP(hipMemsetAsync(set.counter, 0, sizeof(uint32_t), s));
     uint32_t* const rc_ = fv.fold ? set.counter : nullptr; uint32_t* const rh_ = fv.fold ? bvh->work + (size_t)set.head_set * MR_WSET : nullptr;
     const bool nb5 = ctx->cfg.neighbor_count <= 5;
     // mirres_render's chain (packed pixel records + packed reservoirs, no per-ray counters wanted): the queue carries pixel pairs and the traversal kernel forms the rays
@@ -870,7 +938,10 @@ int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainS
     unsigned long long* const mark_dead = (skip_dead && fv.grec && resd(prev_res).rec && (ctx->instrument & 1) && !(ctx->instrument & 4)) ? &ctx->stats[12] : nullptr;
     const dim3 sg_grid(tile_grid(ctx->fx, gen_rows, MR_SGEN_TILE)), sg_block(MR_SGEN_BLOCK / MR_SGEN_PX);
 #define MR_SGEN_ARGS ctx->cfg, gbufd(g), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, set.q, set.counter, set.slot, set.mask, rows, mark_dead, by0, gen_rows
-    if (nb5 && items) k_spatial_gen<5, true><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
+    // pre (mirres_render's chain, whole frames): k_spatial_accept has left this sample's pairs, counter, slots and masks in the batch pool; the pass is trace + resolve
+    if (pre && !(items && rows.mode == 0 && by0 == 0 && gen_rows == ctx->fy && res_rows == ctx->fy)) { set_error("mirres_render: pre-generated acceptance needs the pixel-pair queue and whole frames"); return MIRRES_E_STATE; }
+    if (pre) {}     // no generator launch
+    else if (nb5 && items) k_spatial_gen<5, true><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else if (nb5) k_spatial_gen<5><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else if (items) k_spatial_gen<8, true><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
     else k_spatial_gen<8><<<sg_grid, sg_block, 0, s>>>(MR_SGEN_ARGS);
@@ -879,14 +950,16 @@ int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainS
     const size_t cap = std::min(ctx->any_cap, (size_t)gen_rows * ctx->fx * (size_t)(2 * (ctx->cfg.neighbor_count > 1 ? ctx->cfg.neighbor_count : 1)));
     if (!items && (set.head_set != HS_CHAIN_ANY || by0 != 0 || gen_rows != ctx->fy)) { set_error("mirres_render: the band pipeline needs the pixel-pair queue"); return MIRRES_E_STATE; }   // 32-byte rays: whole frames on lane 0's heads only
     const RaySrc src = {reinterpret_cast<const float4*>(fv.grec), resd(prev_res).rec, ctx->cfg.vis_near, skip_dead};
-    int rc = items ? trace_any_items_q(ctx, bvh, set.q, src, set.counter, cap, set.hit, s, clean, set.head_set) : trace_any_q(ctx, bvh, set.q, set.counter, cap, set.hit, s, 0, clean);
+    // (the resolve's folded reset zeroes set.counter, which a pre-generated pass does not use: the samples' own counters stay as k_spatial_accept left them)
+    int rc = pre ? trace_any_items_q(ctx, bvh, pre->q, src, pre->counter, cap, set.hit, s, clean, set.head_set) :
+             items ? trace_any_items_q(ctx, bvh, set.q, src, set.counter, cap, set.hit, s, clean, set.head_set) : trace_any_q(ctx, bvh, set.q, set.counter, cap, set.hit, s, 0, clean);
     if (rc) return rc;
     GBufD gr = gbufd(g);
     if (fv.grec) gr.rec = reinterpret_cast<const float4*>(fv.grec);   // mirres_render: same values, one 64-byte record per neighbour instead of three arrays
     const bool fuse = next_res && resd(next_res).rec && resd(res).rec && gr.rec;
     const ResD NR = fuse ? resd(next_res) : resd(res);
     const int rg = tile_grid(ctx->fx, res_rows, MR_SRES_TILE), rb = MR_SRES_TILE * MR_SRES_TILE;
-#define MR_SRES_ARGS ctx->cfg, envh(env), gr, resd(res), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, set.slot, set.mask, set.hit, rc_, rh_, NR, next_frame, rows, by0, res_rows
+#define MR_SRES_ARGS ctx->cfg, envh(env), gr, resd(res), resd(prev_res), noff, frameIndex, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, pre ? pre->slot : set.slot, pre ? pre->mask : set.mask, set.hit, rc_, rh_, NR, next_frame, rows, by0, res_rows
     if (nb5 && fuse) k_spatial_resolve<5, true><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
     else if (nb5) k_spatial_resolve<5, false><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
     else if (fuse) k_spatial_resolve<8, true><<<rg, rb, 0, s>>>(MR_SRES_ARGS);
@@ -894,6 +967,20 @@ int launch_spatial(mirres_ctx* ctx, mirres_bvh* bvh, const FrameView& fv, ChainS
 #undef MR_SRES_ARGS
     if (fv.fold) set.clean = true;
     MR_LAUNCH_CHECK("restir_spatial");
+    return MIRRES_OK;
+}
+
+int launch_spatial_accept(mirres_ctx* ctx, const FrameView& fv, int K, uint32_t frame0, uint32_t frame_step, bool first_is_zero, uint2* q, size_t q_stride, uint32_t* counters,
+                          int32_t* slot, uint32_t* mask, hipStream_t s) {
+    if (!ctx || !fv.grec || K < 1 || !q || !counters || !slot || !mask) { set_error("mirres_render: spatial acceptance without packed pixel records"); return MIRRES_E_ARG; }
+    const int N = (int)ctx->N, spt = knob_pregen_spt(K);
+    MR_HIP(hipMemsetAsync(counters, 0, sizeof(uint32_t) * MR_PRE_CSTRIDE * (size_t)K, s));
+    const dim3 grid(tile_grid(ctx->fx, ctx->fy, MR_SGEN_TILE), (K + spt - 1) / spt), block(MR_SGEN_BLOCK);
+#define MR_SACC_ARGS ctx->cfg, reinterpret_cast<const float4*>(fv.grec), ctx->noff, frame0, frame_step, first_is_zero ? 1 : 0, ctx->fx, ctx->fy, N, fv.y_off, fv.occ_own, q, q_stride, counters, slot, mask, K, spt
+    if (ctx->cfg.neighbor_count <= 5) k_spatial_accept<5><<<grid, block, 0, s>>>(MR_SACC_ARGS);
+    else k_spatial_accept<8><<<grid, block, 0, s>>>(MR_SACC_ARGS);
+#undef MR_SACC_ARGS
+    MR_LAUNCH_CHECK("spatial_accept");
     return MIRRES_OK;
 }
 
@@ -938,7 +1025,7 @@ int mirres_ctx_create(mirres_ctx_t** out, int fx, int fy, const mirres_config_t*
 void mirres_ctx_destroy(mirres_ctx_t* c) {
     if (!c) return;
     void* ptrs[] = {c->any_rays, c->any_hit, c->cl_rays, c->cl_hit, c->counters, c->stats, c->slot_a, c->mask_a, c->slot_c, c->pend, c->noff, c->pool, c->tile_aux, c->ptb,
-                    c->ray_prim};
+                    c->ray_prim, c->pregen_counts};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : c->ev_any) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_cl) (void)hipEventDestroy(e);

@@ -177,6 +177,10 @@ struct PtBatch {
     // history-free ReSTIR stages: two sets (batch parity) of K initial / temporal reservoirs and K spatial-output reservoirs, light tiles of K samples
     mirres_res_t rinit[2], rspat[2];
     float *tile_data, *tile_pdf, *tile_aux;
+    // pre-generated neighbour acceptance of the chain (k_spatial_accept), two sets by batch parity like the reservoirs: A(b + 1) is written while C(b) reads A(b).
+    // Per sample a queue segment of pre_stride pairs (every pixel's min(neighbor_count, 8): the worst case), N slots, N masks and one counter line. NULL: not carved
+    struct Pre { uint2* q; int32_t* slot; uint32_t* mask; uint32_t* counters; } pre[2];
+    size_t pre_stride;
 };
 static mirres_res_t res_slot(const mirres_res_t& r, int k, size_t N) {   // packed 32-byte records (passes.hip resd(): light_pdf == NULL)
     mirres_res_t o; o.light_data = r.light_data + 8 * (size_t)k * N; o.light_pdf = nullptr; o.M = nullptr; o.weight = nullptr; return o;
@@ -208,14 +212,16 @@ static hipError_t create_side_stream(hipStream_t* out) {
     }
     return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
 }
-static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS, PtBatch& PB) {
+static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS, PtBatch& PB, bool pregen) {
     if (K < 1) K = 1;
     while ((size_t)K * (size_t)N > 0x30000000ull && K > 1) K--;   // slot indices are 32-bit
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int nb = max_bounce > 0 ? max_bounce : 1;
+    // pre-generated acceptance (PtBatch::pre; MIRRES_SPATIAL_PREGEN): <= 5 (8) pairs of 8 bytes + slot + mask per sample slot, twice: + 96 (144) bytes on ~670
+    const size_t pre_stride = ((size_t)N * (size_t)(ctx->cfg.neighbor_count < 8 ? ctx->cfg.neighbor_count : 8) + 31) & ~(size_t)31;
     auto bytes_for = [&](int k) {
         const size_t NV = (size_t)k * (size_t)N;
-        return al(sizeof(Ray) * 2 * NV) + al(4 * 2 * NV) + al(sizeof(Ray) * NV) + al(sizeof(HitRec) * NV) + al(64) + 5 * al(4 * NV) + al(4 * 18 * NV)
+        return (pregen ? 2 * (al(8 * pre_stride * (size_t)k) + 2 * al(4 * NV) + al(4 * MR_PRE_CSTRIDE * (size_t)k)) : 0) + al(sizeof(Ray) * 2 * NV) + al(4 * 2 * NV) + al(sizeof(Ray) * NV) + al(sizeof(HitRec) * NV) + al(64) + 5 * al(4 * NV) + al(4 * 18 * NV)
              + al(4 * 5 * NV) + 2 * (3 * al(4 * 3 * NV) + al(4 * NV)) + al(4 * 3 * NV) + al(4 * 2 * NV) + al(4 * 9 * NV * (size_t)nb) + al(4 * NV * (size_t)nb)
              + 4 * al(4 * 8 * NV) + al(4 * 3 * (size_t)k * TS) + al(4 * (size_t)k * TS) + al(32 * (size_t)k * TS)
              + 2 * (al(sizeof(Ray) * NV) + 2 * al(4 * NV) + al(64))
@@ -304,6 +310,13 @@ static int carve_batch(mirres_ctx* ctx, int N, int K, int max_bounce, size_t TS,
     PB.qf.cl_rays = nullptr; PB.qf.cl_hit = nullptr; PB.qf.mask_a = nullptr; PB.qf.slot_c = nullptr; PB.qf.pend = nullptr; PB.qf.live[0] = PB.qf.live[1] = nullptr; PB.qf.live_cur = 0;
     PB.qv = PB.qf;
     PB.qv.any_rays = (Ray*)take(sizeof(Ray) * NV); PB.qv.any_hit = (int32_t*)take(4 * NV); PB.qv.slot_a = (int32_t*)take(4 * NV); PB.qv.counters = (uint32_t*)take(64);
+    PB.pre_stride = pre_stride;
+    for (int k = 0; k < 2; k++) {
+        PtBatch::Pre& A = PB.pre[k];
+        A.q = nullptr; A.slot = nullptr; A.mask = nullptr; A.counters = nullptr;
+        if (!pregen) continue;
+        A.q = (uint2*)take(8 * pre_stride * (size_t)K); A.slot = (int32_t*)take(4 * NV); A.mask = (uint32_t*)take(4 * NV); A.counters = (uint32_t*)take(4 * MR_PRE_CSTRIDE * (size_t)K);
+    }
     return 0;
 }
 
@@ -444,6 +457,7 @@ struct Frame {
     int N, i0, i1, nbatch = 0;                  // pixels, the sample range [i0, i1), its batches
     FrameBufs B; PtBatch PB; FrameView fv; mirres_env_t E; mirres_gbuf_t G, Gt; const float* occ;
     bool two_streams = false, dbg_sum = false, matnet_vector = false;
+    bool pregen = false;                        // the chain's neighbour acceptance is made per batch beside I(b) (accept), its spatial pass is trace + resolve
     hipStream_t sp, st, sf, st2 = nullptr;      // sp: I stages, sf: F stages, st (and st2): path-tracing stages
     ChainSet sets[3];                           // the frame's own copies of the context's queue sets: what `clean` says ends with the frame
     bool merged = false;                        // this sample's temporal merge ran inside the previous sample's resolve
@@ -476,7 +490,20 @@ struct Frame {
     }
     int initial(int b) {          // I(b)
         PtQueues Q = PB.qf; Q.NV = batch_k(b) * N;
-        return launch_initial_batch(ctx, bvh, &E, &G, &PB.rinit[b & 1], PB.tile_data, PB.tile_pdf, PB.tile_aux, frame_of(i0 + b * PB.K), batch_k(b), &Q, fv, sp);
+        int rc = launch_initial_batch(ctx, bvh, &E, &G, &PB.rinit[b & 1], PB.tile_data, PB.tile_pdf, PB.tile_aux, frame_of(i0 + b * PB.K), batch_k(b), &Q, fv, sp); if (rc) return rc;
+        return pregen ? accept(b) : 0;
+    }
+    // A(b): neighbour acceptance of the batch's samples, behind I(b) on its stream (it needs the G-buffer only; C(b) waits for both). The set of parity b & 1 was last
+    // read by C(b - 2), which I(b)'s stream has waited for.
+    int accept(int b) {
+        const int ib = i0 + b * PB.K; const PtBatch::Pre& A = PB.pre[b & 1];
+        int rc = launch_spatial_accept(ctx, fv, batch_k(b), frame_of(ib), kRisPasses, ib == 0, A.q, PB.pre_stride, A.counters, A.slot, A.mask, sp); if (rc) return rc;
+        if (b == 0) {   // mirres_debug_spatial_pregen
+            if (!ctx->pregen_counts) MR_HIP(hipMalloc(&ctx->pregen_counts, sizeof(uint32_t) * MR_PRE_CSTRIDE * 64));
+            MR_HIP(hipMemcpyAsync(ctx->pregen_counts, A.counters, sizeof(uint32_t) * MR_PRE_CSTRIDE * (size_t)batch_k(0), hipMemcpyDeviceToDevice, sp));
+            ctx->pregen_last = 1; ctx->pregen_k = batch_k(0);
+        }
+        return 0;
     }
     int final_batch(int b) {      // F(b)
         PtQueues Q = PB.qv; Q.NV = batch_k(b) * N;
@@ -503,7 +530,10 @@ struct Frame {
         }
         const bool fuse_next = may_fuse && knob_fuse_temporal() && !dbg_sum && k + 1 < batch_k(b);      // (sample i + 1 > i0 >= 0: it always has a temporal pass)
         mirres_res_t rn = res_slot(PB.rinit[b & 1], fuse_next ? k + 1 : k, (size_t)N);
-        auto spatial = [&](const SpatialBand& band, const RowSet& rows) { return launch_spatial(ctx, bvh, fv, set, band, rows, &E, &Gt, &rs, &rt, nullptr, base + pass, cs, fuse_next ? &rn : nullptr, frame_of(i + 1) + 3u); };
+        const PtBatch::Pre& A = PB.pre[b & 1];
+        SpatialPre pre = {nullptr, nullptr, nullptr, nullptr};
+        if (pregen) pre = {reinterpret_cast<const Ray*>(A.q + (size_t)k * PB.pre_stride), A.counters + (size_t)k * MR_PRE_CSTRIDE, A.slot + (size_t)k * (size_t)N, A.mask + (size_t)k * (size_t)N};
+        auto spatial = [&](const SpatialBand& band, const RowSet& rows) { return launch_spatial(ctx, bvh, fv, set, band, rows, &E, &Gt, &rs, &rt, nullptr, base + pass, cs, fuse_next ? &rn : nullptr, frame_of(i + 1) + 3u, pregen ? &pre : nullptr); };
         int rc = units(rt, i, spatial); if (rc) return rc;
         merged = fuse_next;
         csum(rs.light_data, 8 * (size_t)N);
@@ -584,11 +614,14 @@ int Frame::fork_streams(int nstreams) {
 // a third of a 2.3 M-ray launch, a small fraction of a K-times larger one.
 int Frame::run() {
     const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
-    int rc = carve_batch(ctx, N, choose_k(i1 - i0, N, knob_pt_batch()), ctx->cfg.max_bounce, TS, PB); if (rc) return rc;
+    const bool want_pregen = knob_spatial_pregen();   // read once per frame: the pool is carved for it, the schedule below decides whether this frame can use it
+    int rc = carve_batch(ctx, N, choose_k(i1 - i0, N, knob_pt_batch()), ctx->cfg.max_bounce, TS, PB, want_pregen); if (rc) return rc;
+    ctx->pregen_last = 0; ctx->pregen_k = 0;
     if (a->tex) { rc = ensure_ray_prim(ctx, (size_t)PB.K * (size_t)N); if (rc) return rc; }   // textured frames only: the batch pool of a material-field frame does not grow
     PB.q.frame = PB.qf.frame = PB.qv.frame = fv;
     // ---- schedule. Per batch b of K samples:
     //   I(b)  initial resampling of the K samples (light tiles, candidates, shadow rays)              bulk stream, K * N slots per launch
+    //   A(b)  neighbour acceptance of the K samples' spatial passes (G-buffer only; accept())         behind I(b), one launch
     //   C(b)  temporal + spatial reuse, one sample after the other (needs the previous sample)        caller's stream, N pixels per launch
     //   F(b)  final visibility + evaluation + shading of the K samples -> totals 0..2                 bulk stream
     //   PT(b) new direction + max_bounce indirect vertices of the K samples -> totals 3..5            path-tracing stream
@@ -633,6 +666,9 @@ int Frame::run() {
         if (overlap && !ctx->halo_stream) MR_HIP(hipStreamCreateWithFlags(&ctx->halo_stream, hipStreamNonBlocking));
         for (int k = 0; overlap && k < 2; k++) if (!ctx->ev_halo[k]) MR_HIP(hipEventCreateWithFlags(&ctx->ev_halo[k], hipEventDisableTiming));
     }
+    // MIRRES_SPATIAL_PREGEN (on): whole-frame passes on the pixel-pair queue take their neighbour acceptance from A(b), one launch per batch, instead of from a
+    // k_spatial_gen launch per sample inside the chain. Not for row-restricted passes (strip_overlap), bands, 32-byte rays or the counting mode: those keep the generator
+    pregen = want_pregen && nbands == 1 && !overlap && !knob_spatial_rays() && !(ctx->instrument & 1) && ctx->cfg.neighbor_count > 0;
     rc = initial(0); if (rc) return rc;
     if (two_streams) MR_HIP(hipEventRecord(ev_bulk(-1), sp));
     for (int b = 0; b < nbatch; b++) {
@@ -713,7 +749,7 @@ int mirres_ctx_reserve(mirres_ctx_t* ctx, int samples_per_batch) {
     if (K > 64) K = 64;
     PtBatch PB;
     const size_t TS = (size_t)ctx->cfg.light_tile_count * ctx->cfg.light_tile_size;
-    const int rc = carve_batch(ctx, ctx->fx * ctx->fy, K, ctx->cfg.max_bounce, TS, PB);
+    const int rc = carve_batch(ctx, ctx->fx * ctx->fy, K, ctx->cfg.max_bounce, TS, PB, knob_spatial_pregen());
     return rc ? rc : PB.K;
 }
 
@@ -748,6 +784,20 @@ int mirres_render(mirres_ctx_t* ctx, mirres_bvh_t* bvh, const mirres_render_args
         return MIRRES_OK;
     }
     return finish(ctx, a, B.tot, B, s);
+}
+
+// Development entry point (outside include/mirres.h, like mirres_debug_matnet_scatter_live): did the last mirres_render frame of this context take its neighbour
+// acceptance from k_spatial_accept (*ran), and how many pixel pairs did each of the *samples samples of its first batch queue (pairs[0 .. *samples), room for 64).
+// Waits for the device.
+int mirres_debug_spatial_pregen(mirres_ctx_t* ctx, int* ran, int* samples, uint32_t* pairs) {
+    if (!ctx || !ran || !samples || !pairs) { set_error("mirres_debug_spatial_pregen: null"); return MIRRES_E_ARG; }
+    *ran = ctx->pregen_last; *samples = ctx->pregen_last ? ctx->pregen_k : 0;
+    if (!*samples) return MIRRES_OK;
+    std::vector<uint32_t> h((size_t)MR_PRE_CSTRIDE * (size_t)*samples);
+    MR_HIP(hipDeviceSynchronize());
+    MR_HIP(hipMemcpy(h.data(), ctx->pregen_counts, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < *samples; k++) pairs[k] = h[(size_t)k * MR_PRE_CSTRIDE] / 2;   // the counter counts rays, two per pair
+    return MIRRES_OK;
 }
 
 int mirres_ctx_halo_time(mirres_ctx_t* ctx, double* ms, int* exchanges) {

@@ -24,7 +24,7 @@ for a, b in zip(chain, chain[1:]):
     if g > 1e6: boundary += g          # frame boundary (LBVH rebuild, environment tables, denoiser, host): reported apart
     else: gap[short(b[2])].append(g)
 for r in chain: dur[short(r[2])].append(r[1] - r[0])
-n_samples = len([r for r in chain if short(r[2]).startswith("k_spatial_gen")])
+n_samples = len([r for r in chain if short(r[2]).startswith("k_spatial_resolve")])      # (one resolve per sample whether or not k_spatial_gen runs in the chain: MIRRES_SPATIAL_PREGEN)
 span = chain[-1][1] - chain[0][0]
 print("chain kernels of %d samples over %.2f ms: period %.1f us per sample" % (n_samples, span / 1e6, span / 1e3 / max(1, n_samples)))
 tot_d = tot_g = 0
