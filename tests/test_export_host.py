@@ -123,6 +123,39 @@ def test_raster_ref_degenerate_and_overlap():
     assert both.any() and (tid[both] == 0).all()
 
 
+def _same_raster(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+
+def test_raster_small_ref_equals_raster_ref():
+    """The vectorised restatement the many-triangle GPU test is held against is the loop restatement: ids and barycentrics equal to the last bit on the first
+    6 000 triangles of that test's input (both diagonals, both windings, 17 zero-area triangles) and on 3 000 small random triangles across the atlas border
+    (clamped boxes, boxes off the grid, overlaps: the lowest index wins); a box beyond maxbox is refused; chunk_first counts ceil(bw * bh / 32) work items per triangle on a case worked by hand."""
+    vt, ft, n_small = R.cell_grid_input()
+    W = H = 1024
+    part = ft[:6000]
+    assert (part[:, 0] == part[:, 1]).sum() == 6000 // 349
+    want = R.raster_ref(vt, part, W, H)
+    got = R.raster_small_ref(vt, part, W, H, 2)
+    assert _same_raster(got, want) and len(np.unique(want[0][want[0] >= 0])) == 6000 - 6000 // 349 and (want[0] >= 0).sum() >= 4 * ((6000 - 6000 // 349) // 2)
+    rng = np.random.default_rng(9)
+    W, H = 48, 40
+    c = np.where(rng.random((3000, 1, 2)) < 0.5, rng.choice([0.0, 1.0], (3000, 1, 2)), rng.uniform(0, 1, (3000, 1, 2)))     # a coordinate on the border or anywhere
+    uv = (c + rng.uniform(-2.5, 2.5, (3000, 3, 2)) / np.array([W, H])).astype(np.float32).reshape(-1, 2)
+    tri = np.arange(9000).reshape(-1, 3)
+    tri[::7] = tri[::7][:, [0, 2, 1]]; tri[5::50, 2] = 9000; tri[6::50, 1] = -1                                               # some reversed, some out of range
+    uv[30::301] = np.nan; uv[31::301] = np.inf
+    s = R.tri_setup(uv, tri, W, H)
+    assert s["bw"].max() <= 6 and s["bh"].max() <= 6 and (s["bw"] == 0).sum() > 100 and ((s["bw"] > 0) & (s["bw"] < 5) & (s["c0"] == 0)).any()
+    want = R.raster_ref(uv, tri, W, H)
+    assert _same_raster(R.raster_small_ref(uv, tri, W, H, 6), want) and (want[0] >= 0).mean() > 0.5 and (want[0] < 0).any()
+    with pytest.raises(AssertionError, match="maxbox"):
+        R.raster_small_ref(uv, tri, W, H, int(max(s["bw"].max(), s["bh"].max())) - 1)
+    # boxes of 16 x 16 = 256, 0 and 7 x 5 = 35 texels: 8, 0 and 2 work items
+    hand = np.array([[0, 0], [1, 0], [0, 1], [7 / 16, 0], [0, 5 / 16]], np.float32)
+    assert R.chunk_first(hand, np.array([[0, 1, 2], [0, 0, 1], [0, 3, 4]]), 16, 16).tolist() == [0, 8, 8, 10]
+
+
 def test_obj_and_mtl_format(EX, tmp_path, scene_mod):
     v, f = scene_mod.make_mesh(2, 4)
     v = v * np.float32(1.2345678) + np.float32(1e-6)

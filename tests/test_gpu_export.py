@@ -21,9 +21,9 @@ def EX():
     return export
 
 
-def _rast_vs_ref(EX, vt, ft, W, H):
+def _rast_vs_ref(EX, vt, ft, W, H, ref=R.raster_ref):
     rast = EX.uv_rasterize(vt, ft, W, H).cpu().numpy()
-    tid, b0, b1 = R.raster_ref(vt, ft, W, H)
+    tid, b0, b1 = ref(vt, ft, W, H)
     assert np.array_equal(rast[:, 3].astype(np.int64) - 1, tid), "%d texels differ" % int((rast[:, 3].astype(np.int64) - 1 != tid).sum())
     cov = tid >= 0
     assert np.abs(rast[cov, 0] - b0[cov]).max(initial=0) <= 1e-6 and np.abs(rast[cov, 1] - b1[cov]).max(initial=0) <= 1e-6
@@ -62,6 +62,28 @@ def test_uv_rasterize_adversarial(EX):
                          [[0, 0, 1], [2, 3, 2]], rng.integers(0, N, (40, 3))))
     ft = np.concatenate((ft, ft[:, [0, 2, 1]]))                                # the same triangles reversed: the lower index wins
     _rast_vs_ref(EX, vt, ft, W, H)
+
+
+def test_uv_rasterize_scans_more_than_two_rounds_of_block_sums(EX):
+    """Branch: the carry of k_scan_sums (csrc/bake.hip:113) — one workgroup walks the block sums BK_BLOCK = 256 (:15) at a time, each sum covering BK_SCAN = 1024
+    (:88) triangles, so a second round needs more than 262 144 triangles — with a ragged last round, a ragged last block of k_scan_local, zero-chunk
+    triangles (equal neighbours in first[], which k_uv_cover's binary search must step over) and triangles of many chunks.
+    Input (bake_refs.cell_grid_input): a 1024 x 1024 grid tiled by 2 x 2-texel cells, each split along a random diagonal through two texel centres (the fill
+    rule decides them), half the triangles reversed, a zero-area triangle at every 349th position, 200 triangles with boxes of up to 100 x 100 texels last.
+    Host assertions before the launch: T > 2 * 262 144, nb % 256 != 0, T % 1024 != 0, first[] restated has equal neighbours, every texel covered in the
+    reference.  Observed: T = 525 994, nb = 514 block sums = 3 rounds (the last of 2), 1 507 zero-chunk triangles, 528 919 work items, up to 169 for one triangle."""
+    BK_BLOCK, BK_SCAN = 256, 1024                                              # csrc/bake.hip:15 and :88
+    W = H = 1024
+    vt, ft, n_small = R.cell_grid_input(W)
+    T = ft.shape[0]; nb = -(-T // BK_SCAN)
+    first = R.chunk_first(vt, ft, W, H)
+    ref = R.raster_split_ref(vt, ft, n_small, W, H, 2)
+    print("T %d, nb %d, rounds %d, zero-chunk triangles %d, work items %d" % (T, nb, -(-nb // BK_BLOCK), int((np.diff(first) == 0).sum()), first[-1]))
+    assert T > 2 * BK_BLOCK * BK_SCAN and -(-nb // BK_BLOCK) >= 3 and nb % BK_BLOCK != 0 and T % BK_SCAN != 0
+    assert (np.diff(first) == 0).sum() >= n_small // 349 and np.diff(first).max() > 100
+    assert (ref[0] >= 0).all() and len(np.unique(ref[0])) == n_small - n_small // 349
+    tid = _rast_vs_ref(EX, vt, ft, W, H, ref=lambda *a: ref)
+    assert np.array_equal(tid, ref[0])
 
 
 def _mlp():

@@ -101,7 +101,9 @@ def test_march_rays_train_bit_equal(RM, kind, shape_i):
         assert all(R.march_train_case(kind, shape_i, pi, 65)["rays"][:, 1].sum() == 0 for pi in range(len(R.MARCH_PARAMS)) if not R.MARCH_PARAMS[pi]["contract"])
 
 
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 2048])
+# k_rm_scan (csrc/raymarch.hip:121) gives each of its RM_SCAN_BLOCK = 1024 threads a run of ceil(N / 1024) rays: 1025, 2050 and 3073 make runs of 2, 3 and 4,
+# a last non-empty thread (512, 683, 768) that holds ONE ray, and empty threads after it; 2048 divides evenly
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 2048, 1025, 2050, 3073])
 def test_march_rays_train_ray_counts_and_repeatability(RM, N):
     for pi in (0, 15):                                                       # (dt_gamma 0, no perturb, no contract, 64 steps) and (1/256, perturb, contract, 1024)
         c = R.march_train_case("random", 1, pi, N)

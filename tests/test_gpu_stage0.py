@@ -1,6 +1,7 @@
 """The stage-0 extraction on the device (csrc/mcubes.hip) through the C ABI: marching cubes bit for bit against the numpy restatement (tests/stage0_refs.py, same
 generated table, same fp32 expressions), surface properties, the checkpoint's density grid, visibility marking against raster.rasterize's own output, ring
-dilatation, compaction, edge-connected components against scipy, cleaning, and scripts/export_stage0.py --synthetic end to end."""
+dilatation, compaction, edge-connected components against scipy, cleaning, and scripts/export_stage0.py --synthetic end to end; last, the same kernels at sizes
+where the second level of their prefix sums has more than one workgroup total per scan thread, each test asserting on the host that its input gets there."""
 import ctypes as C
 import os
 import subprocess
@@ -42,10 +43,10 @@ def _mc_abi(vol, iso):
     return rc, rc2, verts.cpu().numpy(), tris.cpu().numpy()
 
 
-def _check_mc(vol, iso, what):
+def _check_mc(vol, iso, what, ref=None):
     rc, rc2, v, t = _mc_abi(vol, iso)
     assert rc == 0 and rc2 == 0, what
-    rv, rt = R.marching_cubes(vol, iso)
+    rv, rt = ref if ref is not None else R.marching_cubes(vol, iso)
     assert t.shape == rt.shape and np.array_equal(t, rt), "%s: triangles differ (%s vs %s)" % (what, t.shape, rt.shape)
     assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32)), "%s: %d of %d vertex words differ" % (
         what, int((v.view(np.uint32) != rv.view(np.uint32)).sum()) if v.shape == rv.shape else -1, rv.size)
@@ -302,3 +303,219 @@ def test_export_stage0_synthetic_end_to_end(S0, tmp_path):
     env = torch.from_numpy(scene.make_env(32, 64)).cuda()
     img = harness.test_view(W, None, env, torch.from_numpy(poses[0]), intr, 32, 32, 2)
     assert tuple(img.shape) == (32, 32, 3) and torch.isfinite(img).all() and float(img.min()) >= 0 and float((img < 0.999).float().mean()) > 0.05
+
+
+# ------------------------------------------------------------------------------------------------ past the first chunk of the second-level scans
+MC_BLOCK, MC_SCAN_BLOCK = 256, 1024                                                  # csrc/mcubes.hip:24 and :25
+
+
+def _scan_split(n_items):
+    """How k_scan_ints (csrc/mcubes.hip:91-96) splits the workgroup totals of n_items elements -> (nb totals, `per` totals per scan thread, whether the last scan
+    thread's chunk is empty (its i0 = 1023 per is not below nb), whether the last non-empty chunk is shorter than per)."""
+    nb = -(-n_items // MC_BLOCK); per = -(-nb // MC_SCAN_BLOCK)
+    return nb, per, (MC_SCAN_BLOCK - 1) * per >= nb, nb % per != 0
+
+
+def _mc_structure(vol, iso):
+    """What the kernels of csrc/mcubes.hip see of a volume, restated: the number of crossed owned edges per grid point g (k_mc_count's popc(eflags)), the point
+    that owns each vertex (vertices are numbered in (g, axis) order) and the point whose cell emits each triangle (triangles are numbered in (g, table) order)."""
+    v = np.nan_to_num(np.asarray(vol, np.float32), nan=0.0, posinf=R.FLT_MAX, neginf=-R.FLT_MAX)
+    nx, ny, nz = v.shape
+    inside = v >= np.float32(iso)
+    cross = np.zeros((nx, ny, nz, 3), bool)
+    cross[:-1, :, :, 0] = inside[:-1] != inside[1:]
+    cross[:, :-1, :, 1] = inside[:, :-1] != inside[:, 1:]
+    cross[:, :, :-1, 2] = inside[:, :, :-1] != inside[:, :, 1:]
+    n_edges = cross.reshape(-1, 3).sum(1)
+    cfg = np.zeros((nx - 1, ny - 1, nz - 1), np.int64)
+    for c in range(8):
+        dx, dy, dz = c & 1, (c >> 1) & 1, (c >> 2) & 1                              # corner c of a cell (csrc/mcubes.hip:52)
+        cfg |= inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz].astype(np.int64) << c
+    cx, cy, cz = np.nonzero(R.NTRI[cfg] > 0)
+    return n_edges, np.repeat(np.arange(n_edges.size), n_edges), np.repeat((cx * ny + cy) * nz + cz, R.NTRI[cfg[cx, cy, cz]])
+
+
+def _max_block_prefix(n_edges):
+    """The largest exclusive vertex prefix inside a 256-point workgroup at a point that owns a vertex: the 10-bit field of local[g] (csrc/mcubes.hip:86)."""
+    b = np.zeros(-(-n_edges.size // MC_BLOCK) * MC_BLOCK, np.int64); b[:n_edges.size] = n_edges
+    b = b.reshape(-1, MC_BLOCK)
+    return int(((np.cumsum(b, 1) - b) * (b > 0)).max())
+
+
+_MC_CASES = {}
+
+
+def _mc_case(shape):
+    """(volume, reference vertices, reference triangles) of normal noise in `shape`, computed once per process and read-only."""
+    if shape not in _MC_CASES:
+        vol = np.random.default_rng(sum(shape)).normal(size=shape).astype(np.float32)
+        rv, rt = R.marching_cubes(vol, 0.8)
+        for a in (vol, rv, rt):
+            a.setflags(write=False)
+        _MC_CASES[shape] = (vol, rv, rt)
+    return _MC_CASES[shape]
+
+
+BIG = (67, 65, 64)                                                                  # the volume whose mesh the mesh tools below work on
+
+
+# the third entry: is the last non-empty chunk of k_scan_ints shorter than `per` (three of the four shapes)
+@pytest.mark.parametrize("shape,far,ragged", [((3, 3, 40000), False, True), ((40000, 3, 3), False, True), ((2, 131073, 2), True, False), (BIG, False, True)])
+def test_marching_cubes_past_the_first_scan_chunk(shape, far, ragged):
+    """Branch: k_scan_ints (csrc/mcubes.hip:91) with per = ceil(nb / MC_SCAN_BLOCK) >= 2 — the chunk loops at :96 and :106, threads whose chunk is empty, and for
+    three of the four shapes a last non-empty chunk shorter than per — with the large stride of blk_v[q / MC_BLOCK] in k_mc_emit (:148) on each axis in turn.
+    Host assertions before the launch: nb = ceil(points / 256) > 1024, per >= 2, (1024 - 1) per >= nb, nb % per != 0 where `ragged`; for (2, 131073, 2), whose
+    x stride is 262 146 points, a triangle of the reference mesh uses a vertex owned by a point more than 1024 workgroups after the emitting cell's.
+    Observed (nb, per, vertices, triangles): (3, 3, 40000) 1407, 2, 280 853, 268 345; (40000, 3, 3) 1407, 2, 281 130, 268 322; (2, 131073, 2) 2049, 3,
+    349 060, 218 128, of which 1 479 triangles read 1025 workgroups ahead; (67, 65, 64) 1089, 2, 274 043, 442 622."""
+    vol, rv, rt = _mc_case(shape)
+    nb, per, empty, short = _scan_split(vol.size)
+    print("%s: nb %d, per %d, %d vertices, %d triangles" % (shape, nb, per, len(rv), len(rt)))
+    assert nb > MC_SCAN_BLOCK and per >= 2 and empty and short == ragged
+    if far:
+        n_edges, owner, cell = _mc_structure(vol, 0.8)
+        assert len(owner) == len(rv) and len(cell) == len(rt)
+        reach = owner[rt].max(1) // MC_BLOCK - cell // MC_BLOCK
+        print("%d triangles read blk_v more than %d workgroups ahead (at most %d)" % (int((reach > MC_SCAN_BLOCK).sum()), MC_SCAN_BLOCK, reach.max()))
+        assert (reach > MC_SCAN_BLOCK).any()
+    v, t = _check_mc(vol, 0.8, "noise %s" % (shape,), ref=(rv, rt))
+    assert t.min() == 0 and t.max() == len(v) - 1
+
+
+@pytest.mark.parametrize("shape", [(12, 11, 13), (3, 3, 40000)])
+def test_checkerboard_sets_the_top_bit_of_the_prefix_field(shape):
+    """Branch: bit 9 of the 10-bit vertex prefix k_mc_count packs into local[g] under the edge flags (csrc/mcubes.hip:86), which k_mc_emit masks out with 1023
+    (:148).  A checkerboard sign * (1 + u) at iso 0 crosses every edge, so a workgroup of MC_BLOCK = 256 points owns close to 3 * 256 vertices.
+    Host assertion before the launch: the largest exclusive prefix inside a workgroup at a point that owns a vertex, computed as k_mc_count does, is >= 512.
+    Observed: 733 at (12, 11, 13), 765 at (3, 3, 40000); the noise volumes above stop at 322."""
+    rng = np.random.default_rng(sum(shape))
+    x, y, z = np.meshgrid(*(np.arange(n) for n in shape), indexing="ij")
+    vol = (np.where((x + y + z) & 1, -1.0, 1.0) * (1.0 + rng.random(shape))).astype(np.float32)
+    top = _max_block_prefix(_mc_structure(vol, 0.0)[0])
+    print("%s: largest prefix %d" % (shape, top))
+    assert 512 <= top < 1024
+    v, t = _check_mc(vol, 0.0, "checkerboard %s" % (shape,))
+    assert len(v) == sum((shape[a] - 1) * shape[a - 1] * shape[a - 2] for a in range(3))      # every edge of the grid carries a vertex
+
+
+def test_sphere_at_128_scans_eight_totals_per_thread(S0):
+    """Branch: k_scan_ints (csrc/mcubes.hip:91) at per = 8 on the scene the export's smoke run uses, S0.synthetic_volume(128) at iso 10: a dented ball and a small
+    floater, two closed surfaces of genus 0.
+    Host assertion before the launch: 128^3 points are nb = 8192 workgroups of MC_BLOCK = 256, per = 8 for MC_SCAN_BLOCK = 1024 scan threads, none of them empty.
+    Checked: bit-equal to the restatement, every edge shared by two triangles in opposite directions, two components of Euler characteristic 2 each, outward
+    orientation, two runs byte-identical.  Observed: 27 360 vertices, 54 712 triangles, components of 140 (the floater, first in memory order) and 54 572 faces."""
+    nb, per, empty, short = _scan_split(128 ** 3)
+    assert (nb, per, empty, short) == (8192, 8, False, False)
+    vol = S0.synthetic_volume(128).cpu().numpy()
+    v, t = _check_mc(vol, 10.0, "synthetic_volume(128)")
+    lab = _scipy_labels(t)
+    parts = [t[lab == l] for l in np.unique(lab)]
+    print("%d vertices, %d triangles, components of %s faces" % (len(v), len(t), [len(p) for p in parts]))
+    assert R.mesh_edges_ok(t) and len(parts) == 2 and R.signed_volume(v, t) > 0
+    assert all(R.euler_characteristic(len(np.unique(p)), p) == 2 for p in parts)
+    v2, t2 = S0.marching_cubes(vol, 10.0)
+    assert v.tobytes() == v2.cpu().numpy().tobytes() and t.tobytes() == t2.cpu().numpy().tobytes()
+
+
+@pytest.fixture(scope="module")
+def big_mesh():
+    """The reference mesh of the (67, 65, 64) noise volume: both ceil(V / 256) and ceil(T / 256) exceed 1024, so every k_scan_ints of mirres_mesh_compact runs
+    with per = 2, an empty last thread and a ragged last chunk."""
+    vol, rv, rt = _mc_case(BIG)
+    return dict(v=rv, t=rt, V=len(rv), T=len(rt))
+
+
+def _keep_mask(name, T):
+    keep = np.zeros(T, np.uint8)
+    if name == "all": keep[:] = 1
+    elif name == "last": keep[-1] = 1
+    elif name == "first": keep[0] = 1
+    elif name == "random": keep[:] = np.random.default_rng(12).random(T) < 0.3
+    elif name == "beyond": keep[MC_SCAN_BLOCK * MC_BLOCK:] = 1
+    return keep
+
+
+@pytest.mark.parametrize("mask", ["all", "none", "last", "first", "random", "beyond"])
+def test_compaction_past_the_first_scan_chunk(S0, big_mesh, mask):
+    """Branch: both k_scan_ints launches of mirres_mesh_compact (csrc/mcubes.hip:471, :474) with per >= 2 over the totals of k_flag_sums, for masks that put the
+    kept elements everywhere, nowhere, in the last or first workgroup only, at random, and ("beyond") exactly in the workgroups after the first
+    MC_SCAN_BLOCK * MC_BLOCK = 262 144 faces, whose offsets come from the second entry of a scan thread's chunk on.
+    Host assertion before the launch: ceil(V / 256) > 1024 and ceil(T / 256) > 1024 (per >= 2), the last scan thread's chunk empty; "beyond" keeps a face.
+    Observed: V = 274 043 (1071 totals, per 2), T = 442 622 (1729 totals, per 2); "random" keeps 132 681 faces and 219 154 vertices, "beyond" 180 478 and 113 683."""
+    m = big_mesh
+    for n in (m["V"], m["T"]):
+        nb, per, empty, short = _scan_split(n)
+        assert nb > MC_SCAN_BLOCK and per >= 2 and empty
+    keep = _keep_mask(mask, m["T"])
+    assert keep.sum() == {"all": m["T"], "none": 0, "last": 1, "first": 1}.get(mask, keep.sum())
+    if mask == "beyond":
+        assert keep[MC_SCAN_BLOCK * MC_BLOCK:].all() and len(keep) > MC_SCAN_BLOCK * MC_BLOCK and not keep[:MC_SCAN_BLOCK * MC_BLOCK].any()
+    rv, rt = R.compact(m["v"], m["t"], keep)
+    print("%s: keeps %d faces, %d vertices" % (mask, len(rt), len(rv)))
+    v, t = S0.compact_mesh(m["v"], m["t"], keep)
+    v, t = v.cpu().numpy(), t.cpu().numpy()
+    assert t.shape == rt.shape and np.array_equal(t, rt)
+    assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32))
+
+
+@pytest.mark.parametrize("rings", [1, 3])
+def test_dilation_on_a_mesh_of_many_workgroups(S0, big_mesh, rings):
+    """mirres_mesh_dilate (csrc/mcubes.hip:440) over 1729 workgroups of faces and 1071 of vertices, from a random 1 % of the faces, against stage0_refs.dilate.
+    Host assertion before the launch: ceil(T / 256) > 1024, the selection and its complement are not empty.  Observed: 4 501 faces selected, 46 321 after one
+    ring, 122 721 after three."""
+    m = big_mesh
+    assert -(-m["T"] // MC_BLOCK) > MC_SCAN_BLOCK
+    sel = (np.random.default_rng(13).random(m["T"]) < 0.01).astype(np.uint8)
+    want = R.dilate(m["t"], m["V"], sel, rings)
+    print("%d faces selected, %d after %d rings" % (sel.sum(), want.sum(), rings))
+    assert 0 < sel.sum() < want.sum() < m["T"]
+    got = S0.dilate_selection(m["t"], m["V"], sel, rings).cpu().numpy()
+    assert np.array_equal(got.astype(bool), want)
+
+
+def test_components_of_a_mesh_of_many_workgroups(S0, big_mesh):
+    """mirres_mesh_components (csrc/mcubes.hip:486) on 442 622 faces in 23 733 components (noise at iso 0.8: many small pieces), against
+    scipy's connected components; the hook / jump rounds stay within MESH_MAX_ROUNDS = 64 (:26).
+    Host assertion before the launch: ceil(T / 256) > 1024 and the reference finds more than 1000 components, one of them larger than a workgroup.
+    Observed: 23 733 components, the largest of 564 faces, 5 rounds."""
+    m = big_mesh
+    want = _scipy_labels(m["t"])
+    sizes = np.bincount(want)
+    print("%d components, the largest of %d faces" % (int((sizes > 0).sum()), sizes.max()))
+    assert -(-m["T"] // MC_BLOCK) > MC_SCAN_BLOCK and (sizes > 0).sum() > 1000 and sizes.max() > MC_BLOCK
+    lab, rounds = S0.face_components(m["t"])
+    print("%d rounds" % rounds)
+    assert np.array_equal(lab.cpu().numpy(), want) and 1 <= rounds <= 64
+
+
+@pytest.mark.parametrize("S", [128, 256])
+def test_unpack_density_grid_at_checkpoint_sizes(S0, S):
+    """Branch: the `<< 8` step of spread3 (csrc/mcubes.hip:157), which moves bits 4-7 of a coordinate and so does nothing below S = 32; checkpoints use S = 128.
+    Host assertion before the launch: S - 1 has a bit in 4-7 set; the two host restatements (the bit trick of stage0_refs.unpack_morton and the per-bit loop
+    of stage0.morton_indices) agree.  Exact against both."""
+    assert (S - 1) & 0xF0 and S <= 256
+    grid = np.random.default_rng(S).random(S ** 3, dtype=np.float32)
+    want = R.unpack_morton(grid, S)
+    assert np.array_equal(want, grid[S0.morton_indices(S)])
+    got = S0.unpack_density_grid(grid).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("Rr,S", [(129, 128), (200, 128), (255, 64), (128, 128)])
+def test_mask_by_density_grid_at_other_ratios(S0, Rr, S):
+    """k_mask_nearest (csrc/mcubes.hip:171) at ratios where floor(dst * (float)(S / R)) lands beside the exact quotient or needs its clamp: one more than the grid,
+    a non-integer ratio, almost four to one, and one to one; NaN and infinities under both values of the mask.  Exact against F.interpolate(mode='nearest').
+    Host assertion before the launch: the reference mask has both values, and non-finite cells lie under a cleared and under a set mask."""
+    rng = np.random.default_rng(Rr + S)
+    grid = (rng.random((S, S, S)) * 9).astype(np.float32)
+    dense = (rng.random((Rr, Rr, Rr)) * 9 + 1).astype(np.float32)
+    flat = dense.reshape(-1)
+    bad = rng.choice(flat.size, 300, replace=False)
+    flat[bad[:100]] = np.nan; flat[bad[100:200]] = np.inf; flat[bad[200:]] = -np.inf
+    mask = torch.nn.functional.interpolate(torch.from_numpy(grid)[None, None], size=[Rr] * 3, mode="nearest")[0, 0] > 4.5
+    under = mask.reshape(-1).numpy()[bad]
+    assert 0.3 < float(mask.float().mean()) < 0.7 and under.any() and not under.all()
+    want = torch.from_numpy(dense) * mask
+    got = S0.mask_by_density_grid(dense, grid, 4.5).cpu()
+    assert torch.equal(torch.nan_to_num(got, 0), torch.nan_to_num(want, 0)) and torch.equal(torch.isnan(got), torch.isnan(want))
+    assert np.array_equal(got.numpy()[~np.isnan(got.numpy())].view(np.uint32), want.numpy()[~np.isnan(want.numpy())].view(np.uint32))
