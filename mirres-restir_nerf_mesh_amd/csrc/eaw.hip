@@ -230,7 +230,8 @@ __global__ void __launch_bounds__(MR_BLOCK) k_eaw_bwd_gather(int fx, int fy, int
 
 // ---------------------------------------------------------------- bilateral denoiser (nerf/renderutils: ops.py:173-211, c_src/denoising.cu:14-130)
 // The alternative denoiser of run_restir_di_with_pt (--use_bi_de, renderer_restir.py:529-541). Per pixel, over a (2r+1)^2 window with
-// r = 2 ceil(2.5 sigma) + 1 (sigma = 4 -> 43 x 43 taps): w = exp(-d^2 / 2 sigma^2) * clamp(n_t . n_c, 1e-4, 1)^128 * exp(-|z_t - z_c| / max(dz_c d, 1e-4));
+// r = 2 ceil(2.5 sigma) + 1, the product taken in double as denoising.cu:26,86 does (sigma = 4 -> 43 x 43 taps; in float 0.4f * 2.5f rounds onto 1 and the
+// window comes out one ring pair short): w = exp(-d^2 / 2 sigma^2) * clamp(n_t . n_c, 1e-4, 1)^128 * exp(-|z_t - z_c| / max(dz_c d, 1e-4));
 // out = (sum w col, max(sum w, 1e-4)). The backward is the transposed gather (the depth term's denominator uses the TAP's dz, denoising.cu:113).
 // Inputs are read from one packed 32-byte record per pixel {col.xyz n.x | n.yz z dz} built by k_bilateral_pack (the normal is normalised
 // there: safe_normalize, ops.py:168-169), so a tap is two 16-byte loads that neighbouring pixels share through L1.
@@ -262,7 +263,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_bilateral(int fx, int fy, float si
     const v3 c_nrm = V3(ca.w, cb.x, cb.y);
     const float c_z = cb.z, c_dz = cb.w;
     const float variance = sigma * sigma;
-    const int rad = 2 * (int)ceilf(sigma * 2.5f) + 1;
+    const int rad = 2 * (int)ceil((double)sigma * 2.5) + 1;
     float accum_w = 0.f; v3 acc = V3(0.f);
     for (int dy = -rad; dy <= rad; ++dy) {
         const int yy = y + dy;
@@ -319,7 +320,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_bilateral_pack5(size_t n, const fl
 __global__ void __launch_bounds__(MR_BLOCK) k_bilateral5(int fx, int fy, float sigma, const float4* __restrict__ rec, Bil5 P) {
     __shared__ float s_wxy[(2 * MR_BIL_MAXRAD + 1) * (2 * MR_BIL_MAXRAD + 1)], s_dist[(2 * MR_BIL_MAXRAD + 1) * (2 * MR_BIL_MAXRAD + 1)];
     const float variance = sigma * sigma;
-    const int rad = 2 * (int)ceilf(sigma * 2.5f) + 1, wdt = 2 * rad + 1;
+    const int rad = 2 * (int)ceil((double)sigma * 2.5) + 1, wdt = 2 * rad + 1;
     for (int i = threadIdx.x; i < wdt * wdt; i += MR_BLOCK) {
         const int dy = i / wdt - rad, dx = i % wdt - rad;
         const float dist_sqr = (float)(dx * dx + dy * dy);
@@ -363,7 +364,7 @@ int launch_bilateral_divided(int fx, int fy, float sigma, const float* col, cons
 // scratch: f32[N, 20]
 int launch_bilateral5(int fx, int fy, float sigma, const float* const col[5], const float* nrm, const float* zdz, float* scratch, float* const out[5], hipStream_t s) {
     const size_t n = (size_t)fx * fy;
-    if (2 * (int)ceilf(sigma * 2.5f) + 1 > MR_BIL_MAXRAD) {
+    if (2 * (int)ceil((double)sigma * 2.5) + 1 > MR_BIL_MAXRAD) {
         for (int k = 0; k < 5; k++) { int rc = launch_bilateral_divided(fx, fy, sigma, col[k], nrm, zdz, scratch, out[k], s); if (rc) return rc; }
         return 0;
     }

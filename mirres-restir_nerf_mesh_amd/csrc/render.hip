@@ -370,8 +370,8 @@ static int finish(mirres_ctx* ctx, const mirres_render_args_t* a, float* tot[6],
     k_average<<<grid_for(n3, MR_BLOCK), MR_BLOCK, 0, s>>>(n3, (float)spp, tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], B.comb);
     const float* srcs[5] = {tot[1], tot[2], B.comb, tot[4], tot[5]};
     if (a->gb_depth) {
-        // bilateral_denoiser(_no_di) with factor 2 (renderer_restir.py:529-541): sigma = max(2 * factor, 1e-4); the packed tap records live in
-        // the (now idle) packed G-buffer area of the pool (16 floats per pixel >= the 8 needed)
+        // bilateral_denoiser(_no_di) with factor 2 (renderer_restir.py:529-541): sigma = max(2 * factor, 1e-4); the packed tap records of the
+        // five-buffer kernel (20 floats per pixel, k_bilateral_pack5) live in the pool's own area for them (B.bil = 20 * N floats)
         const float sigma = fmaxf(2.0f * 2.0f, 0.0001f);
         float* const dsts[5] = {a->outs[1], a->outs[2], a->outs[3], a->outs[4], a->outs[5]};
         int rc = launch_bilateral5(ctx->fx, ctx->fy, sigma, srcs, a->normal, a->gb_depth, B.bil, dsts, s); if (rc) return rc;   // one pass: the five buffers share the weights

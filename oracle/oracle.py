@@ -27,16 +27,17 @@ def build(force=False):
 
 
 def build_ref(force=False):
-    """oracle/_ref: the reference's own kernels compiled by hipcc from the reference tree (oracle/Makefile `ref`): the bilateral denoiser (libref_denoise.so) and the
-    ray-marching operators (libref_raymarch.so).  Only possible where the reference tree exists (the build container); the GPU box uses the prebuilt files that
-    travelled with the snapshot.  make decides what is stale (drivers, shim headers, the reference's sources), so it runs on every call.  -> the list of the files
+    """oracle/_ref: the reference's own kernels compiled by hipcc from the reference tree (oracle/Makefile `ref`): the bilateral denoiser (libref_denoise.so), the
+    ray-marching operators (libref_raymarch.so) and the shading normal (libref_normal.so, built last).  Only possible where the reference tree exists (the build
+    container); the GPU box uses the prebuilt files that travelled with the snapshot.  make decides what is stale (drivers, shim headers, the reference's sources), so it runs on every call.  -> the list of the files
     that exist afterwards (None without a reference tree).  When one is missing its consumer skips: tests/test_gpu_bilateral.py's reference-kernel comparison without
-    libref_denoise.so, the whole of tests/test_gpu_ref_raymarch.py without libref_raymarch.so (the build's failure text names the first only)."""
+    libref_denoise.so and its shading-normal comparison without libref_normal.so, the whole of tests/test_gpu_ref_raymarch.py without libref_raymarch.so (the
+    build's failure text names the first only)."""
     ref = os.environ.get("MIRRES_REF", "/root/reference")
     if not os.path.isdir(ref):
         return None
     subprocess.run(["make", "-C", _HERE, "ref", "REF=" + ref] + (["-B"] if force else []), check=True, capture_output=True, text=True)   # the tree the isdir test looked at
-    return [q for q in (os.path.join(_HERE, "_ref", f) for f in ("libref_denoise.so", "libref_raymarch.so")) if os.path.exists(q)]
+    return [q for q in (os.path.join(_HERE, "_ref", f) for f in ("libref_denoise.so", "libref_raymarch.so", "libref_normal.so")) if os.path.exists(q)]
 
 
 def ref_denoise_lib():
@@ -48,6 +49,20 @@ def ref_denoise_lib():
     vp = C.c_void_p
     L.ref_bilateral_fwd.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]; L.ref_bilateral_fwd.restype = C.c_int
     L.ref_bilateral_bwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]; L.ref_bilateral_bwd.restype = C.c_int
+    return L
+
+
+def ref_normal_lib():
+    """ctypes handle of oracle/_ref/libref_normal.so (GPU code: the reference's normal.cu behind oracle/ref_normal_driver.hip), or None when it was not built.
+    ref_shading_normal_fwd(in[6], shapes[18], two_sided, opengl, out, stream) / ref_shading_normal_bwd(in[6], shapes[18], two_sided, opengl, dout, grads[6], stream):
+    `in` / `grads` are host arrays of six device pointers (pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm), `shapes` the (n, h, w) of each input."""
+    p = os.path.join(_HERE, "_ref", "libref_normal.so")
+    if not os.path.exists(p):
+        return None
+    L = C.CDLL(p)
+    vp, p6, s18 = C.c_void_p, C.POINTER(C.c_void_p * 6), C.POINTER(C.c_int * 18)
+    L.ref_shading_normal_fwd.argtypes = [p6, s18, C.c_int, C.c_int, vp, vp]; L.ref_shading_normal_fwd.restype = C.c_int
+    L.ref_shading_normal_bwd.argtypes = [p6, s18, C.c_int, C.c_int, vp, p6, vp]; L.ref_shading_normal_bwd.restype = C.c_int
     return L
 
 
