@@ -101,6 +101,8 @@ MR_DEV void atomic_add3(float* p, size_t i, v3 v) { atomicAdd(&p[3 * i], v.x); a
 
 // Adjoint of k_eaw (what Slang autodiff produces for process_EAWDenoise.bwd, Denoising.py:38-44):
 //   out = S / W,  S = sum_i c_i w_i k_i,  W = sum_i w_i k_i,  w_i = exp(-|c0-c_i|^2/phi_c) exp(-|n0-n_i|^2/phi_n) exp(-|p0-p_i|^2/phi_p)
+// For POSITIVE phis only: there exp(.) <= 1 and the forward's min(., 1) never binds. With phi <= 0 the clamp is active, autodiff passes no gradient through it
+// and this adjoint, which differentiates the exponentials regardless, differs (tests/eaw_refs.py; non-positive phis are outside what the path uses).
 __global__ void __launch_bounds__(MR_BLOCK) k_eaw_bwd(int fx, int fy, int step, float c_phi, float n_phi, float p_phi, const float* __restrict__ occ,
                                                       const float* __restrict__ color, const float* __restrict__ normal, const float* __restrict__ pos,
                                                       const float* __restrict__ gout, float* __restrict__ gc, float* __restrict__ gn, float* __restrict__ gp) {
