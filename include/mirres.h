@@ -539,6 +539,28 @@ int mirres_density_volume(const mirres_density_t* net, const float* xs, int nx, 
                           const float* grid_vol, int S, float thresh, float* out, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------------------------------------------
+ * The stage-0 radiance network (radiance.hip): NeRFNetwork.forward(x, d) (nerf/network.py:146-174) in one fused query per sample point, fp32 throughout (the
+ * reference: fp16 autocast, as for the density; DESIGN.md sections 5.14 and 8).  The position encoder and its bits are mirres_density_points'; sigma_net gives all
+ * 16 outputs h16 = W1 . relu(W0 . feat), sigma = mrf_exp(h16[0]) with the bits mirres_density_points gives the same point, geo_feat = h16[1..15]; the direction goes
+ * through the degree-4 spherical-harmonics encoder (shencoder/src/shencoder.cu:43-68 after SHEncoder.forward's normalisation; the arithmetic is fixed without FMA,
+ * section 5.14); rgb = mrf_sigmoid(C2 . relu(C1 . relu(C0 . [sh, geo_feat]))), every layer bias-free and every output a k-ascending fmaf chain from 0.  A point out
+ * of bounds (or not finite) has zero features: sigma 1, geo_feat 0, and its colour is still evaluated.  A zero or non-finite direction gives NaN sh and NaN rgb.  */
+typedef struct {
+    mirres_density_t grid;   /* levels, table, w0; grid.w1 = row 0 of w1 as today */
+    const float* w1;         /* device f32 [16, 64]: sigma_net.1.weight            */
+    const float* c0;         /* device f32 [64, 31]: color_net.0.weight            */
+    const float* c1;         /* device f32 [64, 64]: color_net.1.weight            */
+    const float* c2;         /* device f32 [3, 64]:  color_net.2.weight            */
+} mirres_radiance_t;
+/* pos, dirs f32[n,3] -> sigma_out f32[n] (NULL: NeRFNetwork.rgb, the colour alone), rgb_out f32[n,3] and, when not NULL, h16_out f32[n,16] (sigma_net's raw
+ * outputs) and sh_out f32[n,16].  n in [0, 2^38]; n == 0 launches nothing.  h16_out and sh_out are written 16 bytes at a time: they must be 16-byte aligned
+ * (as feat_out of mirres_density_points).                                                                                                                       */
+int mirres_radiance_points(const mirres_radiance_t* net, const float* pos, const float* dirs, long long n, float bound, float* sigma_out, float* rgb_out,
+                           float* h16_out, float* sh_out, void* stream);
+/* the direction encoder alone: dirs f32[n,3] (any length; normalised inside) -> out f32[n,16], 16-byte aligned                                                  */
+int mirres_sh_encode(const float* dirs, long long n, float* out, void* stream);
+
+/* --------------------------------------------------------------------------------------------------------------------------------------------
  * The stage-0 ray-marching operators (raymarch.hip): torch-ngp's raymarching module (raymarching/src/raymarching.cu), fp32 only, and the upkeep of the
  * occupancy grid the marchers read (nerf/renderer.py:1438-1595).  The arithmetic is FIXED (csrc/device_march.hpp): no contraction, IEEE
  * division, the reference's own C++ promotions, mrf_exp where the reference has __expf.  Deviations: march_rays_train hands out point offsets as the exclusive

@@ -67,6 +67,10 @@ class DensityNet(C.Structure):
                 ("table", vp), ("w0", vp), ("w1", vp)]
 
 
+class RadianceNet(C.Structure):
+    _fields_ = [("grid", DensityNet), ("w1", vp), ("c0", vp), ("c1", vp), ("c2", vp)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int, vp)   # int halo(void* user, float* records, int sample, void* stream)
 
 
@@ -158,6 +162,8 @@ SIGNATURES = {
     "mirres_density_layout": (C.c_longlong, [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(DensityNet)]),
     "mirres_density_points": (C.c_int, [C.POINTER(DensityNet), vp, C.c_longlong, f32, vp, vp, vp]),
     "mirres_density_volume": (C.c_int, [C.POINTER(DensityNet), vp, C.c_int, vp, C.c_int, vp, C.c_int, f32, vp, C.c_int, f32, vp, vp]),
+    "mirres_radiance_points": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp, vp]),
+    "mirres_sh_encode": (C.c_int, [vp, C.c_longlong, vp, vp]),
     "mirres_rm_near_far": (C.c_int, [vp, vp, vp, C.c_longlong, f32, vp, vp, vp]),
     "mirres_rm_morton3d": (C.c_int, [vp, C.c_longlong, vp, vp]),
     "mirres_rm_morton3d_invert": (C.c_int, [vp, C.c_longlong, vp, vp]),

@@ -15,13 +15,17 @@ nvdiffrast behind it.
     v, t = remove_selected_verts(v, t, box, "inside")      # meshutils.py:159-181 (:663, :676)
     v, t = outer_shell(grid_vol, cas, bound, 256, thresh, aabb)                 # :642-676: one outer cascade up to (not including) cleaning
     export_outer_meshes(save_path, ckpt, bound=2)          # :632-698: mesh_1.ply ... for a checkpoint trained with bound > 1 (export_stage0(outer=True))
+    rf = RadianceField.from_checkpoint(ck, bound=1.0)      # NeRFNetwork.forward (nerf/network.py:146-174): + SH direction encoder + colour net, csrc/radiance.hip
+    sigma, rgb = rf.forward(x, d)                          # one fused query per point
+    out = render_stage0(rf, DensityGrid.from_checkpoint(ck), rays_o, rays_d)     # :714-717, 778-839: the inference branch of render -> image, depth, weights_sum
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
 when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
 collapses independent sets of edges round by round instead of one edge at a time from a global heap, without MeshLab's quality / normal / planar extras, and may
 end one face below the target; the density network is evaluated in fp32 (the reference: fp16 autocast), unfused, and a NaN coordinate counts as out of bounds;
 the outer cascades' vertices are fp32 from marching cubes on (the reference holds float64 until after decimation), and the --sdf / contracted outer mesh
-(:575-629) is not built.
+(:575-629) is not built; the radiance network likewise runs in fp32, its direction encoder with a fixed operation order and no FMA,
+and a zero or non-finite direction gives NaN as the reference's 0 / 0 does; of render only the inference branch is built.
 Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
 import ctypes as C
 import os
@@ -34,7 +38,8 @@ from ._lib import lib, check, ptr, stream_ptr
 
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
            "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "DensityGrid", "density_layout",
-           "synthetic_checkpoint", "export_stage0", "occupancy_volume", "remove_selected_verts", "outer_shell", "export_outer_meshes"]
+           "synthetic_checkpoint", "export_stage0", "occupancy_volume", "remove_selected_verts", "outer_shell", "export_outer_meshes",
+           "RadianceField", "render_stage0", "synthetic_radiance_checkpoint", "synthetic_radiance_color"]
 
 
 def _dev():
@@ -477,10 +482,9 @@ class DensityField:
         self.w1 = w1.detach().to(dev, torch.float32).contiguous()
         self.net.table, self.net.w0, self.net.w1 = self.table.data_ptr(), self.w0.data_ptr(), self.w1.data_ptr()
 
-    @classmethod
-    def from_checkpoint(cls, ckpt, bound=1.0, **layout):
-        """A torch-ngp stage-0 checkpoint dict (or its `model` state dict): encoder.embeddings [N, 2], encoder.offsets [17], sigma_net.0.weight [64, 32],
-        sigma_net.1.weight [16, 64].  per_level_scale is not stored in a checkpoint, so the layout is recomputed from `bound` and compared with the stored offsets."""
+    @staticmethod
+    def _checked_model(ckpt, bound, layout):
+        """What from_checkpoint refuses, before anything is copied -> (the model state dict, sigma_net.0.weight, sigma_net.1.weight)."""
         model = ckpt["model"] if "model" in ckpt else ckpt
         if any(k.startswith("encoder.encoder.") for k in model):
             raise NotImplementedError("this checkpoint's encoder is tiny-cuda-nn's (encoder.encoder.params, --tcnn): not supported, only torch-ngp's GridEncoder "
@@ -499,6 +503,13 @@ class DensityField:
             raise ValueError("sigma_net weights of %s and %s: the stage-0 density head is 32 -> 64 -> 16 without biases" % (tuple(w0.shape), tuple(w1.shape)))
         if any(k in model for k in ("sigma_net.0.bias", "sigma_net.1.bias")):
             raise ValueError("sigma_net has biases: the stage-0 density head is bias-free")
+        return model, w0, w1
+
+    @classmethod
+    def from_checkpoint(cls, ckpt, bound=1.0, **layout):
+        """A torch-ngp stage-0 checkpoint dict (or its `model` state dict): encoder.embeddings [N, 2], encoder.offsets [17], sigma_net.0.weight [64, 32],
+        sigma_net.1.weight [16, 64].  per_level_scale is not stored in a checkpoint, so the layout is recomputed from `bound` and compared with the stored offsets."""
+        model, w0, w1 = cls._checked_model(ckpt, bound, layout)
         return cls(model["encoder.embeddings"], w0, w1, bound=bound, **layout)
 
     def _points(self, x, want_feat):
@@ -647,6 +658,160 @@ class DensityGrid:
         return None
 
 
+SH_DIM, GEO_FEAT_DIM, COLOR_HIDDEN = 16, 15, 64      # encoder_dir's outputs (degree 4), geo_feat, the colour net's width (nerf/network.py:68-72, 98)
+
+
+class RadianceField(DensityField):
+    """The stage-0 radiance network on the device (csrc/radiance.hip): NeRFNetwork.forward(x, d) (nerf/network.py:146-174) in one fused query per point, table and
+    weights in fp32.  On top of DensityField's table and w0: w1 f32 [16, 64] (sigma_net.1.weight, all rows: row 0 is sigma, rows 1 .. 15 geo_feat), c0 f32 [64, 31]
+    (color_net.0.weight, input [sh(16), geo_feat(15)]), c1 f32 [64, 64], c2 f32 [3, 64]; no biases.  encoder_dir (spherical harmonics, degree 4) has no
+    parameters.  density, encode and volume are DensityField's, on the same table."""
+
+    def __init__(self, table, w0, w1, c0, c1, c2, bound=1.0, **layout):
+        w1, c0, c1, c2 = (torch.as_tensor(w) for w in (w1, c0, c1, c2))
+        if tuple(w1.shape) != (1 + GEO_FEAT_DIM, 64):
+            raise ValueError("RadianceField: sigma_net.1.weight of %s, expected [16, 64] (all rows: 1 .. 15 are geo_feat)" % (tuple(w1.shape),))
+        for name, w, shape in (("color_net.0.weight", c0, (COLOR_HIDDEN, SH_DIM + GEO_FEAT_DIM)), ("color_net.1.weight", c1, (COLOR_HIDDEN, COLOR_HIDDEN)),
+                               ("color_net.2.weight", c2, (3, COLOR_HIDDEN))):
+            if tuple(w.shape) != shape:
+                raise ValueError("RadianceField: %s of %s, expected %s" % (name, tuple(w.shape), list(shape)))
+        super().__init__(table, w0, w1, bound=bound, **layout)
+        dev = self.table.device
+        self.w1_full, self.c0, self.c1, self.c2 = (w.detach().to(dev, torch.float32).contiguous() for w in (w1, c0, c1, c2))
+        self.rnet = _lib.RadianceNet()
+        self.rnet.grid = self.net
+        self.rnet.w1, self.rnet.c0, self.rnet.c1, self.rnet.c2 = self.w1_full.data_ptr(), self.c0.data_ptr(), self.c1.data_ptr(), self.c2.data_ptr()
+
+    @classmethod
+    def from_checkpoint(cls, ckpt, bound=1.0, **layout):
+        """A torch-ngp stage-0 checkpoint dict (or its `model`): what DensityField.from_checkpoint reads and refuses, and color_net.{0,1,2}.weight of [64, 31],
+        [64, 64] and [3, 64] without biases."""
+        model, w0, w1 = cls._checked_model(ckpt, bound, layout)
+        keys = ["color_net.%d.weight" % l for l in range(3)]
+        for k in keys:
+            if k not in model:
+                raise KeyError("checkpoint has no %s: not a stage-0 radiance network" % k)
+        c0, c1, c2 = (torch.as_tensor(model[k]) for k in keys)
+        if tuple(c0.shape) != (64, 31) or tuple(c1.shape) != (64, 64) or tuple(c2.shape) != (3, 64):
+            raise ValueError("color_net weights of %s, %s and %s: the stage-0 colour net is 31 -> 64 -> 64 -> 3 without biases" % (tuple(c0.shape), tuple(c1.shape), tuple(c2.shape)))
+        if any(k.startswith("color_net.") and k.endswith(".bias") for k in model):
+            raise ValueError("color_net has biases: the stage-0 colour net is bias-free")
+        return cls(model["encoder.embeddings"], w0, w1, c0, c1, c2, bound=bound, **layout)
+
+    @staticmethod
+    def _n3(t, what):
+        t = torch.as_tensor(t).to(_dev(), torch.float32)
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("RadianceField: %s of %s, expected [n, 3]" % (what, tuple(t.shape)))
+        return t.contiguous()
+
+    def _query(self, x, d, want_sigma=True, want_aux=False):
+        """-> (sigma or None, rgb, h16 or None, sh or None): one launch."""
+        x, d = self._n3(x, "positions"), self._n3(d, "directions")
+        if x.shape[0] != d.shape[0]:
+            raise ValueError("RadianceField: %d positions and %d directions" % (x.shape[0], d.shape[0]))
+        n = int(x.shape[0])
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)
+        sigma = new(n) if want_sigma else None
+        rgb = new(n, 3)
+        h16, sh = (new(n, 1 + GEO_FEAT_DIM), new(n, SH_DIM)) if want_aux else (None, None)
+        p = (lambda t: ptr(t) if (t is not None and n) else None)
+        check(lib().mirres_radiance_points(C.byref(self.rnet), p(x), p(d), n, self.bound, p(sigma), p(rgb), p(h16), p(sh), stream_ptr()), "mirres_radiance_points")
+        return sigma, rgb, h16, sh
+
+    def forward(self, x, d):
+        """x [n, 3], d [n, 3] (any length; the encoder normalises) -> (sigma f32 [n], rgb f32 [n, 3]); sigma has DensityField.density's bits."""
+        return self._query(x, d)[:2]
+
+    def rgb(self, x, d):
+        """NeRFNetwork.rgb: the colour alone, with forward's bits."""
+        return self._query(x, d, want_sigma=False)[1]
+
+    def sh(self, d):
+        """d [n, 3] -> encoder_dir's output f32 [n, 16]; NaN for a zero or non-finite direction (the reference's 0 / 0)."""
+        d = self._n3(d, "directions")
+        n = int(d.shape[0])
+        out = torch.empty((n, SH_DIM), dtype=torch.float32, device=d.device)
+        check(lib().mirres_sh_encode(ptr(d) if n else None, n, ptr(out) if n else None, stream_ptr()), "mirres_sh_encode")
+        return out
+
+
+def _safe_normalize(x, eps=1e-20):
+    """nerf/utils.py:43-44."""
+    return x / torch.sqrt(torch.clamp(torch.sum(x * x, -1, keepdim=True), min=eps))
+
+
+def _bg_color(bg_color, N):
+    """None -> 1; a scalar, [3] or [N, 3] -> what broadcasts against image [N, 3] (a tensor stays where it is)."""
+    if bg_color is None:
+        return 1
+    if isinstance(bg_color, (int, float)):
+        return float(bg_color)
+    bg = torch.as_tensor(bg_color)
+    if bg.dim() == 0 or tuple(bg.shape) in ((3,), (N, 3)):
+        return bg
+    raise ValueError("render_stage0: bg_color of %s, expected a scalar, [3] or [%d, 3]" % (tuple(bg.shape), N))
+
+
+@torch.no_grad()
+def render_stage0(field, grid, rays_o, rays_d, bg_color=None, dt_gamma=0, max_steps=1024, T_thresh=1e-4, cam_near_far=None, perturb=False, min_near=None, aabb=None):
+    """The INFERENCE branch of NeRFRenderer.render (nerf/renderer.py:714-717, 778-839) over the ray-marching operators -> {"image" [N, 3], "depth" [N],
+    "weights_sum" [N]}: near_far_from_aabb (aabb: 6 values, default the grid's aabb_train; min_near: default the grid's), the optional cam_near_far [N, 2] clamp,
+    then while step < max_steps with n_step = max(min(N // n_alive, 8), 1): march_rays (perturb on the first step only) -> safe_normalize(dirs) in torch as the
+    reference writes it -> field.forward -> composite_rays -> compaction of rays_alive; last image + (1 - weights_sum) * bg_color (None: 1; a scalar, [3] or [N, 3]).
+    field: a RadianceField; grid: a DensityGrid with its bitfield.  rays_o, rays_d [..., 3]; the outputs are flat.
+    Not built: the training branch (march_rays_train / composite_rays_train with gradients), --sdf and individual_codes."""
+    from . import raymarching as RM
+    if not isinstance(field, RadianceField):
+        raise TypeError("render_stage0: field must be a RadianceField, got %s" % type(field).__name__)
+    if not isinstance(grid, DensityGrid):
+        raise TypeError("render_stage0: grid must be a DensityGrid, got %s" % type(grid).__name__)
+    max_steps = int(max_steps)
+    if max_steps < 1:
+        raise ValueError("render_stage0: max_steps %d" % max_steps)
+    rays_o, rays_d = torch.as_tensor(rays_o), torch.as_tensor(rays_d)
+    if rays_o.shape != rays_d.shape or rays_o.dim() < 1 or rays_o.shape[-1] != 3:
+        raise ValueError("render_stage0: rays_o %s and rays_d %s, expected two [..., 3] of one shape" % (tuple(rays_o.shape), tuple(rays_d.shape)))
+    N = int(rays_o.numel() // 3)
+    if cam_near_far is not None:
+        cam_near_far = torch.as_tensor(cam_near_far)
+        if tuple(cam_near_far.shape) != (N, 2):
+            raise ValueError("render_stage0: cam_near_far of %s, expected [%d, 2]" % (tuple(cam_near_far.shape), N))
+    if aabb is not None and torch.as_tensor(aabb).numel() != 6:
+        raise ValueError("render_stage0: aabb of %d values, expected 6" % torch.as_tensor(aabb).numel())
+    bg = _bg_color(bg_color, N)
+    dev = _dev()
+    if torch.is_tensor(bg):
+        bg = bg.to(dev, torch.float32)
+    rays_o = rays_o.to(dev, torch.float32).contiguous().view(-1, 3)
+    rays_d = rays_d.to(dev, torch.float32).contiguous().view(-1, 3)
+    box = grid.aabb_train if aabb is None else torch.as_tensor(aabb).to(dev, torch.float32).reshape(6)
+    nears, fars = RM.near_far_from_aabb(rays_o, rays_d, box, grid.min_near if min_near is None else float(min_near))
+    if cam_near_far is not None:
+        cam_near_far = cam_near_far.to(dev, torch.float32)
+        nears = torch.maximum(nears, cam_near_far[:, 0])
+        fars = torch.minimum(fars, cam_near_far[:, 1])
+    weights_sum = torch.zeros(N, dtype=torch.float32, device=dev)
+    depth = torch.zeros(N, dtype=torch.float32, device=dev)
+    image = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    rays_alive = torch.arange(N, dtype=torch.int32, device=dev)
+    rays_t = nears.clone()
+    step = 0
+    while step < max_steps:
+        n_alive = rays_alive.shape[0]
+        if n_alive <= 0:
+            break
+        n_step = max(min(N // n_alive, 8), 1)
+        xyzs, dirs, ts = RM.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, grid.bound, False, grid.density_bitfield, grid.cascade, grid.grid_size,
+                                       nears, fars, perturb if step == 0 else False, dt_gamma, max_steps)
+        sigmas, rgbs = field.forward(xyzs, _safe_normalize(dirs))
+        RM.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, ts, weights_sum, depth, image, T_thresh, False)
+        rays_alive = rays_alive[rays_alive >= 0]
+        step += n_step
+    image = image + (1 - weights_sum).unsqueeze(-1) * bg
+    return {"image": image, "depth": depth, "weights_sum": weights_sum}
+
+
 def _synthetic_outer_row(S, k, c, A):
     """Row k >= 1 of synthetic_checkpoint's density_grid in [x][y][z] order: the scene at the centres of cascade k's cells (world = normalised * 2^k)."""
     cc = (np.arange(S, dtype=np.float64) + 0.5) / S * 2.0 - 1.0
@@ -706,6 +871,51 @@ def synthetic_checkpoint(S=16, radius=0.6, cascades=1):
         b = float(2 ** (cascades - 1))
         ck["model"]["density_grid"] = torch.from_numpy(np.stack(rows, 0))
         ck["model"]["aabb_train"] = torch.tensor([-b, -b, -b, b, b, b], dtype=torch.float32)
+    return ck
+
+
+# synthetic_radiance_checkpoint's constants: the fp32 values of the reference's SH literals for l = 0 and l = 1, and the gains of the three channels
+SYN_SH0, SYN_SH1 = float(np.float32(0.28209479177387814)), float(np.float32(0.48860251190291987))
+SYN_KR, SYN_KG, SYN_KB, SYN_BIAS = 4.0, 4.0, 2.0, 4.0
+
+
+def synthetic_radiance_color(d, feat0):
+    """synthetic_radiance_checkpoint's closed form in float64 numpy: d [n, 3] directions of any non-zero length, feat0 [n] the encoder's feature 0 (level 0,
+    channel 0: trilinear(2 - |x|)) at the positions -> rgb [n, 3]."""
+    d = np.asarray(d, np.float64); f = np.asarray(feat0, np.float64)
+    u = d / np.sqrt((d * d).sum(axis=1, keepdims=True))
+    sig = lambda h: 1.0 / (1.0 + np.exp(-h))
+    return np.stack([sig(SYN_KR * SYN_SH1 * u[:, 0]), sig(SYN_KG * SYN_SH1 * u[:, 2]), sig(SYN_KB * (1.5 * f - SYN_BIAS * SYN_SH0))], axis=1)
+
+
+def synthetic_radiance_checkpoint(S=16, radius=0.6):
+    """synthetic_checkpoint(S, radius) with a colour net whose output is a closed form, for tests and smoke runs.  Everything the density reads is
+    synthetic_checkpoint's (table, sigma_net.0.weight, row 0 of sigma_net.1.weight, density_grid, mean_density): sigma is unchanged.  With u = d / |d| the unit view
+    direction, F(x) = the encoder's feature 0 (trilinear(2 - |x|) on level 0), SH0 = fp32(0.28209479177387814) and SH1 = fp32(0.48860251190291987):
+        r = sigmoid(4 * SH1 * u_x)                      direction alone: - 4 * sh[3], sh[3] = - SH1 * u_x
+        g = sigmoid(4 * SH1 * u_z)                      direction alone: + 4 * sh[2], sh[2] = + SH1 * u_z
+        b = sigmoid(2 * (1.5 * F(x) - 4 * SH0))         position alone, through geo_feat[14] = 1.5 * F(x) and the constant sh[0] = SH0 in the place of a bias
+    (synthetic_radiance_color).  How: row 15 of sigma_net.1.weight is [1, 0, ...], so geo_feat[14] = relu(1.5 F) = 1.5 F (F > 0 in the cube) — input 16 + 14 = 30 of
+    the colour net, which pins the [sh, geo_feat] order and the 1 + 14 offset; a value t passes both hidden ReLU layers as the pair relu(t), relu(-t) (neurons 0 / 1:
+    t = sh[3]; 2 / 3: t = sh[2]; 4 / 5: t = geo_feat[14] - 4 sh[0]; color_net.1.weight is the identity on them) and color_net.2.weight recombines
+    k * (relu(t) - relu(-t)) = k * t.  Every weight is a small integer: in fp32 the pre-activations of r and g are exact products of the encoder's sh."""
+    ck = synthetic_checkpoint(S, radius)
+    m = ck["model"]
+    w1 = m["sigma_net.1.weight"].clone(); w1[15, 0] = 1.0
+    c0 = torch.zeros((COLOR_HIDDEN, SH_DIM + GEO_FEAT_DIM), dtype=torch.float32)
+    c0[0, 3], c0[1, 3] = 1.0, -1.0
+    c0[2, 2], c0[3, 2] = 1.0, -1.0
+    c0[4, 0], c0[4, SH_DIM + 14] = -SYN_BIAS, 1.0
+    c0[5, 0], c0[5, SH_DIM + 14] = SYN_BIAS, -1.0
+    c1 = torch.zeros((COLOR_HIDDEN, COLOR_HIDDEN), dtype=torch.float32)
+    for k in range(6):
+        c1[k, k] = 1.0
+    c2 = torch.zeros((3, COLOR_HIDDEN), dtype=torch.float32)
+    c2[0, 0], c2[0, 1] = -SYN_KR, SYN_KR
+    c2[1, 2], c2[1, 3] = SYN_KG, -SYN_KG
+    c2[2, 4], c2[2, 5] = SYN_KB, -SYN_KB
+    m["sigma_net.1.weight"] = w1
+    m["color_net.0.weight"], m["color_net.1.weight"], m["color_net.2.weight"] = c0, c1, c2
     return ck
 
 
