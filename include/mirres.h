@@ -559,6 +559,19 @@ int mirres_radiance_points(const mirres_radiance_t* net, const float* pos, const
                            float* h16_out, float* sh_out, void* stream);
 /* the direction encoder alone: dirs f32[n,3] (any length; normalised inside) -> out f32[n,16], 16-byte aligned                                                  */
 int mirres_sh_encode(const float* dirs, long long n, float* out, void* stream);
+/* The adjoint of mirres_radiance_points (radiance_bwd.hip): pos, dirs f32[n,3], grad_sigma f32[n] (NULL: zeros), grad_rgb f32[n,3] -> the gradients of the six
+ * parameters, all fp32 and all ACCUMULATED INTO (+=; the caller zeroes them): grad_table [entries,2], grad_w0 [64,32], grad_w1 [16,64], grad_c0 [64,31],
+ * grad_c1 [64,64], grad_c2 [3,64].  The forward is recomputed from pos / dirs; nothing is taped.  d_pre = grad_rgb rgb (1 - rgb); a ReLU passes the cotangent where
+ * its output is > 0; d_h16[0] = grad_sigma mrf_exp(clamp(h16[0], -15, 15)) (trunc_exp's backward, activation.py:14-16), d_h16[1..15] = the colour net's d_in[16..30].
+ * A point out of bounds (or not finite) scatters nothing and adds 0 to grad_w0 / grad_w1; its colour path still reaches grad_c0/1/2.  Positions and directions get
+ * no gradient.  The weight gradients carry no atomics: min(ceil(n / 256), max_blocks; 0: 1024) blocks write one partial each to workspace [blocks][9344] f32 and a
+ * second kernel adds them in block order, so equal inputs and an equal max_blocks give equal bits.  The table gradient is scattered with fp32 atomics and varies in
+ * its last bits from run to run.  workspace: device memory of at least mirres_radiance_bwd_workspace_bytes(n, max_blocks) bytes, 4-byte aligned; its contents need
+ * not be kept.  n == 0 launches nothing and touches nothing.                                                                                                    */
+long long mirres_radiance_bwd_workspace_bytes(long long n, int max_blocks);
+int mirres_radiance_points_bwd(const mirres_radiance_t* net, const float* pos, const float* dirs, long long n, float bound, const float* grad_sigma,
+                               const float* grad_rgb, float* grad_table, float* grad_w0, float* grad_w1, float* grad_c0, float* grad_c1, float* grad_c2,
+                               void* workspace, long long workspace_bytes, int max_blocks, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------------------------------------------
  * The stage-0 ray-marching operators (raymarch.hip): torch-ngp's raymarching module (raymarching/src/raymarching.cu), fp32 only, and the upkeep of the

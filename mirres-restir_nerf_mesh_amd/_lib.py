@@ -164,6 +164,8 @@ SIGNATURES = {
     "mirres_density_volume": (C.c_int, [C.POINTER(DensityNet), vp, C.c_int, vp, C.c_int, vp, C.c_int, f32, vp, C.c_int, f32, vp, vp]),
     "mirres_radiance_points": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp, vp]),
     "mirres_sh_encode": (C.c_int, [vp, C.c_longlong, vp, vp]),
+    "mirres_radiance_bwd_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "mirres_radiance_points_bwd": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_int, vp]),
     "mirres_rm_near_far": (C.c_int, [vp, vp, vp, C.c_longlong, f32, vp, vp, vp]),
     "mirres_rm_morton3d": (C.c_int, [vp, C.c_longlong, vp, vp]),
     "mirres_rm_morton3d_invert": (C.c_int, [vp, C.c_longlong, vp, vp]),

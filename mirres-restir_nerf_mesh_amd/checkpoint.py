@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 __all__ = ["read_ply", "write_ply", "load_stage0_mesh", "read_checkpoint", "apply_checkpoint", "save_checkpoint", "material_config",
-           "resolve_material_config", "material_field_args", "cascade_of_bound"]
+           "resolve_material_config", "material_field_args", "cascade_of_bound", "save_stage0_checkpoint"]
 
 _PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H", "int": "i", "int32": "i",
               "uint": "I", "uint32": "I", "float": "f", "float32": "f", "double": "d", "float64": "d"}
@@ -271,3 +271,37 @@ def save_checkpoint(path, mlp_mat, vertices_offsets, light_base, epoch=0, global
             raise KeyError("train_state: unknown entry %r (expected %s)" % (k, ", ".join(TRAIN_STATE_KEYS)))
         state[k] = v
     torch.save(state, path)
+
+
+STAGE0_WEIGHT_KEYS = ("encoder.embeddings", "sigma_net.0.weight", "sigma_net.1.weight", "color_net.0.weight", "color_net.1.weight", "color_net.2.weight")
+
+
+def save_stage0_checkpoint(path, field, grid, epoch=0, global_step=0, optimizer=None, ema=None):
+    """A stage-0 checkpoint in the reference's layout (Trainer.save_checkpoint, nerf/utils.py:1843-1920, of a NeRFNetwork with --cuda_ray), from a
+    stage0.RadianceField and a stage0.DensityGrid: `model` holds encoder.embeddings [entries, 2], encoder.offsets i32 [levels + 1], sigma_net.{0,1}.weight,
+    color_net.{0,1,2}.weight, density_grid [cascade, H^3], density_bitfield u8, aabb_train and aabb_infer [6]; the top level mean_density, epoch, global_step, stats.
+    optimizer: an optimiser whose state_dict goes under `optimizer`.  ema: a dict with `decay`, `num_updates` and `shadow_params` (six tensors in the order of
+    RadianceField.PARAMETER_NAMES): `model` then holds the SHADOW weights, as the reference saves the averaged model (:1894-1897), and `ema` keeps the dict with the
+    field's own weights as `collected_params`, from which a resumed run continues.  Everything is written as host tensors."""
+    host = lambda t: t.detach().to("cpu").clone()
+    own = [host(getattr(field, k)) for k in field.PARAMETER_NAMES]
+    weights = own
+    if ema is not None:
+        weights = [host(t) for t in ema["shadow_params"]]
+        if [tuple(w.shape) for w in weights] != [tuple(w.shape) for w in own]:
+            raise ValueError("save_stage0_checkpoint: ema shadow_params do not have the shapes of the field's parameters")
+    model = dict(zip(STAGE0_WEIGHT_KEYS, weights))
+    model["encoder.offsets"] = torch.tensor([int(field.net.offsets[k]) for k in range(field.net.num_levels + 1)], dtype=torch.int32)
+    model["density_grid"] = host(grid.density_grid)
+    model["density_bitfield"] = host(grid.density_bitfield)
+    model["aabb_train"] = host(grid.aabb_train)
+    model["aabb_infer"] = host(grid.aabb_train)
+    model = {k: model[k] for k in ("aabb_train", "aabb_infer", "density_grid", "density_bitfield", "encoder.embeddings", "encoder.offsets") + STAGE0_WEIGHT_KEYS[1:]}
+    state = {"epoch": int(epoch), "global_step": int(global_step), "stats": {}, "mean_density": float(grid.mean_density), "model": model}
+    if optimizer is not None:
+        state["optimizer"] = optimizer.state_dict()
+    if ema is not None:
+        state["ema"] = {"decay": float(ema["decay"]), "num_updates": int(ema["num_updates"]), "shadow_params": weights, "collected_params": own}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(state, path)
+    return state

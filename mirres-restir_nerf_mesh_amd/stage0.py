@@ -18,6 +18,8 @@ nvdiffrast behind it.
     rf = RadianceField.from_checkpoint(ck, bound=1.0)      # NeRFNetwork.forward (nerf/network.py:146-174): + SH direction encoder + colour net, csrc/radiance.hip
     sigma, rgb = rf.forward(x, d)                          # one fused query per point
     out = render_stage0(rf, DensityGrid.from_checkpoint(ck), rays_o, rays_d)     # :714-717, 778-839: the inference branch of render -> image, depth, weights_sum
+    sigma, rgb = rf.forward_train(x, d)                    # the same bits, differentiable in rf.parameters(): csrc/radiance_bwd.hip recomputes and adjoins
+    out = render_stage0_train(rf, grid, rays_o, rays_d)    # :735-773, 830-838: the training branch (march_rays_train, composite_rays_train)
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
 when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
@@ -25,7 +27,8 @@ collapses independent sets of edges round by round instead of one edge at a time
 end one face below the target; the density network is evaluated in fp32 (the reference: fp16 autocast), unfused, and a NaN coordinate counts as out of bounds;
 the outer cascades' vertices are fp32 from marching cubes on (the reference holds float64 until after decimation), and the --sdf / contracted outer mesh
 (:575-629) is not built; the radiance network likewise runs in fp32, its direction encoder with a fixed operation order and no FMA,
-and a zero or non-finite direction gives NaN as the reference's 0 / 0 does; of render only the inference branch is built.
+and a zero or non-finite direction gives NaN as the reference's 0 / 0 does; training runs in fp32 without autocast or a gradient scaler, and the table's
+gradient is summed by atomics in no fixed order.
 Tensors live on the current device; every function returns device tensors (vertices f32 [V, 3], triangles i32 [T, 3])."""
 import ctypes as C
 import os
@@ -39,7 +42,7 @@ from ._lib import lib, check, ptr, stream_ptr
 __all__ = ["marching_cubes", "morton_indices", "unpack_density_grid", "select_iso", "mask_by_density_grid", "seen_faces", "mark_unseen_triangles", "dilate_selection",
            "compact_mesh", "remove_masked_trigs", "face_components", "clean_mesh", "decimate_round", "decimate_mesh", "index_to_world", "synthetic_volume", "DensityField", "DensityGrid", "density_layout",
            "synthetic_checkpoint", "export_stage0", "occupancy_volume", "remove_selected_verts", "outer_shell", "export_outer_meshes",
-           "RadianceField", "render_stage0", "synthetic_radiance_checkpoint", "synthetic_radiance_color"]
+           "RadianceField", "render_stage0", "render_stage0_train", "synthetic_radiance_checkpoint", "synthetic_radiance_color"]
 
 
 def _dev():
@@ -678,6 +681,11 @@ class RadianceField(DensityField):
         super().__init__(table, w0, w1, bound=bound, **layout)
         dev = self.table.device
         self.w1_full, self.c0, self.c1, self.c2 = (w.detach().to(dev, torch.float32).contiguous() for w in (w1, c0, c1, c2))
+        # DensityField kept a copy of row 0; here the density head reads row 0 of w1_full itself (the first 64 floats of a contiguous [16, 64]), so that density()
+        # and DensityGrid.update follow an optimiser's in-place steps on w1_full
+        self.w1 = self.w1_full[0]
+        self.net.w1 = self.w1_full.data_ptr()
+        self.bwd_max_blocks = 0                          # forward_train's backward: the grid of mirres_radiance_points_bwd (0: the library's default)
         self.rnet = _lib.RadianceNet()
         self.rnet.grid = self.net
         self.rnet.w1, self.rnet.c0, self.rnet.c1, self.rnet.c2 = self.w1_full.data_ptr(), self.c0.data_ptr(), self.c1.data_ptr(), self.c2.data_ptr()
@@ -735,6 +743,76 @@ class RadianceField(DensityField):
         check(lib().mirres_sh_encode(ptr(d) if n else None, n, ptr(out) if n else None, stream_ptr()), "mirres_sh_encode")
         return out
 
+    PARAMETER_NAMES = ("table", "w0", "w1_full", "c0", "c1", "c2")
+
+    def parameters(self):
+        """The six trainable tensors (PARAMETER_NAMES: table, w0, w1_full, c0, c1, c2) as leaf tensors with requires_grad, for an optimiser.  They are the tensors the
+        kernels read: in-place updates (optimizer.step()) are seen by every later query, density() and DensityGrid.update included; assigning a new tensor is not."""
+        return [getattr(self, k).requires_grad_(True) for k in self.PARAMETER_NAMES]
+
+    @classmethod
+    def init_random(cls, bound=1.0, seed=0, **layout):
+        """A freshly initialised network as the reference builds it: the table U(-1e-4, 1e-4) (gridencoder/grid.py reset_parameters), the five bias-free matrices
+        nn.Linear's default U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)), all from one host generator seeded with `seed`."""
+        _, total = density_layout(bound, **layout)
+        g = torch.Generator().manual_seed(int(seed))
+        table = (torch.rand((total, 2), generator=g, dtype=torch.float32) * 2 - 1) * 1e-4
+        lin = lambda o, i: (torch.rand((o, i), generator=g, dtype=torch.float32) * 2 - 1) / float(np.sqrt(i))
+        return cls(table, lin(64, 2 * DENSITY_LEVELS), lin(1 + GEO_FEAT_DIM, 64), lin(COLOR_HIDDEN, SH_DIM + GEO_FEAT_DIM), lin(COLOR_HIDDEN, COLOR_HIDDEN),
+                   lin(3, COLOR_HIDDEN), bound=bound, **layout)
+
+    def backward_points(self, x, d, grad_sigma, grad_rgb, grads=None, max_blocks=None):
+        """The adjoint of forward (csrc/radiance_bwd.hip), one mirres_radiance_points_bwd call: x, d [n, 3], grad_sigma [n] or None (zeros), grad_rgb [n, 3] ->
+        the gradients of PARAMETER_NAMES, fp32.  grads: six tensors to ADD to (default: fresh zeros).  The weight gradients are bit-reproducible for one max_blocks
+        (None: self.bwd_max_blocks); the table gradient is scattered with atomics and is not.  Positions and directions get no gradient."""
+        x, d = self._n3(x, "positions"), self._n3(d, "directions")
+        n = int(x.shape[0])
+        grad_rgb = torch.as_tensor(grad_rgb).to(x.device, torch.float32).contiguous()
+        if d.shape[0] != n or tuple(grad_rgb.shape) != (n, 3):
+            raise ValueError("RadianceField: %d positions, %d directions and grad_rgb of %s" % (n, d.shape[0], tuple(grad_rgb.shape)))
+        if grad_sigma is not None:
+            grad_sigma = torch.as_tensor(grad_sigma).to(x.device, torch.float32).contiguous()
+            if tuple(grad_sigma.shape) != (n,):
+                raise ValueError("RadianceField: grad_sigma of %s for %d points" % (tuple(grad_sigma.shape), n))
+        params = [getattr(self, k) for k in self.PARAMETER_NAMES]
+        if grads is None:
+            grads = [torch.zeros(w.shape, dtype=torch.float32, device=x.device) for w in params]
+        for g, w, k in zip(grads, params, self.PARAMETER_NAMES):
+            if g.shape != w.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != w.device:
+                raise ValueError("RadianceField: the gradient buffer of %s must be a contiguous fp32 %s on the field's device" % (k, tuple(w.shape)))
+        mb = int(self.bwd_max_blocks if max_blocks is None else max_blocks)
+        L = lib()
+        nbytes = int(L.mirres_radiance_bwd_workspace_bytes(n, mb))
+        if nbytes < 0:
+            check(nbytes, "mirres_radiance_bwd_workspace_bytes")
+        ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+        p = (lambda t: ptr(t) if (t is not None and n) else None)
+        check(L.mirres_radiance_points_bwd(C.byref(self.rnet), p(x), p(d), n, self.bound, p(grad_sigma), p(grad_rgb), *(ptr(g) for g in grads), ptr(ws), nbytes, mb,
+                                           stream_ptr()), "mirres_radiance_points_bwd")
+        return grads
+
+    def forward_train(self, x, d):
+        """forward with gradients: (sigma [n], rgb [n, 3]) with forward's bits, differentiable in parameters() (not in x or d).  The forward is one
+        mirres_radiance_points launch; nothing but x and d is kept, the backward recomputes (backward_points)."""
+        return _RadianceTrain.apply(self, self._n3(x, "positions").detach(), self._n3(d, "directions").detach(), *[getattr(self, k) for k in self.PARAMETER_NAMES])
+
+
+class _RadianceTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, x, d, *params):
+        sigma, rgb = field._query(x, d)[:2]
+        ctx.field = field
+        ctx.save_for_backward(x, d)
+        return sigma, rgb
+
+    @staticmethod
+    def backward(ctx, grad_sigma, grad_rgb):
+        x, d = ctx.saved_tensors
+        if grad_rgb is None:
+            grad_rgb = torch.zeros((x.shape[0], 3), dtype=torch.float32, device=x.device)
+        grads = ctx.field.backward_points(x, d, grad_sigma, grad_rgb)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
 
 def _safe_normalize(x, eps=1e-20):
     """nerf/utils.py:43-44."""
@@ -760,7 +838,7 @@ def render_stage0(field, grid, rays_o, rays_d, bg_color=None, dt_gamma=0, max_st
     then while step < max_steps with n_step = max(min(N // n_alive, 8), 1): march_rays (perturb on the first step only) -> safe_normalize(dirs) in torch as the
     reference writes it -> field.forward -> composite_rays -> compaction of rays_alive; last image + (1 - weights_sum) * bg_color (None: 1; a scalar, [3] or [N, 3]).
     field: a RadianceField; grid: a DensityGrid with its bitfield.  rays_o, rays_d [..., 3]; the outputs are flat.
-    Not built: the training branch (march_rays_train / composite_rays_train with gradients), --sdf and individual_codes."""
+    The training branch is render_stage0_train.  Not built: --sdf and individual_codes."""
     from . import raymarching as RM
     if not isinstance(field, RadianceField):
         raise TypeError("render_stage0: field must be a RadianceField, got %s" % type(field).__name__)
@@ -810,6 +888,42 @@ def render_stage0(field, grid, rays_o, rays_d, bg_color=None, dt_gamma=0, max_st
         step += n_step
     image = image + (1 - weights_sum).unsqueeze(-1) * bg
     return {"image": image, "depth": depth, "weights_sum": weights_sum}
+
+
+def render_stage0_train(field, grid, rays_o, rays_d, bg_color=None, perturb=False, dt_gamma=0, max_steps=1024, T_thresh=1e-4, cam_near_far=None, noises=None):
+    """The TRAINING branch of NeRFRenderer.render (nerf/renderer.py:735-773, 830-838) -> {"image" [N, 3], "depth" [N], "weights_sum" [N], "weights" [M],
+    "num_points" M, "xyzs" [M, 3]}, differentiable in field.parameters(): near_far_from_aabb on the grid's aabb_train (min_near the grid's), the optional
+    cam_near_far [N, 2] clamp, march_rays_train (perturb; noises [N] in [0, 1) or None for torch.rand), safe_normalize(dirs), field.forward_train,
+    composite_rays_train, image + (1 - weights_sum) * bg_color (None: 1; a scalar, [3] or [N, 3]).  rays_o, rays_d [..., 3]; the outputs are flat."""
+    from . import raymarching as RM
+    if not isinstance(field, RadianceField):
+        raise TypeError("render_stage0_train: field must be a RadianceField, got %s" % type(field).__name__)
+    if not isinstance(grid, DensityGrid):
+        raise TypeError("render_stage0_train: grid must be a DensityGrid, got %s" % type(grid).__name__)
+    rays_o, rays_d = torch.as_tensor(rays_o), torch.as_tensor(rays_d)
+    if rays_o.shape != rays_d.shape or rays_o.dim() < 1 or rays_o.shape[-1] != 3:
+        raise ValueError("render_stage0_train: rays_o %s and rays_d %s, expected two [..., 3] of one shape" % (tuple(rays_o.shape), tuple(rays_d.shape)))
+    N = int(rays_o.numel() // 3)
+    bg = _bg_color(bg_color, N)
+    dev = _dev()
+    if torch.is_tensor(bg):
+        bg = bg.to(dev, torch.float32)
+    rays_o = rays_o.detach().to(dev, torch.float32).contiguous().view(-1, 3)
+    rays_d = rays_d.detach().to(dev, torch.float32).contiguous().view(-1, 3)
+    nears, fars = RM.near_far_from_aabb(rays_o, rays_d, grid.aabb_train, grid.min_near)
+    if cam_near_far is not None:
+        cam_near_far = torch.as_tensor(cam_near_far)
+        if tuple(cam_near_far.shape) != (N, 2):
+            raise ValueError("render_stage0_train: cam_near_far of %s, expected [%d, 2]" % (tuple(cam_near_far.shape), N))
+        cam_near_far = cam_near_far.to(dev, torch.float32)
+        nears = torch.maximum(nears, cam_near_far[:, 0])
+        fars = torch.minimum(fars, cam_near_far[:, 1])
+    xyzs, dirs, ts, rays = RM.march_rays_train(rays_o, rays_d, grid.bound, False, grid.density_bitfield, grid.cascade, grid.grid_size, nears, fars, perturb, dt_gamma,
+                                               max_steps, noises)
+    sigmas, rgbs = field.forward_train(xyzs, _safe_normalize(dirs))
+    weights, weights_sum, depth, image = RM.composite_rays_train(sigmas, rgbs, ts, rays, T_thresh, False)
+    image = image + (1 - weights_sum).unsqueeze(-1) * bg
+    return {"image": image, "depth": depth, "weights_sum": weights_sum, "weights": weights, "num_points": int(xyzs.shape[0]), "xyzs": xyzs}
 
 
 def _synthetic_outer_row(S, k, c, A):
