@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 
 namespace mr {
 
@@ -74,26 +75,19 @@ __global__ void __launch_bounds__(AL_BLOCK) k_compact_count(const float* __restr
     }
 }
 
-// exclusive scan of the AL_PARTS segment counts, offset by the pool's count, which then grows by the total (clamped to the capacity: state[2] reports the overflow)
+// exclusive scan (block_excl_scan, device_scan.hpp) of the AL_PARTS segment counts, offset by the pool's count, which then grows by the total (clamped to the capacity: state[2] reports the overflow)
 __global__ void __launch_bounds__(AL_BLOCK) k_compact_scan(u64* __restrict__ counts, u64* __restrict__ state, u64 cap) {
-    __shared__ u64 sh[AL_BLOCK];
+    __shared__ u64 sh[AL_BLOCK / 64];
     constexpr int PER = AL_PARTS / AL_BLOCK;
-    u64 v[PER], s = 0;
+    u64 v[PER], s = 0, all;
     for (int k = 0; k < PER; k++) { v[k] = counts[PER * threadIdx.x + k]; s += v[k]; }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < AL_BLOCK; off <<= 1) {
-        const u64 a = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0ULL;
-        __syncthreads();
-        sh[threadIdx.x] += a;
-        __syncthreads();
-    }
-    const u64 base = state[0];
-    u64 run = base + sh[threadIdx.x] - s;
+    const u64 excl = block_excl_scan<AL_BLOCK>(s, sh, all);
+    const u64 base = state[0];                              // every thread reads it before the barrier below, one writes it after
+    u64 run = base + excl;
     for (int k = 0; k < PER; k++) { counts[PER * threadIdx.x + k] = run; run += v[k]; }
     __syncthreads();
     if (threadIdx.x == AL_BLOCK - 1) {
-        const u64 total = base + sh[AL_BLOCK - 1];
+        const u64 total = base + all;
         if (total > cap) state[2] = 1;
         state[0] = total > cap ? cap : total;
     }

@@ -9,6 +9,7 @@
 //   mirres_texture_downsample  cv2's INTER_LINEAR at an integer factor.
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 
 namespace mr {
 
@@ -85,39 +86,26 @@ __global__ void __launch_bounds__(BK_BLOCK) k_uv_setup(const float* __restrict__
 }
 
 // exclusive scan of n u64 counts, in place, + the total in a[n]: 1024 per workgroup, the workgroup sums scanned by one workgroup, then added
+// (inside a workgroup: block_excl_scan, device_scan.hpp)
 #define BK_SCAN 1024
-MR_DEV unsigned long long block_exclusive(unsigned long long v, unsigned long long* sh, unsigned long long& total) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < BK_BLOCK; off <<= 1) {           // Hillis-Steele over 256 lanes (8 steps)
-        const unsigned long long a = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0ULL;
-        __syncthreads();
-        sh[threadIdx.x] += a;
-        __syncthreads();
-    }
-    total = sh[BK_BLOCK - 1];
-    const unsigned long long incl = sh[threadIdx.x];
-    __syncthreads();
-    return incl - v;
-}
 __global__ void __launch_bounds__(BK_BLOCK) k_scan_local(unsigned long long* __restrict__ a, int n, unsigned long long* __restrict__ sums) {
-    __shared__ unsigned long long sh[BK_BLOCK];
+    __shared__ unsigned long long sh[BK_BLOCK / 64];
     const size_t base = (size_t)blockIdx.x * BK_SCAN + 4 * threadIdx.x;
     unsigned long long v[4], s = 0;
     for (int k = 0; k < 4; k++) { v[k] = base + k < (size_t)n ? a[base + k] : 0ULL; s += v[k]; }
     unsigned long long total;
-    unsigned long long run = block_exclusive(s, sh, total);
+    unsigned long long run = block_excl_scan<BK_BLOCK>(s, sh, total);
     for (int k = 0; k < 4; k++) { if (base + k < (size_t)n) a[base + k] = run; run += v[k]; }
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 __global__ void __launch_bounds__(BK_BLOCK) k_scan_sums(unsigned long long* __restrict__ sums, int nb, unsigned long long* __restrict__ total_out) {
-    __shared__ unsigned long long sh[BK_BLOCK];
+    __shared__ unsigned long long sh[BK_BLOCK / 64];
     unsigned long long carry = 0;
     for (int b0 = 0; b0 < nb; b0 += BK_BLOCK) {               // nb <= 2^14: at most 64 rounds
         const int i = b0 + threadIdx.x;
         const unsigned long long v = i < nb ? sums[i] : 0ULL;
         unsigned long long total;
-        const unsigned long long ex = block_exclusive(v, sh, total);
+        const unsigned long long ex = block_excl_scan<BK_BLOCK>(v, sh, total);
         if (i < nb) sums[i] = carry + ex;
         carry += total;
     }

@@ -9,6 +9,7 @@
 //   * a packing pass that emits the 64-byte two-child traversal records used by bvh_trace.hip.
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include <cstring>
 #include <cstdarg>
 #include <cstdio>
@@ -109,7 +110,7 @@ __global__ void __launch_bounds__(256) k_morton(const float* __restrict__ ele, c
 // codes, equal codes in ascending element order (the hierarchy's delta() breaks ties by position, so stability is part of the node arrays). Here: four
 // 8-bit passes, each  histogram per 2048-key tile -> per digit: exclusive scan over the tiles + total -> stable scatter.  Inside a tile a wave owns 512 consecutive keys
 // and takes them 64 at a time: the lanes holding the same digit find each other with eight ballots (wave64 match), the lowest of them bumps the wave's own
-// LDS counter of that digit, and a key's rank is  tile base of its digit + its digit's count in the waves before + in this wave's earlier rounds + in lower lanes.
+// LDS counter of that digit (wave_digit_rank, device_scan.hpp, where the scans of both kernels below live too), and a key's rank is  tile base of its digit + its digit's count in the waves before + in this wave's earlier rounds + in lower lanes.
 #define MR_RS_BLOCK 256
 #define MR_RS_ITEMS 8
 #define MR_RS_TILE (MR_RS_BLOCK * MR_RS_ITEMS)
@@ -130,22 +131,13 @@ __global__ void __launch_bounds__(MR_RS_BLOCK) k_rs_hist(const uint32_t* __restr
 __global__ void __launch_bounds__(256) k_rs_scan(uint32_t* __restrict__ hist, int nb, uint32_t* __restrict__ totals) {
     __shared__ uint32_t wsum[4];
     uint32_t* h = hist + (size_t)blockIdx.x * nb;
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     uint32_t running = 0u;
     for (int c0 = 0; c0 < nb; c0 += 256) {
         const int i = c0 + (int)threadIdx.x;
-        const uint32_t x = i < nb ? h[i] : 0u;
-        uint32_t inc = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const uint32_t t = wsum[w]; if (w < wave) before += t; all += t; }
-        if (i < nb) h[i] = running + before + inc - x;
+        uint32_t all;
+        const uint32_t before = block_excl_scan<256>(i < nb ? h[i] : 0u, wsum, all);
+        if (i < nb) h[i] = running + before;
         running += all;
-        __syncthreads();
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = running;
 }
@@ -155,7 +147,6 @@ __global__ void __launch_bounds__(MR_RS_BLOCK) k_rs_scatter(const uint32_t* __re
     __shared__ uint32_t wh[MR_RS_BLOCK / 64][256];
     __shared__ uint32_t dsum[MR_RS_BLOCK / 64];
     const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     for (int w = 0; w < MR_RS_BLOCK / 64; w++) wh[w][threadIdx.x] = 0u;
     __syncthreads();
     const int base = blockIdx.x * MR_RS_TILE + wave * (64 * MR_RS_ITEMS);
@@ -165,24 +156,13 @@ __global__ void __launch_bounds__(MR_RS_BLOCK) k_rs_scatter(const uint32_t* __re
         const int idx = base + i * 64 + lane;
         const bool valid = idx < n;
         k[i] = valid ? kin[idx] : 0xffffffffu; v[i] = valid ? vin[idx] : 0u;
-        const uint32_t d = (k[i] >> shift) & 255u;
-        uint64_t m = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) { const bool bit = (d >> b) & 1u; const uint64_t bal = __ballot(bit); m &= bit ? bal : ~bal; }
-        // m = the valid lanes of this round with the same digit (this lane included when it is valid)
-        const int leader = valid ? __builtin_ctzll(m) : lane;
-        uint32_t prev = 0u;
-        if (valid && lane == leader) { prev = wh[wave][d]; wh[wave][d] = prev + (uint32_t)__popcll(m); }
-        prev = (uint32_t)__shfl((int)prev, leader, 64);
-        r[i] = prev + (uint32_t)__popcll(m & lt_mask);
+        r[i] = wave_digit_rank((k[i] >> shift) & 255u, valid, wh[wave]);
         __syncthreads();                                                  // the next round's leaders read what this round's leaders wrote
     }
     {   // per digit (thread d = digit d): where each wave's keys start in the output = all keys with smaller digits + this digit's keys in the tiles before
         // + its counts in the waves before
         const uint32_t tot = totals[threadIdx.x];
-        uint32_t inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+        const uint32_t inc = wave_incl_scan(tot);
         if (lane == 63) dsum[wave] = inc;
         __syncthreads();
         uint32_t run = inc - tot + offs[(size_t)threadIdx.x * nb + blockIdx.x];

@@ -18,6 +18,7 @@
 //   * rays come from compacted queues; blocks grid-stride over the queue, count read on device (no host sync).
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include <cstdlib>
 
 namespace mr {

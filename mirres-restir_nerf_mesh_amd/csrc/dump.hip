@@ -7,6 +7,7 @@
 // (nerf/renderer.py:179), it is not the ReSTIR path's bvh_hit with its t-blind triangle test.
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 
 namespace mr {
 

@@ -9,6 +9,7 @@
 // (k_mlp_mfma, the production path) runs the SAME chains on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32, K = 2 per step in ascending k): same bits.
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include "device_grid.hpp"
 #include <hip/hip_fp16.h>
 #include <cmath>
@@ -307,7 +308,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_active_from_live(const float* __re
 // ---- LSD radix sort (8-bit digits, one pass per key byte) of (key, slot) pairs whose count lives on the device. No global atomics (a first version that counted and
 // scattered with one atomic per element cost 2.9 ms per launch for 7.5 M entries, more than the ordered gathers saved): a fixed grid of MR_LS_GRID workgroups,
 // each owning a contiguous run of 2048-key tiles — digit histogram of its run -> per digit: exclusive scan over the workgroups -> stable scatter walking the run
-// tile by tile with the wave64 digit matching of bvh_build.hip's sort (a key's rank = running base of its digit in this workgroup + the digit's count in the waves
+// tile by tile with the wave64 digit matching bvh_build.hip's sort uses (wave_digit_rank and the scans: device_scan.hpp; a key's rank = running base of its digit in this workgroup + the digit's count in the waves
 // before + in this wave's earlier rounds + in lower lanes).
 #define MR_LS_GRID 1024
 #define MR_LS_TILE 2048
@@ -328,24 +329,15 @@ __global__ void __launch_bounds__(MR_BLOCK) k_ls_hist(const uint32_t* __restrict
 }
 // per digit (one workgroup each): exclusive scan over the MR_LS_GRID workgroup counters in place + the digit's total
 __global__ void __launch_bounds__(MR_BLOCK) k_ls_scan(uint32_t* __restrict__ hist, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t wsum[4];
+    __shared__ uint32_t wsum[MR_BLOCK / 64];
     uint32_t* h = hist + (size_t)blockIdx.x * MR_LS_GRID;
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     uint32_t running = 0u;
     for (int c0 = 0; c0 < MR_LS_GRID; c0 += MR_BLOCK) {
         const int i = c0 + (int)threadIdx.x;
-        const uint32_t x = h[i];
-        uint32_t inc = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const uint32_t t = wsum[w]; if (w < wave) before += t; all += t; }
-        h[i] = running + before + inc - x;
+        uint32_t all;
+        const uint32_t before = block_excl_scan<MR_BLOCK>(h[i], wsum, all);
+        h[i] = running + before;
         running += all;
-        __syncthreads();
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = running;
 }
@@ -355,13 +347,10 @@ __global__ void __launch_bounds__(MR_BLOCK) k_ls_scatter(const uint32_t* __restr
     __shared__ uint32_t dsum[MR_BLOCK / 64];
     __shared__ uint32_t base[256];
     const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const uint32_t n = *d_count; uint32_t t0, t1; ls_run(n, t0, t1);
     {   // where this workgroup's keys of digit d (= thread d) start: all keys with smaller digits + this digit's keys in the workgroups before
         const uint32_t tot = totals[threadIdx.x];
-        uint32_t inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+        const uint32_t inc = wave_incl_scan(tot);
         if (lane == 63) dsum[wave] = inc;
         __syncthreads();
         uint32_t run = inc - tot + offs[(size_t)threadIdx.x * MR_LS_GRID + blockIdx.x];
@@ -378,16 +367,8 @@ __global__ void __launch_bounds__(MR_BLOCK) k_ls_scatter(const uint32_t* __restr
             const uint32_t idx = first + i * 64 + lane;
             const bool valid = idx < n;
             k[i] = valid ? kin[idx] : 0xffffffffu; v[i] = valid ? vin[idx] : 0;
-            const uint32_t d = (k[i] >> shift) & 255u;
-            uint64_t m = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < 8; b++) { const bool bit = (d >> b) & 1u; const uint64_t bal = __ballot(bit); m &= bit ? bal : ~bal; }
-            const int leader = valid ? __builtin_ctzll(m) : lane;
-            uint32_t prev = 0u;
-            if (valid && lane == leader) { prev = wh[wave][d]; wh[wave][d] = prev + (uint32_t)__popcll(m); }
-            prev = (uint32_t)__shfl((int)prev, leader, 64);
-            r[i] = prev + (uint32_t)__popcll(m & lt_mask);
-            __syncthreads();
+            r[i] = wave_digit_rank((k[i] >> shift) & 255u, valid, wh[wave]);
+            __syncthreads();                                              // the next round's leaders read what this round's leaders wrote
         }
         {   // per digit: the waves' starting places in this tile, and the workgroup's running base moves past the tile
             uint32_t run = base[threadIdx.x];

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include "device_light.hpp"
 #include "device_brdf.hpp"
 

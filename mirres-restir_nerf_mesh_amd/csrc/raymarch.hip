@@ -13,6 +13,7 @@
 #include <float.h>
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include "device_density.hpp"
 #include "device_march.hpp"
 
@@ -117,27 +118,21 @@ __global__ void __launch_bounds__(RM_BLOCK) k_rm_march_train(const float* __rest
     if (!WRITE) { rays[2 * n] = 0; rays[2 * n + 1] = (int32_t)m.step; }
 }
 
-// rays[n, 0] = sum of rays[k, 1] over k < n, total[0] = the sum over all rays: one workgroup, every thread a contiguous run of rays
+// rays[n, 0] = sum of rays[k, 1] over k < n, total[0] = the sum over all rays: one workgroup, every thread a contiguous run of rays, the runs' sums
+// through block_excl_scan (device_scan.hpp) in 64 bits
 __global__ void __launch_bounds__(RM_SCAN_BLOCK) k_rm_scan(int32_t* __restrict__ rays, i64 N, i64* __restrict__ total) {
-    __shared__ i64 part[RM_SCAN_BLOCK];
+    __shared__ unsigned long long part[RM_SCAN_BLOCK / 64];
     const i64 run = (N + RM_SCAN_BLOCK - 1) / RM_SCAN_BLOCK;
     const i64 a = min((i64)threadIdx.x * run, N), b = min(a + run, N);
     i64 s = 0;
     for (i64 k = a; k < b; k++) s += (i64)(uint32_t)rays[2 * k + 1];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < RM_SCAN_BLOCK; off <<= 1) {              // inclusive scan of the runs' sums
-        const i64 v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    i64 base = part[threadIdx.x] - s;
+    unsigned long long all;                                          // exclusive scan of the runs' sums (none negative: counts are read as uint32)
+    i64 base = (i64)block_excl_scan<RM_SCAN_BLOCK>((unsigned long long)s, part, all);
     for (i64 k = a; k < b; k++) {
         rays[2 * k] = (int32_t)(base > 0x7fffffffLL ? 0x7fffffffLL : base);      // beyond 2^31 - 1 samples the caller refuses (total says so); never a wrapped offset
         base += (i64)(uint32_t)rays[2 * k + 1];
     }
-    if (threadIdx.x == RM_SCAN_BLOCK - 1) total[0] = part[threadIdx.x];
+    if (threadIdx.x == 0) total[0] = (i64)all;
 }
 
 __global__ void __launch_bounds__(RM_BLOCK) k_rm_composite_train_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ ts,

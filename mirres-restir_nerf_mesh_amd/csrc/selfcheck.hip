@@ -6,6 +6,7 @@
 #endif
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 
 namespace mr {
 

@@ -8,6 +8,7 @@
 #endif
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "device_scan.hpp"
 #include "device_light.hpp"
 #include "device_brdf.hpp"
 

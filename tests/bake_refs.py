@@ -86,7 +86,7 @@ def tri_setup(vt, ft, W, H):
     return dict(X=X, Y=Y, flip=flip, area=area, c0=c0, r0=r0, bw=np.where(ok, c1 - c0 + 1, 0), bh=np.where(ok, r1 - r0 + 1, 0))
 
 
-CHUNK = 32                                  # BK_CHUNK (csrc/bake.hip:16): box texels per work item
+CHUNK = 32                                  # BK_CHUNK (csrc/bake.hip:17): box texels per work item
 
 
 def chunk_first(vt, ft, W, H):

@@ -65,14 +65,14 @@ def test_uv_rasterize_adversarial(EX):
 
 
 def test_uv_rasterize_scans_more_than_two_rounds_of_block_sums(EX):
-    """Branch: the carry of k_scan_sums (csrc/bake.hip:113) — one workgroup walks the block sums BK_BLOCK = 256 (:15) at a time, each sum covering BK_SCAN = 1024
+    """Branch: the carry of k_scan_sums (csrc/bake.hip:101) — one workgroup walks the block sums BK_BLOCK = 256 (:16) at a time, each sum covering BK_SCAN = 1024
     (:88) triangles, so a second round needs more than 262 144 triangles — with a ragged last round, a ragged last block of k_scan_local, zero-chunk
     triangles (equal neighbours in first[], which k_uv_cover's binary search must step over) and triangles of many chunks.
     Input (bake_refs.cell_grid_input): a 1024 x 1024 grid tiled by 2 x 2-texel cells, each split along a random diagonal through two texel centres (the fill
     rule decides them), half the triangles reversed, a zero-area triangle at every 349th position, 200 triangles with boxes of up to 100 x 100 texels last.
     Host assertions before the launch: T > 2 * 262 144, nb % 256 != 0, T % 1024 != 0, first[] restated has equal neighbours, every texel covered in the
     reference.  Observed: T = 525 994, nb = 514 block sums = 3 rounds (the last of 2), 1 507 zero-chunk triangles, 528 919 work items, up to 169 for one triangle."""
-    BK_BLOCK, BK_SCAN = 256, 1024                                              # csrc/bake.hip:15 and :88
+    BK_BLOCK, BK_SCAN = 256, 1024                                              # csrc/bake.hip:16 and :90
     W = H = 1024
     vt, ft, n_small = R.cell_grid_input(W)
     T = ft.shape[0]; nb = -(-T // BK_SCAN)

@@ -101,7 +101,7 @@ def test_march_rays_train_bit_equal(RM, kind, shape_i):
         assert all(R.march_train_case(kind, shape_i, pi, 65)["rays"][:, 1].sum() == 0 for pi in range(len(R.MARCH_PARAMS)) if not R.MARCH_PARAMS[pi]["contract"])
 
 
-# k_rm_scan (csrc/raymarch.hip:121) gives each of its RM_SCAN_BLOCK = 1024 threads a run of ceil(N / 1024) rays: 1025, 2050 and 3073 make runs of 2, 3 and 4,
+# k_rm_scan (csrc/raymarch.hip:123) gives each of its RM_SCAN_BLOCK = 1024 threads a run of ceil(N / 1024) rays: 1025, 2050 and 3073 make runs of 2, 3 and 4,
 # a last non-empty thread (512, 683, 768) that holds ONE ray, and empty threads after it; 2048 divides evenly
 @pytest.mark.parametrize("N", [1, 63, 64, 65, 2048, 1025, 2050, 3073])
 def test_march_rays_train_ray_counts_and_repeatability(RM, N):
@@ -115,6 +115,51 @@ def test_march_rays_train_ray_counts_and_repeatability(RM, N):
         c = R.march_train_case("random", 0, 1, N)
         assert c["rays"][3, 1] == 0 and c["nears"][3] == R.FLT_MAX           # the ray that misses
         assert c["rays"][4:9, 1].sum() > 0                                   # the rays along cell faces and from inside do sample
+
+
+def _scan_fill(kind, N):
+    """int32 counts [N] for k_rm_scan, which reads them as uint32.  'all': every count 0xFFFFFFFF.  'edges': zeros, and 0xFFFFFFFF at every ray of scan threads
+    31, 32, 63 and 64 (lane 0 of the second wave) and at the first and the last ray of every other eighth thread's run (thread 0 among them) and of the last
+    thread that holds a ray; a run is ceil(N / 1024) rays, so runs of 4 keep zeros between their ends."""
+    if kind == "all":
+        return np.full(N, -1, np.int32)
+    run = -(-N // 1024)
+    last_thread = (N - 1) // run
+    counts = np.zeros(N, np.int32)
+    for t in range(last_thread + 1):
+        a, b = t * run, min((t + 1) * run, N)
+        if t in (31, 32, 63, 64):
+            counts[a:b] = -1
+        elif t % 8 == 0 or t == last_thread:
+            counts[a] = counts[b - 1] = -1
+    return counts
+
+
+@pytest.mark.parametrize("N", [64, 65, 1024, 1025, 3073])
+@pytest.mark.parametrize("kind", ["all", "edges"])
+def test_march_train_scan_carries_past_32_bits(kind, N):
+    """mirres_rm_march_train_scan on counts whose prefix sums pass 2^32 (with 'all' at the second ray): the 64-bit workgroup scan (block_excl_scan of
+    csrc/device_scan.hpp on unsigned long long, whose wave step shuffles a value as two 32-bit halves) must carry between the halves inside a wave, across waves
+    and across the threads' runs.  Called through ctypes: march_rays_train refuses such totals.  Offsets = the exclusive sums clamped at 2^31 - 1, total = the
+    exact sum (at most 3073 (2^32 - 1)), the counts untouched — all from numpy int64.  This is the one place the library's u64 scan can be driven past 2^32 at
+    test sizes: csrc/bake.hip's and csrc/albedo.hip's u64 scans would need more than 2^32 work items or pixels through their entry points, and they share the
+    primitive this test drives there."""
+    from mirres_restir_nerf_mesh_amd._lib import lib, check, ptr, stream_ptr
+    counts = _scan_fill(kind, N)
+    c64 = counts.astype(np.uint32).astype(np.int64)
+    if kind == "edges":
+        run = -(-N // 1024)
+        assert c64[0] == 0xFFFFFFFF and c64[31 * run] == 0xFFFFFFFF and c64[min(64 * run - 1, N - 1)] == 0xFFFFFFFF and 3 <= (c64 != 0).sum() < N
+    excl = np.cumsum(c64) - c64
+    assert excl[1] == 0xFFFFFFFF and excl[-1] + c64[-1] >= 2 ** 32 and excl.max() < 2 ** 62         # the sums are exact in int64 and pass 32 bits
+    rays = np.stack([np.full(N, 0x5A5A5A5A, np.int32), counts], 1)             # column 0 arrives dirty: every offset is written
+    g_rays = dev(rays)
+    total = torch.full((1,), -7, dtype=torch.int64, device="cuda")
+    check(lib().mirres_rm_march_train_scan(ptr(g_rays), N, ptr(total), stream_ptr()), "mirres_rm_march_train_scan")
+    got = host(g_rays)
+    assert np.array_equal(got[:, 0].astype(np.int64), np.minimum(excl, 2 ** 31 - 1))
+    assert int(total.item()) == int(c64.sum())
+    assert np.array_equal(got[:, 1], counts)
 
 
 def test_march_perturb_without_noises_draws_on_the_device(RM):

@@ -306,11 +306,11 @@ def test_export_stage0_synthetic_end_to_end(S0, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ past the first chunk of the second-level scans
-MC_BLOCK, MC_SCAN_BLOCK = 256, 1024                                                  # csrc/mcubes.hip:24 and :25
+MC_BLOCK, MC_SCAN_BLOCK = 256, 1024                                                  # csrc/mcubes.hip:25 and :26
 
 
 def _scan_split(n_items):
-    """How k_scan_ints (csrc/mcubes.hip:91-96) splits the workgroup totals of n_items elements -> (nb totals, `per` totals per scan thread, whether the last scan
+    """How k_scan_ints (csrc/mcubes.hip:75-80) splits the workgroup totals of n_items elements -> (nb totals, `per` totals per scan thread, whether the last scan
     thread's chunk is empty (its i0 = 1023 per is not below nb), whether the last non-empty chunk is shorter than per)."""
     nb = -(-n_items // MC_BLOCK); per = -(-nb // MC_SCAN_BLOCK)
     return nb, per, (MC_SCAN_BLOCK - 1) * per >= nb, nb % per != 0
@@ -329,14 +329,14 @@ def _mc_structure(vol, iso):
     n_edges = cross.reshape(-1, 3).sum(1)
     cfg = np.zeros((nx - 1, ny - 1, nz - 1), np.int64)
     for c in range(8):
-        dx, dy, dz = c & 1, (c >> 1) & 1, (c >> 2) & 1                              # corner c of a cell (csrc/mcubes.hip:52)
+        dx, dy, dz = c & 1, (c >> 1) & 1, (c >> 2) & 1                              # corner c of a cell (csrc/mcubes.hip:36)
         cfg |= inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz].astype(np.int64) << c
     cx, cy, cz = np.nonzero(R.NTRI[cfg] > 0)
     return n_edges, np.repeat(np.arange(n_edges.size), n_edges), np.repeat((cx * ny + cy) * nz + cz, R.NTRI[cfg[cx, cy, cz]])
 
 
 def _max_block_prefix(n_edges):
-    """The largest exclusive vertex prefix inside a 256-point workgroup at a point that owns a vertex: the 10-bit field of local[g] (csrc/mcubes.hip:86)."""
+    """The largest exclusive vertex prefix inside a 256-point workgroup at a point that owns a vertex: the 10-bit field of local[g] (csrc/mcubes.hip:70)."""
     b = np.zeros(-(-n_edges.size // MC_BLOCK) * MC_BLOCK, np.int64); b[:n_edges.size] = n_edges
     b = b.reshape(-1, MC_BLOCK)
     return int(((np.cumsum(b, 1) - b) * (b > 0)).max())
@@ -362,7 +362,7 @@ BIG = (67, 65, 64)                                                              
 # the third entry: is the last non-empty chunk of k_scan_ints shorter than `per` (three of the four shapes)
 @pytest.mark.parametrize("shape,far,ragged", [((3, 3, 40000), False, True), ((40000, 3, 3), False, True), ((2, 131073, 2), True, False), (BIG, False, True)])
 def test_marching_cubes_past_the_first_scan_chunk(shape, far, ragged):
-    """Branch: k_scan_ints (csrc/mcubes.hip:91) with per = ceil(nb / MC_SCAN_BLOCK) >= 2 — the chunk loops at :96 and :106, threads whose chunk is empty, and for
+    """Branch: k_scan_ints (csrc/mcubes.hip:75) with per = ceil(nb / MC_SCAN_BLOCK) >= 2 — the chunk loops at :80 and :83, threads whose chunk is empty, and for
     three of the four shapes a last non-empty chunk shorter than per — with the large stride of blk_v[q / MC_BLOCK] in k_mc_emit (:148) on each axis in turn.
     Host assertions before the launch: nb = ceil(points / 256) > 1024, per >= 2, (1024 - 1) per >= nb, nb % per != 0 where `ragged`; for (2, 131073, 2), whose
     x stride is 262 146 points, a triangle of the reference mesh uses a vertex owned by a point more than 1024 workgroups after the emitting cell's.
@@ -384,7 +384,7 @@ def test_marching_cubes_past_the_first_scan_chunk(shape, far, ragged):
 
 @pytest.mark.parametrize("shape", [(12, 11, 13), (3, 3, 40000)])
 def test_checkerboard_sets_the_top_bit_of_the_prefix_field(shape):
-    """Branch: bit 9 of the 10-bit vertex prefix k_mc_count packs into local[g] under the edge flags (csrc/mcubes.hip:86), which k_mc_emit masks out with 1023
+    """Branch: bit 9 of the 10-bit vertex prefix k_mc_count packs into local[g] under the edge flags (csrc/mcubes.hip:70), which k_mc_emit masks out with 1023
     (:148).  A checkerboard sign * (1 + u) at iso 0 crosses every edge, so a workgroup of MC_BLOCK = 256 points owns close to 3 * 256 vertices.
     Host assertion before the launch: the largest exclusive prefix inside a workgroup at a point that owns a vertex, computed as k_mc_count does, is >= 512.
     Observed: 733 at (12, 11, 13), 765 at (3, 3, 40000); the noise volumes above stop at 322."""
@@ -399,7 +399,7 @@ def test_checkerboard_sets_the_top_bit_of_the_prefix_field(shape):
 
 
 def test_sphere_at_128_scans_eight_totals_per_thread(S0):
-    """Branch: k_scan_ints (csrc/mcubes.hip:91) at per = 8 on the scene the export's smoke run uses, S0.synthetic_volume(128) at iso 10: a dented ball and a small
+    """Branch: k_scan_ints (csrc/mcubes.hip:75) at per = 8 on the scene the export's smoke run uses, S0.synthetic_volume(128) at iso 10: a dented ball and a small
     floater, two closed surfaces of genus 0.
     Host assertion before the launch: 128^3 points are nb = 8192 workgroups of MC_BLOCK = 256, per = 8 for MC_SCAN_BLOCK = 1024 scan threads, none of them empty.
     Checked: bit-equal to the restatement, every edge shared by two triangles in opposite directions, two components of Euler characteristic 2 each, outward
@@ -437,7 +437,7 @@ def _keep_mask(name, T):
 
 @pytest.mark.parametrize("mask", ["all", "none", "last", "first", "random", "beyond"])
 def test_compaction_past_the_first_scan_chunk(S0, big_mesh, mask):
-    """Branch: both k_scan_ints launches of mirres_mesh_compact (csrc/mcubes.hip:471, :474) with per >= 2 over the totals of k_flag_sums, for masks that put the
+    """Branch: both k_scan_ints launches of mirres_mesh_compact (csrc/mcubes.hip:448, :451) with per >= 2 over the totals of k_flag_sums, for masks that put the
     kept elements everywhere, nowhere, in the last or first workgroup only, at random, and ("beyond") exactly in the workgroups after the first
     MC_SCAN_BLOCK * MC_BLOCK = 262 144 faces, whose offsets come from the second entry of a scan thread's chunk on.
     Host assertion before the launch: ceil(V / 256) > 1024 and ceil(T / 256) > 1024 (per >= 2), the last scan thread's chunk empty; "beyond" keeps a face.
@@ -460,7 +460,7 @@ def test_compaction_past_the_first_scan_chunk(S0, big_mesh, mask):
 
 @pytest.mark.parametrize("rings", [1, 3])
 def test_dilation_on_a_mesh_of_many_workgroups(S0, big_mesh, rings):
-    """mirres_mesh_dilate (csrc/mcubes.hip:440) over 1729 workgroups of faces and 1071 of vertices, from a random 1 % of the faces, against stage0_refs.dilate.
+    """mirres_mesh_dilate (csrc/mcubes.hip:417) over 1729 workgroups of faces and 1071 of vertices, from a random 1 % of the faces, against stage0_refs.dilate.
     Host assertion before the launch: ceil(T / 256) > 1024, the selection and its complement are not empty.  Observed: 4 501 faces selected, 46 321 after one
     ring, 122 721 after three."""
     m = big_mesh
@@ -474,7 +474,7 @@ def test_dilation_on_a_mesh_of_many_workgroups(S0, big_mesh, rings):
 
 
 def test_components_of_a_mesh_of_many_workgroups(S0, big_mesh):
-    """mirres_mesh_components (csrc/mcubes.hip:486) on 442 622 faces in 23 733 components (noise at iso 0.8: many small pieces), against
+    """mirres_mesh_components (csrc/mcubes.hip:463) on 442 622 faces in 23 733 components (noise at iso 0.8: many small pieces), against
     scipy's connected components; the hook / jump rounds stay within MESH_MAX_ROUNDS = 64 (:26).
     Host assertion before the launch: ceil(T / 256) > 1024 and the reference finds more than 1000 components, one of them larger than a workgroup.
     Observed: 23 733 components, the largest of 564 faces, 5 rounds."""
@@ -490,7 +490,7 @@ def test_components_of_a_mesh_of_many_workgroups(S0, big_mesh):
 
 @pytest.mark.parametrize("S", [128, 256])
 def test_unpack_density_grid_at_checkpoint_sizes(S0, S):
-    """Branch: the `<< 8` step of spread3 (csrc/mcubes.hip:157), which moves bits 4-7 of a coordinate and so does nothing below S = 32; checkpoints use S = 128.
+    """Branch: the `<< 8` step of spread3 (csrc/mcubes.hip:134), which moves bits 4-7 of a coordinate and so does nothing below S = 32; checkpoints use S = 128.
     Host assertion before the launch: S - 1 has a bit in 4-7 set; the two host restatements (the bit trick of stage0_refs.unpack_morton and the per-bit loop
     of stage0.morton_indices) agree.  Exact against both."""
     assert (S - 1) & 0xF0 and S <= 256
@@ -503,7 +503,7 @@ def test_unpack_density_grid_at_checkpoint_sizes(S0, S):
 
 @pytest.mark.parametrize("Rr,S", [(129, 128), (200, 128), (255, 64), (128, 128)])
 def test_mask_by_density_grid_at_other_ratios(S0, Rr, S):
-    """k_mask_nearest (csrc/mcubes.hip:171) at ratios where floor(dst * (float)(S / R)) lands beside the exact quotient or needs its clamp: one more than the grid,
+    """k_mask_nearest (csrc/mcubes.hip:148) at ratios where floor(dst * (float)(S / R)) lands beside the exact quotient or needs its clamp: one more than the grid,
     a non-integer ratio, almost four to one, and one to one; NaN and infinities under both values of the mask.  Exact against F.interpolate(mode='nearest').
     Host assertion before the launch: the reference mask has both values, and non-finite cells lie under a cleared and under a set mask."""
     rng = np.random.default_rng(Rr + S)
