@@ -572,6 +572,22 @@ long long mirres_radiance_bwd_workspace_bytes(long long n, int max_blocks);
 int mirres_radiance_points_bwd(const mirres_radiance_t* net, const float* pos, const float* dirs, long long n, float bound, const float* grad_sigma,
                                const float* grad_rgb, float* grad_table, float* grad_w0, float* grad_w1, float* grad_c0, float* grad_c1, float* grad_c2,
                                void* workspace, long long workspace_bytes, int max_blocks, void* stream);
+/* GridEncoder.grad_total_variation (gridencoder/grid.py:170-192) over kernel_grad_tv (gridencoder/src/gridencoder.cu:505-609), grid_tv.hip: the in-place
+ * total-variation regulariser of the hash grid.  pos f32[n,3] in world coordinates, as for mirres_density_points; grad_table f32[entries,2] is ACCUMULATED into;
+ * net->w0 and net->w1 are not read and may be NULL.  Per point and level: c = the encoder's corner 0 (floorf(u * scale + 0.5f) per axis), e = its entry; for
+ * d = 0, 1, 2 first the right neighbour (c[d] + 1, when c[d] < resolution), then the left (c[d] - 1, when c[d] > 0), per channel diff = table[e] - table[nb],
+ * res += diff, idelta += diff * diff; value = (w * res) * (1 / sqrt(idelta + 1e-9f)) with w = weight / 6.0f, every operation rounded on its own and 1 / sqrt by
+ * IEEE (the reference: rsqrtf).  A point with a coordinate outside [-bound, bound] or not finite contributes to no level (the reference casts a NaN to an index).
+ * DENSE levels (hashed[l] == 0) take no fp32 atomic: the points of every cell are counted with integer atomics in `workspace`, then every entry with a count gets
+ * grad[e] = grad[e] + (float)count * value by one plain store — one fixed set of bits for a given multiset of points, whatever their order; (float)count rounds
+ * above 2^24 points in one cell.  Entries without a point are not touched.  HASHED levels add value with fp32 atomics in no fixed order; the lanes of a wave that
+ * hold one cell add (float)k * value once.  workspace: device memory of at least mirres_grid_tv_workspace_bytes(net) bytes (4 bytes per entry of the dense
+ * levels), 4-byte aligned; its contents need not be initialised and it can be handed to the next call on the same stream.  Refused before a device is touched:
+ * a NULL net or table or a bad layout, n < 0 or n > 2^31, NULL pos with n > 0, NULL grad_table, a negative or non-finite weight, a bound that is not positive,
+ * a NULL or short workspace.  n == 0 or weight == 0 returns 0 and changes nothing.                                                                              */
+long long mirres_grid_tv_workspace_bytes(const mirres_density_t* net);
+int mirres_grid_tv_grad(const mirres_density_t* net, const float* pos, long long n, float bound, float weight, float* grad_table, void* workspace,
+                        long long workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------------------------------------------
  * The stage-0 ray-marching operators (raymarch.hip): torch-ngp's raymarching module (raymarching/src/raymarching.cu), fp32 only, and the upkeep of the

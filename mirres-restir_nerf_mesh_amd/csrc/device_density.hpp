@@ -83,11 +83,12 @@ MR_DEV void dn_stage_weights(const mirres_density_t& N, float* sw0, float* sw1) 
     __syncthreads();
 }
 
-// what every entry that takes a net checks before a launch
-static bool dn_net_ok(const mirres_density_t* N, const char* who) {
+// what every entry that takes a net checks before a launch; need = 1: an entry that reads the table and the levels alone (w0 and w1 may be NULL), 0: the levels alone
+static bool dn_net_ok(const mirres_density_t* N, const char* who, int need = 2) {
     if (!N) { set_error("%s: net is NULL", who); return false; }
     if (N->num_levels < 1 || N->num_levels > DN_LEVELS) { set_error("%s: num_levels %d outside [1, %d]", who, N->num_levels, DN_LEVELS); return false; }
-    if (!N->table || !N->w0 || !N->w1) { set_error("%s: net has a NULL table / w0 / w1", who); return false; }
+    if (need >= 2 && (!N->table || !N->w0 || !N->w1)) { set_error("%s: net has a NULL table / w0 / w1", who); return false; }
+    if (need >= 1 && !N->table) { set_error("%s: net has a NULL table", who); return false; }
     if (N->offsets[0] < 0) { set_error("%s: negative level offset", who); return false; }
     for (int l = 0; l < N->num_levels; l++) {
         if (N->offsets[l + 1] <= N->offsets[l] || N->resolution[l] < 1 || N->resolution[l] > (1 << 24) || !(N->scale[l] >= 0.f) || !(N->scale[l] <= 16777216.f)) {

@@ -101,6 +101,23 @@ def get_rays(pose, intrinsics, H, W):
     return rays_o.contiguous(), rays_d.contiguous()
 
 
+def get_rays_at(poses, intrinsics, H, W, pix):
+    """get_rays for single pixels of many cameras (nerf/utils.py:350-423 with N > 0, one pose per ray): poses [n, 4, 4] cam2world, pix i64 [n] row-major pixel
+    indices in [0, H * W) -> (rays_o [n, 3], rays_d [n, 3]) with get_rays' pixel centres and axes.  Each direction component is the explicit sum
+    (x * R[k, 0] + y * R[k, 1]) + z * R[k, 2], so it does not depend on a GEMM's order of accumulation."""
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    poses = poses.to(torch.float32)
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or pix.dim() != 1 or pix.shape[0] != poses.shape[0]:
+        raise ValueError("get_rays_at: poses of %s and pix of %s, expected [n, 4, 4] and [n]" % (tuple(poses.shape), tuple(pix.shape)))
+    pix = pix.to(poses.device, torch.int64)
+    i = (pix % W).to(torch.float32) + 0.5
+    j = torch.div(pix, W, rounding_mode="floor").to(torch.float32) + 0.5
+    x, y, z = (i - cx) / fx, -(j - cy) / fy, -torch.ones_like(i)
+    R = poses[:, :3, :3]
+    rays_d = torch.stack([(x * R[:, k, 0] + y * R[:, k, 1]) + z * R[:, k, 2] for k in range(3)], dim=-1)
+    return poses[:, :3, 3].contiguous(), rays_d.contiguous()
+
+
 def mvp_from_pose(pose, intrinsics, H, W, near=0.05, far=1000.0):
     """The model-view-projection matrix the dataset hands to render_stage1 (nerf/provider.py:277-288): an OpenGL-style perspective projection with
     the image's y axis flipped (row 0 at the top, like get_rays) times the inverse of the cam2world pose.  `near` = --min_near (main.py default 0.05),

@@ -20,6 +20,7 @@ nvdiffrast behind it.
     out = render_stage0(rf, DensityGrid.from_checkpoint(ck), rays_o, rays_d)     # :714-717, 778-839: the inference branch of render -> image, depth, weights_sum
     sigma, rgb = rf.forward_train(x, d)                    # the same bits, differentiable in rf.parameters(): csrc/radiance_bwd.hip recomputes and adjoins
     out = render_stage0_train(rf, grid, rays_o, rays_d)    # :735-773, 830-838: the training branch (march_rays_train, composite_rays_train)
+    rf.grad_total_variation(1e-8, out["xyzs"])             # gridencoder/grid.py:170-192 after loss.backward(): the table's TV regulariser in place, csrc/grid_tv.hip
 
 Deviations from the reference: background pixels mark no face (the reference's `mask[-1] += 1` marks the last one); vertices are merged
 when their three coordinates are bit-identical (MeshLab's tolerance merge is not reproduced); non-manifold repair and remeshing are not built; decimation
@@ -554,6 +555,43 @@ class DensityField:
         check(lib().mirres_density_volume(C.byref(self.net), ptr(axes[0]), res[0], ptr(axes[1]), res[1], ptr(axes[2]), res[2], self.bound, ptr(g), S,
                                           float(thresh) if g is not None else 0.0, ptr(out), stream_ptr()), "mirres_density_volume")
         return out
+
+    @torch.no_grad()
+    def grad_total_variation(self, weight=1e-7, inputs=None, grad=None, B=1000000, generator=None):
+        """GridEncoder.grad_total_variation (gridencoder/grid.py:170-192; csrc/grid_tv.hip): adds the total-variation term of every level's cell under every
+        point to the table's gradient, in place -> None.  To be called after loss.backward() and before optimizer.step().  inputs [..., 3]: world positions; None
+        or empty: B points uniform in [-bound, bound]^3 (the reference's random branch; `generator`: a device generator for them).  grad: a contiguous fp32
+        device tensor of the table's shape (default: self.table.grad).  The dense levels' sum has one fixed set of bits for a given set of points; the hashed
+        levels are summed by fp32 atomics in no fixed order.  One workspace tensor is kept per field."""
+        if grad is None:
+            grad = self.table.grad
+            if grad is None:
+                raise ValueError("grad is None, should be called after loss.backward() and before optimizer.step()!")
+        if not torch.is_tensor(grad):
+            raise TypeError("grad_total_variation: grad must be a tensor, got %s" % type(grad).__name__)
+        if grad.dtype != torch.float32 or grad.device != self.table.device:
+            raise TypeError("grad_total_variation: grad must be fp32 on the table's device, got %s on %s" % (grad.dtype, grad.device))
+        if tuple(grad.shape) != tuple(self.table.shape) or not grad.is_contiguous():
+            raise ValueError("grad_total_variation: grad of %s%s, the table has %s" % (tuple(grad.shape), "" if grad.is_contiguous() else " (not contiguous)", tuple(self.table.shape)))
+        weight = float(weight)
+        dev = self.table.device
+        if inputs is None or torch.as_tensor(inputs).numel() == 0:
+            x = (torch.rand(int(B), 3, dtype=torch.float32, device=dev, generator=generator) * 2 - 1) * self.bound
+        else:
+            x = torch.as_tensor(inputs)
+            if x.shape[-1] != 3:
+                raise ValueError("grad_total_variation: inputs of %s, expected [..., 3]" % (tuple(x.shape),))
+            x = x.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+        n = int(x.shape[0])
+        L = lib()
+        nbytes = int(L.mirres_grid_tv_workspace_bytes(C.byref(self.net)))
+        if nbytes < 0:
+            check(nbytes, "mirres_grid_tv_workspace_bytes")
+        ws = getattr(self, "_tv_workspace", None)
+        if ws is None or ws.device != dev or ws.numel() * 4 < nbytes:
+            ws = self._tv_workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+        check(L.mirres_grid_tv_grad(C.byref(self.net), ptr(x) if n else None, n, self.bound, weight, ptr(grad), ptr(ws), ws.numel() * 4, stream_ptr()), "mirres_grid_tv_grad")
+        return None
 
 
 class DensityGrid:

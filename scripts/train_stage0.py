@@ -4,15 +4,23 @@ grid's upkeep — from a NeRF-blender folder to `<workspace>/checkpoints/ngp.pth
 
     python scripts/train_stage0.py --path data/lego --workspace out/lego --bound 1 --scale 0.8 --mark_untrained --eval_views 4
     python scripts/train_stage0.py --synthetic --iters 300
+    python scripts/train_stage0.py --path data/lego --workspace out/lego -O --bound 1 --scale 0.8 --lambda_tv 1e-8        # the reference's stage-0 recipe, in fp32
 
 The reference's settings: Adam (lr 1e-2, eps 1e-15), the LambdaLR warm-up and decay of main.py:285 stepped every iteration, 7500 iterations of 4096 uniformly random
 pixels of one training image each, white or random background with gt = rgb * a + bg * (1 - a), loss = lambda_rgb * MSE(rgb).mean(-1) + lambda_mask * MSE(weights_sum,
 a) when the images have alpha, perturbed sampling, DensityGrid.update every --update_extra_interval steps before the step, an exponential moving average of the
 parameters (decay 0.95) whose weights are what the checkpoint's `model` holds.
 
-Declared and NOT built (DESIGN.md section 8): fp16 autocast and GradScaler (fp32 throughout); the total-variation regulariser (lambda_tv); --adaptive_num_rays;
---sdf, individual_codes, depth supervision, --trainable_density_grid, error_map sampling and data-parallel training; the reference's partial grid updates after
-step 16 (every update here covers the whole grid).
+Built, and off unless asked for: --lambda_tv X, the in-place total-variation regulariser of the hash grid on the step's own sample points after loss.backward()
+(nerf/utils.py:1152-1158, RadianceField.grad_total_variation; with --bound > 1 the points outside the unit box take 10 X); --adaptive_num_rays, which rescales the
+ray count after every step so that a step marches about --num_points samples (utils.py:1133-1134, adapt_num_rays); --random_image_batch, which keeps every training
+view on the device and draws each ray's image and pixel independently (harness.get_rays_at); -O, the reference's bundle as far as it is built: --mark_untrained
+--random_image_batch --adaptive_num_rays.  Deviations: --lambda_tv defaults to 0 where the reference has 1e-8, so a run without new
+options computes what it did before them; the ray count stays as it is after a step without samples and is clamped to [1, --max_num_rays].
+
+Declared and NOT built: fp16 autocast and GradScaler (fp32 throughout, also under -O); --sdf, individual_codes, depth supervision,
+--trainable_density_grid, error_map sampling and data-parallel training; the reference's partial grid updates after step 16 (every update here covers the whole
+grid).
 
 --synthetic needs no data: it renders ground-truth views of stage0.synthetic_radiance_checkpoint() at a small size from render_stage0.orbit_poses, trains a
 RadianceField.init_random on them and prints the first-window and last-window loss and the held-out PSNR."""
@@ -56,9 +64,18 @@ class EMA:
         return {"decay": self.decay, "num_updates": self.num_updates, "shadow_params": self.shadow}
 
 
+def adapt_num_rays(num_rays, num_points, target, max_num_rays):
+    """nerf/utils.py:1133-1134: int(round(target / num_points * num_rays)) (Python's round: halves to even), clamped to [1, max_num_rays]; a step without
+    samples (where the reference divides by zero) keeps the count it had."""
+    if num_points <= 0:
+        return int(num_rays)
+    return max(1, min(int(max_num_rays), int(round(target / num_points * num_rays))))
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description="Train a stage-0 radiance field on the HIP path (fp32; see the module docstring for what the reference has and this does not: "
-                                            "fp16 autocast / GradScaler, lambda_tv, --adaptive_num_rays, --sdf, individual_codes, depth supervision, "
+    p = argparse.ArgumentParser(description="Train a stage-0 radiance field on the HIP path (fp32; built and off by default: --lambda_tv, --adaptive_num_rays, "
+                                            "--random_image_batch, bundled by -O; see the module docstring for what the reference has and this does not: "
+                                            "fp16 autocast / GradScaler, --sdf, individual_codes, depth supervision, "
                                             "--trainable_density_grid, error_map sampling, data-parallel training)")
     p.add_argument("--path", default=None, help="a NeRF-blender folder: transforms_train.json (and transforms_test.json for --eval_views) with its images")
     p.add_argument("--workspace", default=None)
@@ -76,6 +93,14 @@ def build_parser():
     p.add_argument("--min_near", type=float, default=0.2); p.add_argument("--density_thresh", type=float, default=10.0)
     p.add_argument("--color_space", choices=["srgb", "linear"], default="srgb")
     p.add_argument("--seed", type=int, default=0); p.add_argument("--window", type=int, default=50, help="iterations per reported loss window")
+    p.add_argument("--lambda_tv", type=float, default=0.0, help="weight of the hash grid's total-variation regulariser on each step's sample points (0: off; the "
+                                                                "reference's default is 1e-8); with --bound > 1 the points outside the unit box take ten times it")
+    p.add_argument("--adaptive_num_rays", action="store_true", help="after every step, rescale the ray count so that a step marches about --num_points samples")
+    p.add_argument("--num_points", type=int, default=1 << 18, help="--adaptive_num_rays: the target number of samples per step (ignored without it)")
+    p.add_argument("--max_num_rays", type=int, default=1 << 18, help="--adaptive_num_rays: the ray count never exceeds this")
+    p.add_argument("--random_image_batch", action="store_true", help="keep all training views on the device and draw every ray's image and pixel independently")
+    p.add_argument("-O", dest="O", action="store_true", help="the reference's -O as far as it is built: --mark_untrained --random_image_batch --adaptive_num_rays "
+                                                             "(fp16 stays unbuilt)")
     return p
 
 
@@ -83,6 +108,12 @@ def parse_args(argv=None):
     """Validates what can be validated without a device."""
     p = build_parser()
     a = p.parse_args(argv)
+    if a.O:
+        a.mark_untrained = a.random_image_batch = a.adaptive_num_rays = True
+    if not (a.lambda_tv >= 0) or a.lambda_tv == float("inf"):
+        p.error("--lambda_tv %r: not negative and finite" % a.lambda_tv)
+    if a.num_points < 1 or a.max_num_rays < 1:
+        p.error("--num_points and --max_num_rays at least 1")
     if a.synthetic:
         if a.path:
             p.error("--synthetic brings its own views: drop --path")
@@ -110,8 +141,23 @@ def parse_args(argv=None):
     return a
 
 
-def load_blender(a, split, limit=None):
-    """-> (H, W, focal, [(pose f32 [4, 4], premultiplied rgb f32 [H * W, 3], alpha f32 [H * W] or None)]) of transforms_<split>.json, on the host."""
+def pixels_to_gt(px, color_space):
+    """uint8 pixels [..., C] (C = 3 or 4) -> (premultiplied rgb f32 [..., 3], alpha f32 [...] or None): load_blender's conversion, applied to pixels that were
+    gathered first.  Division by 255 and the product are IEEE on host and device alike, so an srgb pixel has load_blender's bits; --color_space linear goes
+    through the device's pow."""
+    import torch
+    from mirres_restir_nerf_mesh_amd import harness
+    px = px.to(torch.float32) / 255.0
+    rgb = px[..., :3]
+    if color_space == "linear":
+        rgb = harness.srgb_to_linear(rgb)
+    alpha = px[..., 3] if px.shape[-1] == 4 else None
+    return (rgb * alpha[..., None] if alpha is not None else rgb), alpha
+
+
+def load_blender(a, split, limit=None, u8=False):
+    """-> (H, W, focal, [(pose f32 [4, 4], premultiplied rgb f32 [H * W, 3], alpha f32 [H * W] or None)]) of transforms_<split>.json, on the host.
+    u8 (--random_image_batch): the views are (pose, the image's own uint8 pixels [H * W, C], None); pixels_to_gt converts what a step gathers."""
     import numpy as np
     from PIL import Image
     from evaluate import nerf_pose
@@ -127,6 +173,10 @@ def load_blender(a, split, limit=None):
             H, W = img.height // a.downscale, img.width // a.downscale
         if (img.height, img.width) != (H, W):
             img = img.resize((W, H), Image.BILINEAR)
+        if u8:
+            raw = torch.from_numpy(np.array(img, dtype=np.uint8))
+            views.append((nerf_pose(fr["transform_matrix"], a.scale, a.offset), raw.reshape(H * W, -1).contiguous(), None))
+            continue
         px = torch.from_numpy(np.asarray(img).astype(np.float32) / 255.0)
         rgb = px[..., :3]
         if a.color_space == "linear":
@@ -170,7 +220,7 @@ def main(argv=None):
         a.workspace = a.workspace or tempfile.mkdtemp(prefix="stage0_train_")
         H, W, focal, train, held = synthetic_views(a, a.views, max(a.eval_views, 2))
     else:
-        H, W, focal, train = load_blender(a, "train")
+        H, W, focal, train = load_blender(a, "train", u8=a.random_image_batch)
         held = load_blender(a, "test", a.eval_views)[3] if a.eval_views and os.path.exists(os.path.join(a.path, "transforms_test.json")) else []
     intr = (focal, focal, W * 0.5, H * 0.5)
     ck_path = os.path.join(a.workspace, "checkpoints", "ngp.pth")
@@ -208,31 +258,57 @@ def main(argv=None):
     def save(step):
         CK.save_stage0_checkpoint(ck_path, field, grid, epoch=step // max(len(train), 1), global_step=step, optimizer=opt, ema=ema.state_dict())
 
+    if a.random_image_batch:                                                      # every training view on the device once
+        all_poses = torch.from_numpy(np.stack([v[0] for v in train])).to(dev)
+        all_pixels = torch.stack([v[1] for v in train]).to(dev)                   # [V, H * W, C]: uint8 as read from disk, f32 renders under --synthetic
+        all_alpha = torch.stack([v[2] for v in train]).to(dev) if train[0][2] is not None else None
+
     losses = []
+    num_rays = a.num_rays
     for step in range(step0, a.iters):
         if step % a.update_extra_interval == 0:
             grid.update(field, noise=torch.rand(grid.cascade, grid.grid_size ** 3, 3, generator=gen, device=dev))
-        pose, premult, alpha = train[int(torch.randint(len(train), (1,), generator=gen, device=dev).item())]
-        pix = torch.randint(H * W, (a.num_rays,), generator=gen, device=dev)
-        o, d = harness.get_rays(torch.from_numpy(pose).to(dev), intr, H, W)
-        bg = torch.rand(a.num_rays, 3, generator=gen, device=dev) if a.background == "random" else torch.ones(a.num_rays, 3, device=dev)
-        gt = premult.to(dev)[pix]
-        al = alpha.to(dev)[pix] if alpha is not None else None
+        if a.random_image_batch:
+            index = torch.randint(len(train), (num_rays,), generator=gen, device=dev)
+            pix = torch.randint(H * W, (num_rays,), generator=gen, device=dev)
+            rays_o, rays_d = harness.get_rays_at(all_poses[index], intr, H, W, pix)
+            if all_pixels.dtype == torch.uint8:
+                gt, al = pixels_to_gt(all_pixels[index, pix], a.color_space)
+            else:
+                gt, al = all_pixels[index, pix], (all_alpha[index, pix] if all_alpha is not None else None)
+        else:
+            pose, premult, alpha = train[int(torch.randint(len(train), (1,), generator=gen, device=dev).item())]
+            pix = torch.randint(H * W, (num_rays,), generator=gen, device=dev)
+            o, d = harness.get_rays(torch.from_numpy(pose).to(dev), intr, H, W)
+            rays_o, rays_d = o[pix], d[pix]
+            gt = premult.to(dev)[pix]
+            al = alpha.to(dev)[pix] if alpha is not None else None
+        bg = torch.rand(num_rays, 3, generator=gen, device=dev) if a.background == "random" else torch.ones(num_rays, 3, device=dev)
         if al is not None:
             gt = gt + bg * (1 - al[:, None])
-        out = stage0.render_stage0_train(field, grid, o[pix], d[pix], bg_color=bg, perturb=True, dt_gamma=a.dt_gamma, max_steps=a.max_steps, T_thresh=a.T_thresh,
-                                         noises=torch.rand(a.num_rays, generator=gen, device=dev))
+        out = stage0.render_stage0_train(field, grid, rays_o, rays_d, bg_color=bg, perturb=True, dt_gamma=a.dt_gamma, max_steps=a.max_steps, T_thresh=a.T_thresh,
+                                         noises=torch.rand(num_rays, generator=gen, device=dev))
         loss = a.lambda_rgb * ((out["image"] - gt) ** 2).mean(-1)
         if al is not None:
             loss = loss + a.lambda_mask * (out["weights_sum"] - al) ** 2
         loss = loss.mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
+        if a.lambda_tv > 0 and field.table.grad is not None:                      # nerf/utils.py:1152-1158, on the step's own sample points
+            xyzs = out["xyzs"]
+            if a.bound > 1:
+                inner = xyzs.abs().amax(-1) <= 1
+                field.grad_total_variation(a.lambda_tv, xyzs[inner])
+                field.grad_total_variation(a.lambda_tv * 10, xyzs[~inner])
+            else:
+                field.grad_total_variation(a.lambda_tv, xyzs)
         opt.step(); sched.step(); ema.update(params)
         losses.append(float(loss.item()))
         if (step + 1) % a.window == 0:
-            log("[INFO] iteration %d: loss %.6f (mean of the last %d), %d samples, lr %.3e" % (step + 1, float(np.mean(losses[-a.window:])), a.window, out["num_points"],
-                                                                                          opt.param_groups[0]["lr"]))
+            log("[INFO] iteration %d: loss %.6f (mean of the last %d), %d rays, %d samples, lr %.3e" % (step + 1, float(np.mean(losses[-a.window:])), a.window, num_rays,
+                                                                                                   out["num_points"], opt.param_groups[0]["lr"]))
+        if a.adaptive_num_rays:
+            num_rays = adapt_num_rays(num_rays, out["num_points"], a.num_points, a.max_num_rays)
         if a.save_interval and (step + 1) % a.save_interval == 0 and step + 1 < a.iters:
             save(step + 1)
     save(a.iters)
