@@ -717,7 +717,8 @@ __global__ void __launch_bounds__(1024) k_sah_tail(int level0, SahState* st, Sah
     }
 }
 // the rebuilt upper levels into the private node arrays — or nothing at all when the counts do not add up
-__global__ void __launch_bounds__(256) k_sah_install(const SahState* st, const SahNode* __restrict__ nodes, const int32_t* __restrict__ top_ids, int32_t* __restrict__ pinfo, float* __restrict__ paabb) {
+__global__ void __launch_bounds__(256) k_sah_install(const SahState* st, const SahNode* __restrict__ nodes, const int32_t* __restrict__ top_ids, int32_t* __restrict__ pinfo, float* __restrict__ paabb,
+                                                     uint32_t* __restrict__ prange) {
     const uint32_t C = st->n_items;
     if (st->fail || C < 2 || C > MR_SAH_MAXC || st->n_resolved != C || st->n_internal != C - 1 || st->n_top != C - 1) return;
     const uint32_t n = st->n_nodes;
@@ -731,6 +732,263 @@ __global__ void __launch_bounds__(256) k_sah_install(const SahState* st, const S
         pinfo[3 * (size_t)id + 2] = 0;
 #pragma unroll
         for (int q = 0; q < 6; q++) paabb[6 * (size_t)id + q] = N.box[q];
+        prange[2 * (size_t)id] = 1u; prange[2 * (size_t)id + 1] = 0u;      // no longer a contiguous range of the private order (k_sb_prepare)
+    }
+}
+
+// ---------------------------------------------------------------- SAH bottom (private level 3): the lower levels rebuilt by exact sweep SAH
+// Every maximal subtree of the private hierarchy that holds at most L leaves (MR_SAH_BOTTOM, 3 <= leaves) gets a new internal topology, built top-down over the
+// leaves' own boxes: per node the leaves are swept in centroid order along the three axes and the cheapest of the 3 (m - 1) object splits (area x count) is taken.
+// The subtree root keeps its id, the rebuilt internal nodes reuse the ids the subtree had (a binary tree over m leaves has m - 1 of them), leaf entries are not
+// touched, node boxes are the fmin / fmax unions of the leaf boxes below (the inclusive scan's last entry: exact and order-free as everywhere else).
+// Leaf counts: below the SAH top a node still covers a contiguous range of the private order (p_range); k_sah_install marks the ids it rewrote with an empty range
+// (1, 0), and their counts are summed bottom-up from the nodes hanging below them (k_sb_count; a walk stops at the first ancestor already known to hold more than L).
+// One workgroup per subtree; leaf boxes, centroid keys, the three axis orders and the segment table (one segment = one node of the current level) live in LDS.
+// Per level: segmented suffix / prefix box scans per axis -> cost of every split position -> 64-bit LDS atomicMin per segment -> stable partition of the three orders.
+// Internal node "idx" of segment [lo, hi) split at mid is mid - 1 (the node between leaf positions mid - 1 and mid): no allocation, every idx in [0, n - 1) used once.
+// Depth: a split is taken only if both sides can still be finished by median splits inside the height H the subtree had BEFORE (level + 1 + ceil(log2(larger side))
+// <= H); otherwise, and when all centroids of the segment coincide, the segment is cut at its object median (ceil(log2) drops by one per level, H >= ceil(log2 n)
+// holds for every binary tree). A rebuilt subtree is therefore never taller than the one it replaces: the depth bound above k_emc_keys / the stack bound of
+// bvh_trace.hip (3 * (MR_SAH_LEVELS + (38 - MR_SAH_PREFIX) + ceil(log2 T))) holds unchanged.
+// Ties are broken by (axis, position) and the leaves / ids are sorted first, so the topology does not vary from run to run.
+#define MR_SAH_BOTTOM 256           // default L; MIRRES_SAH_BOTTOM = 4 .. MR_SB_MAX overrides it (the sweep of profiles/sah_bottom_counts.txt)
+#define MR_SB_MAX 512
+struct SbState { uint32_t n_roots, skipped; };
+__global__ void __launch_bounds__(256) k_sb_prepare(int T, const int32_t* __restrict__ pinfo, const uint32_t* __restrict__ range, int32_t* __restrict__ parent,
+                                                    uint32_t* __restrict__ cnt, SbState* st) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g == 0) { st->n_roots = 0; st->skipped = 0; parent[0] = -1; }
+    if (g >= 2 * T - 1) return;
+    if (g >= T - 1) { cnt[g] = 1u; return; }
+    parent[pinfo[3 * (size_t)g]] = g; parent[pinfo[3 * (size_t)g + 1]] = g;
+    const uint32_t lo = range[2 * (size_t)g], hi = range[2 * (size_t)g + 1];
+    cnt[g] = hi >= lo ? hi - lo + 1u : 0u;                      // 0: rewritten by the SAH top, summed by k_sb_count
+}
+MR_DEV bool sb_ranged(int n, int T, const uint32_t* __restrict__ range) { return n >= T - 1 || range[2 * (size_t)n + 1] >= range[2 * (size_t)n]; }
+__global__ void __launch_bounds__(256) k_sb_count(int T, const uint32_t* __restrict__ range, const int32_t* __restrict__ parent, uint32_t* __restrict__ cnt, uint32_t L) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= 2 * T - 1 || !sb_ranged(n, T, range)) return;
+    int p = parent[n];
+    if (p < 0 || sb_ranged(p, T, range)) return;
+    const uint32_t c = cnt[n];                                  // final: nodes with a range receive no additions
+    for (int guard = 0; p >= 0 && guard < 4 * MR_SAH_LEVELS; guard++) {
+        if (atomicAdd(&cnt[p], c) > L) break;                   // the additions that took p past L went on upwards: every ancestor ends above L as well
+        p = parent[p];
+    }
+}
+__global__ void __launch_bounds__(256) k_sb_select(int T, const int32_t* __restrict__ parent, const uint32_t* __restrict__ cnt, uint32_t L, int32_t* __restrict__ roots, SbState* st) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= T - 1) return;
+    const uint32_t c = cnt[n];
+    if (c < 3u || c > L) return;
+    const int p = parent[n];
+    if (p >= 0 && cnt[p] <= L) return;                          // not maximal
+    roots[atomicAdd(&st->n_roots, 1u)] = n;                     // disjoint subtrees of >= 3 leaves: fewer than T / 3 + 1 roots
+}
+MR_DEV int sb_ceil_log2(int x) { return x <= 1 ? 0 : 32 - __clz((uint32_t)(x - 1)); }
+MR_DEV float sb_area(const float* b) { const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2]; return dx * dy + dy * dz + dz * dx; }
+// segmented inclusive scan of the boxes in s_P along the positions: DIR = -1 prefix (from the segment's start), +1 suffix (from its end)
+template <int DIR>
+MR_DEV void sb_scan(float (*s_P)[MR_SB_MAX], const uint16_t* s_lo, const uint16_t* s_hi, int n, int maxlen) {
+    const int t = threadIdx.x;
+    for (int d = 1; d < maxlen; d <<= 1) {
+        float v[MR_SB_MAX / 256][6]; bool take[MR_SB_MAX / 256];
+#pragma unroll
+        for (int e = 0; e < MR_SB_MAX / 256; e++) {
+            const int i = t + 256 * e, j = i + DIR * d;
+            take[e] = i < n && (DIR < 0 ? j >= (int)s_lo[i] : j < (int)s_hi[i]);
+            if (take[e]) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) v[e][k] = s_P[k][j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < MR_SB_MAX / 256; e++) {
+            const int i = t + 256 * e;
+            if (take[e]) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) { s_P[k][i] = fminf(s_P[k][i], v[e][k]); s_P[3 + k][i] = fmaxf(s_P[3 + k][i], v[e][3 + k]); }
+            }
+        }
+        __syncthreads();
+    }
+}
+// stable sort of n <= MR_SB_MAX distinct (key, index) pairs by counting: out[rank] = index
+MR_DEV void sb_rank_sort(const uint32_t* key, int n, uint16_t* out) {
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const uint32_t ki = key[i]; int r = 0;
+        for (int j = 0; j < n; j++) { const uint32_t kj = key[j]; r += (kj < ki || (kj == ki && j < i)) ? 1 : 0; }
+        out[r] = (uint16_t)i;
+    }
+}
+__global__ void __launch_bounds__(256) k_sb_rebuild(int T, int32_t* __restrict__ pinfo, float* __restrict__ paabb, const uint32_t* __restrict__ cnt, const int32_t* __restrict__ roots,
+                                                    SbState* st) {
+    __shared__ float s_box[6][MR_SB_MAX];             // leaf boxes, by local leaf index
+    __shared__ float s_P[6][MR_SB_MAX];               // scan buffer, by position (during the collection: the two frontiers and the unsorted id lists)
+    __shared__ float s_suf[MR_SB_MAX];                // area of the suffix box [i, hi)
+    __shared__ uint32_t s_ckey[3][MR_SB_MAX];         // centroid per axis, order-preserving bits, by local leaf index
+    __shared__ uint16_t s_ord[2][3][MR_SB_MAX];       // local leaf index at position i of axis order a (ping-pong across the partition)
+    __shared__ unsigned long long s_best[MR_SB_MAX];  // per segment (at its lo): min over (cost bits, axis, position)
+    __shared__ uint32_t s_split[MR_SB_MAX];           // per segment (at its lo): mid | axis << 16; 0 = not split at this level
+    __shared__ uint32_t s_scan[MR_SB_MAX];            // left-side flags of the three orders, 10 bits each, prefix-summed
+    __shared__ uint16_t s_lo[MR_SB_MAX], s_hi[MR_SB_MAX]; __shared__ int16_t s_par[MR_SB_MAX];   // segment of position i; parent idx * 2 + side (-1: the subtree root)
+    __shared__ uint8_t s_side[MR_SB_MAX];
+    __shared__ int32_t s_leaf[MR_SB_MAX], s_int[MR_SB_MAX];      // node ids of the leaves (ascending) and of the internal nodes (ascending, then the root swapped to its idx)
+    __shared__ int s_n[4], s_maxlen[2];
+    const int t = threadIdx.x, LEAF = T - 1;
+    int32_t* s_tmp = reinterpret_cast<int32_t*>(&s_P[0][0]);     // [6 * MR_SB_MAX] words: frontier A, frontier B, leaf ids, internal ids (unsorted)
+    for (uint32_t r = blockIdx.x; r < st->n_roots; r += gridDim.x) {
+        const int root = roots[r], n = (int)cnt[root];
+        __syncthreads();                                         // the previous subtree is done with the shared arrays
+        if (n < 3 || n > MR_SB_MAX) continue;                    // uniform
+        // ---- collect the subtree breadth-first: its leaves, its internal ids, its height
+        if (t == 0) { s_tmp[0] = root; s_n[0] = 1; s_n[1] = 0; s_n[2] = 0; s_n[3] = 0; }
+        __syncthreads();
+        int height = 0, cur = 0; bool bad = false;
+        while (true) {
+            const int nf = s_n[cur];
+            if (nf == 0) break;
+            if (nf > MR_SB_MAX || height > 4 * MR_SAH_LEVELS + 64) { bad = true; break; }      // uniform (cannot happen with consistent counts)
+            int32_t* fin = s_tmp + cur * MR_SB_MAX; int32_t* fout = s_tmp + (cur ^ 1) * MR_SB_MAX;
+            for (int i = t; i < nf; i += 256) {
+                const int node = fin[i];
+                const int q = atomicAdd(&s_n[3], 1); if (q < MR_SB_MAX) s_tmp[3 * MR_SB_MAX + q] = node;
+                for (int k = 0; k < 2; k++) {
+                    const int c = pinfo[3 * (size_t)node + k];
+                    if (c >= LEAF) { const int j = atomicAdd(&s_n[2], 1); if (j < MR_SB_MAX) s_tmp[2 * MR_SB_MAX + j] = c; }
+                    else { const int j = atomicAdd(&s_n[cur ^ 1], 1); if (j < MR_SB_MAX) fout[j] = c; }
+                }
+            }
+            __syncthreads();
+            if (t == 0) s_n[cur] = 0;
+            cur ^= 1; height++;
+            __syncthreads();
+        }
+        if (bad || s_n[2] != n || s_n[3] != n - 1) { if (t == 0) atomicAdd(&st->skipped, 1u); continue; }      // uniform: leave the subtree as it is
+        // ---- ids in ascending order (the collection order depends on LDS atomics), boxes and centroid keys
+        uint16_t* rk = &s_ord[1][0][0];
+        sb_rank_sort(reinterpret_cast<const uint32_t*>(s_tmp + 2 * MR_SB_MAX), n, rk);
+        sb_rank_sort(reinterpret_cast<const uint32_t*>(s_tmp + 3 * MR_SB_MAX), n - 1, rk + MR_SB_MAX);
+        __syncthreads();
+        for (int i = t; i < n; i += 256) s_leaf[i] = s_tmp[2 * MR_SB_MAX + rk[i]];
+        for (int i = t; i < n - 1; i += 256) s_int[i] = s_tmp[3 * MR_SB_MAX + rk[MR_SB_MAX + i]];
+        __syncthreads();
+        for (int i = t; i < n; i += 256) {
+            const float* bx = paabb + 6 * (size_t)s_leaf[i];
+#pragma unroll
+            for (int k = 0; k < 6; k++) s_box[k][i] = bx[k];
+#pragma unroll
+            for (int a = 0; a < 3; a++) s_ckey[a][i] = f2ord(bx[a] + 0.5f * (bx[3 + a] - bx[a]));
+            s_lo[i] = 0; s_hi[i] = (uint16_t)n; s_par[i] = -1;
+        }
+        if (t == 0) { s_maxlen[0] = n; s_maxlen[1] = 1; }
+        __syncthreads();
+        for (int a = 0; a < 3; a++) sb_rank_sort(s_ckey[a], n, s_ord[0][a]);
+        __syncthreads();
+        // ---- top-down, one level of the new subtree per iteration
+        int ob = 0;
+        for (int level = 0; level < height; level++) {
+            const int maxlen = s_maxlen[level & 1];
+            if (maxlen < 2) break;
+            for (int i = t; i < n; i += 256) { s_best[i] = ~0ull; s_split[i] = 0u; }
+            if (t == 0) s_maxlen[(level & 1) ^ 1] = 1;
+            for (int a = 0; a < 3; a++) {
+                for (int i = t; i < n; i += 256) { const int j = s_ord[ob][a][i];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) s_P[k][i] = s_box[k][j]; }
+                __syncthreads();
+                sb_scan<+1>(s_P, s_lo, s_hi, n, maxlen);
+                for (int i = t; i < n; i += 256) { float b[6];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) b[k] = s_P[k][i];
+                    s_suf[i] = sb_area(b); }
+                __syncthreads();
+                for (int i = t; i < n; i += 256) { const int j = s_ord[ob][a][i];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) s_P[k][i] = s_box[k][j]; }
+                __syncthreads();
+                sb_scan<-1>(s_P, s_lo, s_hi, n, maxlen);
+                for (int i = t; i < n; i += 256) {
+                    const int lo = s_lo[i], hi = s_hi[i];
+                    if (i + 1 >= hi) continue;                   // the last position is no split
+                    float b[6];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) b[k] = s_P[k][i];
+                    const float cost = sb_area(b) * (float)(i - lo + 1) + s_suf[i + 1] * (float)(hi - 1 - i);      // >= 0, or NaN / inf on wild boxes: those sort last
+                    atomicMin(&s_best[lo], ((unsigned long long)__float_as_uint(cost) << 32) | (unsigned long long)((uint32_t)a << 16 | (uint32_t)i));
+                }
+                __syncthreads();                                 // s_P: the prefix boxes of this axis stay until the next axis loads (after a == 2: until the decision below)
+            }
+            // ---- decide: one thread per segment of two leaves or more
+            for (int i = t; i < n; i += 256) {
+                const int lo = s_lo[i], hi = s_hi[i], m = hi - lo;
+                if (i != lo || m < 2) continue;
+                const int o0 = s_ord[ob][0][lo], o1 = s_ord[ob][1][lo], o2 = s_ord[ob][2][lo];
+                const bool same = s_ckey[0][o0] == s_ckey[0][s_ord[ob][0][hi - 1]] && s_ckey[1][o1] == s_ckey[1][s_ord[ob][1][hi - 1]] && s_ckey[2][o2] == s_ckey[2][s_ord[ob][2][hi - 1]];
+                const unsigned long long key = s_best[lo];
+                int axis = (int)((key >> 16) & 3u), mid = (int)(key & 0xffffu) + 1;
+                if (same || (uint32_t)(key >> 32) >= 0x7f800000u || axis > 2 || mid <= lo || mid >= hi || level + 1 + sb_ceil_log2(max(mid - lo, hi - mid)) > height) { axis = 0; mid = lo + (m >> 1); }      // object median
+                const int big = hi - mid > mid - lo ? hi - mid : mid - lo;
+                s_split[lo] = (uint32_t)mid | (uint32_t)axis << 16;
+                const int idx = mid - 1;
+                if (level == 0) {                                // the one segment of level 0: the root's id goes to the root's idx
+                    int rp = 0; while (s_int[rp] != root) rp++;
+                    s_int[rp] = s_int[idx]; s_int[idx] = root;
+                }
+                const int id = s_int[idx];
+                const int par = s_par[lo];
+                if (par >= 0) pinfo[3 * (size_t)s_int[par >> 1] + (par & 1)] = id;
+                if (mid - lo == 1) pinfo[3 * (size_t)id] = s_leaf[s_ord[ob][axis][lo]];
+                if (hi - mid == 1) pinfo[3 * (size_t)id + 1] = s_leaf[s_ord[ob][axis][hi - 1]];
+                pinfo[3 * (size_t)id + 2] = 0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) paabb[6 * (size_t)id + k] = s_P[k][hi - 1];      // inclusive prefix at the segment's end: the union of all its leaves
+                atomicMax(&s_maxlen[(level & 1) ^ 1], big);
+            }
+            __syncthreads();
+            // ---- which side every leaf goes to, then the stable partition of the three orders
+            for (int i = t; i < n; i += 256) {
+                const uint32_t sp = s_split[s_lo[i]];
+                if (sp) s_side[s_ord[ob][sp >> 16][i]] = i >= (int)(sp & 0xffffu) ? 1 : 0;
+                else s_side[s_ord[ob][0][i]] = 0;                // a single leaf stays where it is
+            }
+            __syncthreads();
+            for (int i = t; i < n; i += 256) s_scan[i] = (s_side[s_ord[ob][0][i]] ? 0u : 1u) | (s_side[s_ord[ob][1][i]] ? 0u : 1u << 10) | (s_side[s_ord[ob][2][i]] ? 0u : 1u << 20);
+            __syncthreads();
+            for (int d = 1; d < n; d <<= 1) {                    // inclusive sums over all positions; a segment's own count = the difference to its start
+                uint32_t v[MR_SB_MAX / 256];
+#pragma unroll
+                for (int e = 0; e < MR_SB_MAX / 256; e++) { const int i = t + 256 * e; v[e] = (i < n && i >= d) ? s_scan[i - d] : 0u; }
+                __syncthreads();
+#pragma unroll
+                for (int e = 0; e < MR_SB_MAX / 256; e++) { const int i = t + 256 * e; if (i < n) s_scan[i] += v[e]; }
+                __syncthreads();
+            }
+            for (int i = t; i < n; i += 256) {
+                const int lo = s_lo[i], hi = s_hi[i];
+                const uint32_t sp = s_split[lo]; const int mid = sp ? (int)(sp & 0xffffu) : hi;
+                const uint32_t base = lo > 0 ? s_scan[lo - 1] : 0u;
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    const int j = s_ord[ob][a][i]; const uint32_t left = s_side[j] ? 0u : 1u;
+                    const int before = (int)(((s_scan[i] - base) >> (10 * a)) & 1023u) - (int)left;      // left-side leaves of this segment in front of position i (fields never borrow: sums grow with i)
+                    const int np = left ? lo + before : mid + (i - lo - before);
+                    s_ord[ob ^ 1][a][np] = (uint16_t)j;
+                }
+            }
+            __syncthreads();
+            for (int i = t; i < n; i += 256) {                   // the segments of the next level (every thread touches its own positions only; s_split is not written here)
+                const int lo = s_lo[i];
+                const uint32_t sp = s_split[lo];
+                if (!sp) continue;
+                const int mid = (int)(sp & 0xffffu);
+                if (i >= mid) { s_lo[i] = (uint16_t)mid; s_par[i] = (int16_t)(2 * (mid - 1) + 1); }
+                else { s_hi[i] = (uint16_t)mid; s_par[i] = (int16_t)(2 * (mid - 1)); }
+            }
+            __syncthreads();
+            ob ^= 1;
+        }
     }
 }
 
@@ -812,8 +1070,24 @@ static int private_sah_top(mirres_bvh* b, int T, hipStream_t s) {               
         else k_sah_assign<false><<<256, blk, 0, s>>>(level, st, sn, b->sah_iref, b->sah_inode, b->p_aabb);
     }
     k_sah_tail<<<1, 1024, 0, s>>>(MR_SAH_TAIL, st, sn, b->sah_iref, b->sah_inode, b->p_aabb, sb);
-    k_sah_install<<<256, blk, 0, s>>>(st, sn, b->sah_top, b->p_info, b->p_aabb);
+    k_sah_install<<<256, blk, 0, s>>>(st, sn, b->sah_top, b->p_info, b->p_aabb, b->p_range);
     MR_LAUNCH_CHECK("bvh_private_sah_top");
+    return 0;
+}
+static uint32_t sah_bottom_leaves() {
+    static const uint32_t L = [] { const char* e = getenv("MIRRES_SAH_BOTTOM"); const int v = e ? atoi(e) : MR_SAH_BOTTOM; return (uint32_t)(v < 4 ? 4 : (v > MR_SB_MAX ? MR_SB_MAX : v)); }();
+    return L;
+}
+static int private_sah_bottom(mirres_bvh* b, int T, hipStream_t s) {                     // its lower levels rebuilt by sweep SAH inside every subtree of <= L leaves
+    const int blk = 256, grd2 = grid_for(2 * T, blk);
+    const uint32_t L = sah_bottom_leaves();
+    SbState* st = reinterpret_cast<SbState*>(b->sb_state);
+    k_sb_prepare<<<grd2, blk, 0, s>>>(T, b->p_info, b->p_range, b->p_parent, b->sb_cnt, st);
+    k_sb_count<<<grd2, blk, 0, s>>>(T, b->p_range, b->p_parent, b->sb_cnt, L);
+    k_sb_select<<<grid_for(T, blk), blk, 0, s>>>(T, b->p_parent, b->sb_cnt, L, b->sb_roots, st);
+    const int blocks = T / 3 + 1 < 2048 ? T / 3 + 1 : 2048;
+    k_sb_rebuild<<<blocks, blk, 0, s>>>(T, b->p_info, b->p_aabb, b->sb_cnt, b->sb_roots, st);
+    MR_LAUNCH_CHECK("bvh_private_sah_bottom");
     return 0;
 }
 
@@ -861,6 +1135,7 @@ int mirres_bvh_create(mirres_bvh_t** out, int max_tris) {
         for (auto& e : z) { e.count = 0; for (int q = 0; q < 3; q++) { e.box[q] = 0xffffffffu; e.box[3 + q] = 0u; } }
         MR_HIP(hipMemcpy(b->sah_bins, z.data(), sizeof(SahBin) * z.size(), hipMemcpyHostToDevice));      // every split leaves its bins clean again
     }
+    MR_HIP(hipMalloc(&b->sb_state, 16)); MR_HIP(hipMalloc(&b->sb_cnt, sizeof(uint32_t) * 2 * T)); MR_HIP(hipMalloc(&b->sb_roots, sizeof(int32_t) * (T / 3 + 2)));      // SAH bottom (k_sb_*)
     MR_HIP(hipMalloc(&b->top85q, sizeof(Node4q) * 85));
     MR_HIP(hipMalloc(&b->top341q, sizeof(Node4q) * 341));
     MR_HIP(hipMalloc(&b->root_box, sizeof(float) * 8));
@@ -876,7 +1151,7 @@ void mirres_bvh_destroy(mirres_bvh_t* b) {
     if (!b) return;
     void* ptrs[] = {b->ele_aabb, b->extent, b->keys_in, b->keys_out, b->vals_in, b->vals_out, b->parent, b->flags, b->own_info,
                     b->own_aabb, b->nodes, b->tris, b->root_box, b->sort_tmp, b->work, b->redo[0], b->redo[1], b->dump_pool, b->lvl, b->nodes4q, b->leaves, b->top85q, b->top341q,
-                    b->p_keys, b->p_vals, b->p_key64, b->p_info, b->p_aabb, b->p_range, b->p_parent, b->sah_state, b->sah_nodes, b->sah_bins, b->sah_iref, b->sah_inode, b->sah_top};
+                    b->p_keys, b->p_vals, b->p_key64, b->p_info, b->p_aabb, b->p_range, b->p_parent, b->sah_state, b->sah_nodes, b->sah_bins, b->sah_iref, b->sah_inode, b->sah_top, b->sb_state, b->sb_cnt, b->sb_roots};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (b->err) (void)hipHostFree(b->err);
     delete b;
@@ -908,14 +1183,16 @@ int mirres_bvh_build_level(mirres_bvh_t* b, const float* vert, int V, const int3
     }
     k_pack<<<grd, blk, 0, s>>>(T, info, aabb, vert, tri, b->nodes, b->tris, b->root_box);
     // the 4-wide layout of the shadow-ray / ordered closest-hit kernels: collapsed from the private hierarchy — extended-Morton tree with its upper levels rebuilt by
-    // the binned-SAH top (2, default), the plain extended-Morton tree (MIRRES_PRIVATE_TREE=1) — or (0) from the reference LBVH itself
-    static const int private_tree_env = [] { const char* e = getenv("MIRRES_PRIVATE_TREE"); return e ? atoi(e) : 2; }();
+    // the binned-SAH top and its lower levels by the sweep-SAH bottom (3, default), without the bottom (MIRRES_PRIVATE_TREE=2), the plain extended-Morton tree (1) — or
+    // (0) from the reference LBVH itself
+    static const int private_tree_env = [] { const char* e = getenv("MIRRES_PRIVATE_TREE"); return e ? atoi(e) : 3; }();
     int level = private_level >= 0 ? private_level : private_tree_env;
-    if (level > 2) level = 2;
+    if (level > 3) level = 3;
     if (T < 8) level = 0;
     if (level >= 1) {
         int rc = private_step1(b, T, aabb, s); if (rc) return rc;
-        if (level == 2) { rc = private_sah_top(b, T, s); if (rc) return rc; }
+        if (level >= 2) { rc = private_sah_top(b, T, s); if (rc) return rc; }
+        if (level >= 3) { rc = private_sah_bottom(b, T, s); if (rc) return rc; }
         k_pack4q<true><<<grd, blk, 0, s>>>(T, b->p_info, b->p_aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
     } else k_pack4q<false><<<grd, blk, 0, s>>>(T, info, aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
     b->private_level = level;
@@ -929,21 +1206,25 @@ int mirres_bvh_build(mirres_bvh_t* b, const float* vert, int V, const int32_t* t
     return mirres_bvh_build_level(b, vert, V, tri, T, info, aabb, sorted_codes, -1, stream);
 }
 
-int mirres_bvh_private_level(mirres_bvh_t* b) { return b ? b->private_level : -1; }
+// 0 / 1 / 2 as before the SAH bottom existed: which hierarchy stands ABOVE the clusters (a level-3 build reports 2: the bottom step changes nothing up there);
+// mirres_bvh_tree_level reports the level itself, 0 .. 3
+int mirres_bvh_private_level(mirres_bvh_t* b) { return b ? (b->private_level > 2 ? 2 : b->private_level) : -1; }
+int mirres_bvh_tree_level(mirres_bvh_t* b) { return b ? b->private_level : -1; }
 
-// step 2 on top of a level-1 build (same arrays as the build call): binned-SAH top + the 4-wide collapse again. Every hierarchy gives the same answers.
+// steps 2 and 3 on top of a level-1 build (same arrays as the build call): binned-SAH top + sweep-SAH bottom + the 4-wide collapse again. Every hierarchy gives the same answers.
 int mirres_bvh_upgrade(mirres_bvh_t* b, const float* vert, const int32_t* tri, const int32_t* info, const float* aabb, void* stream) {
     if (!b || !vert || !tri) { set_error("mirres_bvh_upgrade: null argument"); return MIRRES_E_ARG; }
     if (b->T < 2) { set_error("mirres_bvh_upgrade: BVH not built"); return MIRRES_E_STATE; }
-    if (b->private_level != 1) return MIRRES_OK;                  // nothing to add (level 2 already, or a level-0 build / tiny mesh that has no private tree)
+    if (b->private_level != 1) return MIRRES_OK;                  // nothing to add (level 2 / 3 already, or a level-0 build / tiny mesh that has no private tree)
     hipStream_t s = (hipStream_t)stream;
     if (!info) info = b->own_info;
     if (!aabb) aabb = b->own_aabb;
     const int T = b->T, blk = 256, grd = grid_for(T, blk);
     int rc = private_sah_top(b, T, s); if (rc) return rc;
+    rc = private_sah_bottom(b, T, s); if (rc) return rc;
     k_pack4q<true><<<grd, blk, 0, s>>>(T, b->p_info, b->p_aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
     if (T - 1 >= 341 * 4) { k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top85q, 85); k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top341q, 341); }
-    b->private_level = 2;
+    b->private_level = 3;
     MR_LAUNCH_CHECK("bvh_upgrade");
     return MIRRES_OK;
 }
@@ -957,6 +1238,26 @@ int mirres_debug_sah_state(mirres_bvh_t* b, uint32_t* h_out) {
     h_out[0] = st.n_items; h_out[1] = st.n_top; h_out[2] = st.n_nodes; h_out[3] = st.n_internal; h_out[4] = st.n_resolved; h_out[5] = st.fail;
     int lv = 0; while (lv + 1 < MR_SAH_LEVELS + 2 && st.first[lv + 1] > st.first[lv]) lv++;
     h_out[6] = (uint32_t)lv; h_out[7] = 0;
+    return MIRRES_OK;
+}
+
+// development aid (not part of include/mirres.h): counters of the last SAH-bottom build: subtrees rebuilt, subtrees left as they were (inconsistent counts: never), L
+int mirres_debug_sah_bottom(mirres_bvh_t* b, uint32_t* h_out) {
+    if (!b || !h_out || !b->sb_state) return MIRRES_E_ARG;
+    SbState st;
+    MR_HIP(hipDeviceSynchronize());
+    MR_HIP(hipMemcpy(&st, b->sb_state, sizeof(st), hipMemcpyDeviceToHost));
+    h_out[0] = st.n_roots; h_out[1] = st.skipped; h_out[2] = sah_bottom_leaves();
+    return MIRRES_OK;
+}
+
+// development aid (not part of include/mirres.h): the private binary hierarchy the 4-wide layout was collapsed from — info i32[2T-1,3] (leaf entries: (0, 0, slot)),
+// aabb f32[2T-1,6] — for the structural check of tests/test_gpu_sah_bottom.py (exact box unions, binary height); levels >= 1 only
+int mirres_debug_private_tree(mirres_bvh_t* b, int32_t* h_info, float* h_aabb) {
+    if (!b || b->T < 2 || b->private_level < 1 || !h_info || !h_aabb) return MIRRES_E_ARG;
+    MR_HIP(hipDeviceSynchronize());
+    MR_HIP(hipMemcpy(h_info, b->p_info, sizeof(int32_t) * 3 * (size_t)(2 * b->T - 1), hipMemcpyDeviceToHost));
+    MR_HIP(hipMemcpy(h_aabb, b->p_aabb, sizeof(float) * 6 * (size_t)(2 * b->T - 1), hipMemcpyDeviceToHost));
     return MIRRES_OK;
 }
 

@@ -97,7 +97,7 @@ struct RaySrc { const float4* grec; const float4* rrec; float vis_near; int skip
 
 struct mirres_bvh {
     int max_tris = 0, T = 0, V = 0;
-    int private_level = 0;          // what the traversal layout was collapsed from: 0 reference LBVH, 1 extended-Morton tree, 2 + binned-SAH top (mirres_bvh_upgrade)
+    int private_level = 0;          // what the traversal layout was collapsed from: 0 reference LBVH, 1 extended-Morton tree, 2 + binned-SAH top, 3 + sweep-SAH bottom (mirres_bvh_upgrade)
     // build workspace
     float* ele_aabb = nullptr;      // [T,6]
     uint32_t* extent = nullptr;     // [6] order-preserving uint encoding of min xyz / max xyz
@@ -115,7 +115,7 @@ struct mirres_bvh {
     mr::Node4q* top85q = nullptr, *top341q = nullptr;   // [85], [341] breadth-first prefixes of nodes4q, children inside tagged MR_TOPBIT
     // private steering hierarchy (bvh_build.hip k_emc_*): extended-Morton keys / slots, 64-bit keys, node arrays in the reference's own layout (leaf info[.][2] = slot)
     uint32_t *p_keys = nullptr, *p_vals = nullptr, *p_range = nullptr; unsigned long long* p_key64 = nullptr; int32_t* p_info = nullptr; float* p_aabb = nullptr;
-    int32_t* p_parent = nullptr; void *sah_state = nullptr, *sah_nodes = nullptr, *sah_bins = nullptr; int32_t *sah_iref = nullptr, *sah_inode = nullptr, *sah_top = nullptr;   // SAH top over prefix clusters (k_sah_*)
+    int32_t* p_parent = nullptr; void *sah_state = nullptr, *sah_nodes = nullptr, *sah_bins = nullptr; int32_t *sah_iref = nullptr, *sah_inode = nullptr, *sah_top = nullptr; void* sb_state = nullptr; uint32_t* sb_cnt = nullptr; int32_t* sb_roots = nullptr;   // SAH top over prefix clusters (k_sah_*)
     float* root_box = nullptr;      // [6]
     uint32_t* work = nullptr;       // [MR_WSETS * MR_WSET] head sets of the persistent traversal kernels (HeadSet above)
     unsigned long long* dbg = nullptr;   // see BvhView::dbg

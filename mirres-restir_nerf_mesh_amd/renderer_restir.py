@@ -78,8 +78,11 @@ class restirbvhWorker:
         info = torch.empty((2 * T - 1, 3), dtype=torch.int32, device=vrt.device)
         aabb = torch.empty((2 * T - 1, 6), dtype=torch.float32, device=vrt.device)
         # The private steering hierarchy is built in two steps (round 6): the extended-Morton tree now, its binned-SAH top (0.9-1.4 ms per build) only when a frame is
-        # long enough to pay for it (ensure_hierarchy_for, called by render_fused). MIRRES_PRIVATE_TREE = 0 / 1 / 2 fixes the level at build time as before.
+        # long enough to pay for it (ensure_hierarchy_for, called by render_fused), together with the sweep-SAH bottom (level 3). MIRRES_PRIVATE_TREE = 0 / 1 / 2 / 3
+        # fixes the level at build time as before.
         env = os.environ.get("MIRRES_PRIVATE_TREE")
+        if env not in (None, "", "auto", "0", "1", "2", "3"):
+            raise ValueError("MIRRES_PRIVATE_TREE must be 0, 1, 2, 3 or auto, not %r" % env)
         level = int(env) if env not in (None, "", "auto") else 1
         check(lib().mirres_bvh_build_level(self.h, vrt.data_ptr(), vrt.shape[0], v_ind.data_ptr(), T, info.data_ptr(), aabb.data_ptr(), None, level, stream_ptr()),
               "mirres_bvh_build_level")
@@ -90,7 +93,7 @@ class restirbvhWorker:
     SAH_TOP_FROM_PIXEL_SAMPLES = 1.0e8      # the SAH top returns ~4-7 % of a frame's traversal time: from about 1e8 pixel-samples on that is more than its build (800 x 800 x 32 spp = 2e7: not; 1600 x 1600 x 512 = 1.3e9: yes; profiles/r06_ab_train_tree.txt)
 
     def upgrade(self):
-        """Completes the private hierarchy (binned-SAH top) on top of the current build; a no-op when it is complete or was fixed by MIRRES_PRIVATE_TREE."""
+        """Completes the private hierarchy (binned-SAH top, sweep-SAH bottom) on top of the current build; a no-op when it is complete or was fixed by MIRRES_PRIVATE_TREE."""
         if self.h is None or self.LBVHNode_info is None:
             return
         vrt, v_ind = self._keep

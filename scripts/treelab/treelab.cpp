@@ -196,6 +196,64 @@ static BTree build_ploc(const Mesh& M, int R = 16, int bits = 21, const std::vec
     B.root = ref[0]; return B;
 }
 
+// ---- sweep-SAH bottom, as shipped (bvh_build.hip k_sb_rebuild): every maximal subtree of 3 .. L leaves is rebuilt top-down by exact sweep SAH over the leaves' own
+// boxes — three axes, centroids sorted (ties by leaf order), cost = area x count in fp32, the cheapest of the 3 (m - 1) object splits, ties to the lower (axis, position).
+// Object median instead when all centroids of a segment coincide or when the larger side could not be finished by median splits inside the height the subtree had
+// before (so no subtree gets taller). The subtree root keeps its id and the rebuilt nodes reuse the ids the subtree had (node "idx" of a split at mid is mid - 1).
+static int ceil_log2i(int x) { int r = 0; while ((1 << r) < x) r++; return r; }
+static void subtree_counts(const BTree& B, std::vector<int>& cnt, std::vector<int>& height, std::vector<int>& parent, std::vector<int>& order) {
+    int n = (int)B.l.size(); cnt.assign(n, 0); height.assign(n, 0); parent.assign(n, -1); order.clear(); std::vector<int> st = {B.root};
+    while (!st.empty()) { int x = st.back(); st.pop_back(); order.push_back(x); for (int ch : {B.l[x], B.r[x]}) if (ch >= 0) { parent[ch] = x; st.push_back(ch); } }
+    for (int k = (int)order.size() - 1; k >= 0; k--) { int x = order[k]; int c = 0, h = 0; for (int ch : {B.l[x], B.r[x]}) { c += ch >= 0 ? cnt[ch] : 1; h = std::max(h, ch >= 0 ? height[ch] : 0); } cnt[x] = c; height[x] = h + 1; }
+}
+static BTree build_sah_bottom(BTree B, const Mesh& M, int L) {
+    std::vector<int> cnt, height, parent, order; subtree_counts(B, cnt, height, parent, order);
+    auto key = [](float f) { uint32_t b; memcpy(&b, &f, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
+    int rebuilt = 0;
+    for (int root : order) {
+        if (cnt[root] < 3 || cnt[root] > L || (parent[root] >= 0 && cnt[parent[root]] <= L)) continue;
+        rebuilt++;
+        std::vector<int> leaf, ids, st = {root};
+        while (!st.empty()) { int x = st.back(); st.pop_back(); ids.push_back(x); for (int ch : {B.l[x], B.r[x]}) { if (ch >= 0) st.push_back(ch); else leaf.push_back(~ch); } }
+        std::sort(leaf.begin(), leaf.end()); std::sort(ids.begin(), ids.end());
+        const int n = (int)leaf.size(), H = height[root];
+        struct Seg { int lo, hi, par, level; std::vector<int> mem; };      // mem: local leaf indices; par: parent idx * 2 + side
+        std::vector<Seg> work; { Seg s0{0, n, -1, 0, {}}; s0.mem.resize(n); std::iota(s0.mem.begin(), s0.mem.end(), 0); work.push_back(s0); }
+        std::vector<int> nl(n - 1), nr(n - 1);      // by idx: children as final refs (filled when known)
+        std::vector<std::pair<int, int>> link;      // (parent idx * 2 + side, child idx)
+        int root_idx = -1;
+        while (!work.empty()) {
+            Seg s = work.back(); work.pop_back(); const int m = s.hi - s.lo;
+            std::vector<int> ord[3]; bool same = true;
+            for (int a = 0; a < 3; a++) { ord[a] = s.mem; std::sort(ord[a].begin(), ord[a].end(), [&](int x, int y) { uint32_t kx = key(M.cen[3 * leaf[x] + a]), ky = key(M.cen[3 * leaf[y] + a]); return kx != ky ? kx < ky : x < y; });
+                same = same && key(M.cen[3 * leaf[ord[a].front()] + a]) == key(M.cen[3 * leaf[ord[a].back()] + a]); }
+            float best = 0; int best_axis = -1, best_pos = -1;
+            for (int a = 0; a < 3; a++) { std::vector<float> suf(m + 1, 0.f); Box acc = empty_box(); for (int i = m - 1; i >= 0; i--) { acc = merge(acc, M.tb[leaf[ord[a][i]]]); suf[i] = area(acc); }
+                acc = empty_box(); for (int i = 0; i + 1 < m; i++) { acc = merge(acc, M.tb[leaf[ord[a][i]]]); float cost = area(acc) * (float)(i + 1) + suf[i + 1] * (float)(m - 1 - i);
+                    if (best_axis < 0 || cost < best) { best = cost; best_axis = a; best_pos = i; } } }
+            int axis = best_axis, mid = best_pos + 1;
+            if (same || !(best >= 0.f && best < INFINITY) || s.level + 1 + ceil_log2i(std::max(mid, m - mid)) > H) { axis = 0; mid = m >> 1; }
+            const int idx = s.lo + mid - 1;
+            if (s.par < 0) root_idx = idx; else link.push_back({s.par, idx});
+            Seg a{s.lo, s.lo + mid, 2 * idx, s.level + 1, std::vector<int>(ord[axis].begin(), ord[axis].begin() + mid)}, b{s.lo + mid, s.hi, 2 * idx + 1, s.level + 1, std::vector<int>(ord[axis].begin() + mid, ord[axis].end())};
+            if (mid == 1) nl[idx] = ~leaf[a.mem[0]]; else work.push_back(a);
+            if (m - mid == 1) nr[idx] = ~leaf[b.mem[0]]; else work.push_back(b);
+        }
+        { int rp = (int)(std::find(ids.begin(), ids.end(), root) - ids.begin()); std::swap(ids[rp], ids[root_idx]); }
+        for (auto& [ps, ci] : link) ((ps & 1) ? nr : nl)[ps >> 1] = ids[ci];
+        for (int i = 0; i < n - 1; i++) { B.l[ids[i]] = nl[i]; B.r[ids[i]] = nr[i]; }
+    }
+    printf("   SAH bottom L = %d: %d subtrees rebuilt\n", L, rebuilt);
+    return B;
+}
+// every triangle below the root exactly once, every internal node at most once
+static bool tree_ok(const BTree& B, const Mesh& M) {
+    std::vector<int> seen(M.T, 0), seen_n(B.l.size(), 0), st = {B.root}; seen_n[B.root] = 1;
+    while (!st.empty()) { int x = st.back(); st.pop_back(); for (int ch : {B.l[x], B.r[x]}) { if (ch < 0) { if (~ch >= M.T) return false; seen[~ch]++; } else { if (ch >= (int)B.l.size() || seen_n[ch]++) return false; st.push_back(ch); } } }
+    for (int i = 0; i < M.T; i++) if (seen[i] != 1) return false;
+    return true;
+}
+
 // ---- 4-wide collapse
 struct Node4 { int ref[4]; Box box[4]; int n; };   // ref >= 0 node4 index, < 0 ~leaf
 struct Tree4 { std::vector<Node4> nodes; int root = 0; };
@@ -207,6 +265,39 @@ static Tree4 collapse_greedy(const BTree& B, const Mesh& M) {     // k_pack4q: o
         map[x] = (int)Q.nodes.size(); Node4 q; q.n = nc; for (int k = 0; k < 4; k++) { q.ref[k] = k < nc ? c[k] : 0; if (k < nc) q.box[k] = child_box(B, M, c[k]); } Q.nodes.push_back(q);
         for (int k = 0; k < nc; k++) if (c[k] >= 0) st.push_back(c[k]); }
     for (auto& q : Q.nodes) for (int k = 0; k < q.n; k++) if (q.ref[k] >= 0) q.ref[k] = map[q.ref[k]];
+    Q.root = map[B.root]; return Q;
+}
+// Treelet fill (a recorded negative): every maximal binary subtree of 3 .. 16 leaves is not collapsed greedily; its leaves, in left-to-right
+// order, are cut into the fewest contiguous runs of <= 4 with the smallest sum of run-box areas (dynamic programme), every run of two or more becomes a full leaf node,
+// and the runs are grouped the same way until at most four entries are left for the treelet's own node. Fewer nodes and far fewer unused entries — and MORE records
+// per ray under every hierarchy of this tool: the boxes of area-minimal contiguous runs overlap more than the ones the binary tree had found.
+static Tree4 collapse_fill(const BTree& B, const Mesh& M, int LT = 16) {
+    std::vector<int> cnt, height, parent, order; subtree_counts(B, cnt, height, parent, order);
+    auto sealed = [&](int x) { return x >= 0 && cnt[x] >= 3 && cnt[x] <= LT; };
+    Tree4 Q; std::vector<int> map(B.l.size(), -1);
+    struct Item { int ref; Box box; bool node4; };      // node4: ref is already an index into Q.nodes
+    std::vector<std::pair<int, int>> fix;               // (node4 index, entry) whose ref is still a binary node id
+    std::function<int(std::vector<Item>)> group = [&](std::vector<Item> it) -> int {
+        while ((int)it.size() > 4) {
+            const int n = (int)it.size(), K = (n + 3) / 4; std::vector<std::vector<double>> c(K + 1, std::vector<double>(n + 1, 1e300)); std::vector<std::vector<int>> from(K + 1, std::vector<int>(n + 1, -1)); c[0][0] = 0;
+            for (int k = 1; k <= K; k++) for (int e = 1; e <= n; e++) for (int len = 1; len <= 4 && len <= e; len++) { if (c[k - 1][e - len] >= 1e300) continue; Box b = empty_box(); for (int i = e - len; i < e; i++) b = merge(b, it[i].box);
+                double v = c[k - 1][e - len] + area(b); if (v < c[k][e]) { c[k][e] = v; from[k][e] = len; } }
+            std::vector<Item> up; std::vector<int> lens; for (int k = K, e = n; k >= 1; k--) { lens.push_back(from[k][e]); e -= from[k][e]; } std::reverse(lens.begin(), lens.end());
+            int p = 0; for (int len : lens) { if (len == 1) { up.push_back(it[p]); p++; continue; }
+                Node4 q; q.n = len; Box b = empty_box(); for (int k = 0; k < len; k++) { q.ref[k] = it[p + k].ref; q.box[k] = it[p + k].box; b = merge(b, it[p + k].box); } for (int k = len; k < 4; k++) q.ref[k] = 0;
+                Q.nodes.push_back(q); up.push_back({(int)Q.nodes.size() - 1, b, true}); p += len; }
+            it.swap(up);
+        }
+        Node4 q; q.n = (int)it.size(); for (int k = 0; k < 4; k++) { q.ref[k] = k < q.n ? it[k].ref : 0; if (k < q.n) q.box[k] = it[k].box; } Q.nodes.push_back(q); return (int)Q.nodes.size() - 1;
+    };
+    std::vector<int> st = {B.root};
+    while (!st.empty()) { int x = st.back(); st.pop_back();
+        if (sealed(x)) { std::vector<Item> it; std::function<void(int)> walk = [&](int r) { if (r < 0) { it.push_back({r, M.tb[~r], false}); return; } walk(B.l[r]); walk(B.r[r]); }; walk(x); map[x] = group(it); continue; }
+        int c[4] = {B.l[x], B.r[x], 0, 0}; int nc = 2;
+        for (int round = 0; round < 2; round++) { int pick = -1; float best = -1; for (int k = 0; k < nc; k++) if (c[k] >= 0 && !sealed(c[k]) && area(B.box[c[k]]) > best) { best = area(B.box[c[k]]); pick = k; } if (pick < 0) break; int o = c[pick]; c[pick] = B.l[o]; c[nc++] = B.r[o]; }
+        map[x] = (int)Q.nodes.size(); Node4 q; q.n = nc; for (int k = 0; k < 4; k++) { q.ref[k] = k < nc ? c[k] : 0; if (k < nc) q.box[k] = child_box(B, M, c[k]); } Q.nodes.push_back(q);
+        for (int k = 0; k < nc; k++) if (c[k] >= 0) { fix.push_back({map[x], k}); st.push_back(c[k]); } }
+    for (auto& [qi, k] : fix) Q.nodes[qi].ref[k] = map[Q.nodes[qi].ref[k]];
     Q.root = map[B.root]; return Q;
 }
 // SAH-optimal collapse (dynamic programme over "how many of the parent's slots does this subtree take", Ylitie et al. 2017 for 4 slots)
@@ -318,6 +409,8 @@ int main(int argc, char** argv) {
     { build_emc(M, 1, 8, 0, 0, 8); std::vector<uint64_t> ek = g_emc_keys; std::vector<int> eo = g_emc_order;
       trees.push_back({"EMC cut 20 bits + SAH8 top", build_hybrid_keys(M, ek, eo, 20, 0, 8)});
       trees.push_back({"EMC cut 24 bits + SAH8 top", build_hybrid_keys(M, ek, eo, 24, 0, 8)});
+      { BTree A = trees.back().second; refit(A, M);      // the adopted hierarchy + the sweep-SAH bottom as shipped (bvh_build.hip k_sb_*)
+        for (int L : {16, 64, 256}) trees.push_back({"EMC cut 24 + SAH8 top + SAH bottom " + std::to_string(L), build_sah_bottom(A, M, L)}); }
       trees.push_back({"EMC cut 24 + SAH8 largest axis", build_hybrid_keys(M, ek, eo, 24, 3, 8)});
       trees.push_back({"EMC cut 24 + SAH16 largest axis", build_hybrid_keys(M, ek, eo, 24, 3, 16)});
       trees.push_back({"EMC cut 28 bits + SAH8 top", build_hybrid_keys(M, ek, eo, 28, 0, 8)}); }
@@ -333,8 +426,10 @@ int main(int argc, char** argv) {
     printf("%-26s %-8s %9s %9s %7s %8s %8s %8s %9s %6s %6s\n", "binary hierarchy", "collapse", "SAH(bin)", "SAH(4w)", "depth4", "rec/ray", "box/ray", "tri/ray", "wave-it", "maxsp", "hit");
     bool first = true;
     for (auto& [name, B] : trees) { refit(B, M); double sb = sah_binary(B, M);
-        for (int c = 0; c < 4; c++) { if (c == 1 && !getenv("TL_DP")) continue; Tree4 Q = c == 1 ? collapse_sah(B, M) : collapse_greedy(B, M); if (c == 2) Q = quantise(Q, 8); if (c == 3) Q = quantise(Q, 12); Counts C = replay(Q, M, rays, first ? &ref_hits : &hits);
+        printf(tree_ok(B, M) ? "   tree ok: %s\n" : "!! a leaf is missing or doubled: %s\n", name.c_str());
+        for (int c = 0; c < 5; c++) { if (c == 1 && !getenv("TL_DP")) continue; if (c == 4 && name.find("SAH8 top") == std::string::npos) continue;      // c == 4: treelet fill (<= 16 leaves), 8-bit boxes
+            Tree4 Q = c == 1 ? collapse_sah(B, M) : (c == 4 ? collapse_fill(B, M) : collapse_greedy(B, M)); if (c == 2 || c == 4) Q = quantise(Q, 8); if (c == 3) Q = quantise(Q, 12); Counts C = replay(Q, M, rays, first ? &ref_hits : &hits);
             if (!first && hits != ref_hits) printf("!! hit bits differ from the first tree\n"); first = false;
-            printf("%-26s %-8s %9.2f %9.2f %7d %8.2f %8.2f %8.2f %9.1f %6d %6.3f\n", name.c_str(), c == 1 ? "sah-dp" : (c == 2 ? "greedy q8" : (c == 3 ? "greedy q12" : "greedy")), sb, sah4(Q, M), depth4(Q), C.rec, C.box, C.tri, C.wave_iter, C.maxsp, C.hit); fflush(stdout); } }
+            printf("%-26s %-10s %9.2f %9.2f %7d %8.2f %8.2f %8.2f %9.1f %6d %6.3f\n", name.c_str(), c == 1 ? "sah-dp" : (c == 2 ? "greedy q8" : (c == 3 ? "greedy q12" : (c == 4 ? "fill16 q8" : "greedy"))), sb, sah4(Q, M), depth4(Q), C.rec, C.box, C.tri, C.wave_iter, C.maxsp, C.hit); fflush(stdout); } }
     return 0;
 }
