@@ -574,6 +574,21 @@ long long mirres_radiance_bwd_workspace_bytes(long long n, int max_blocks);
 int mirres_radiance_points_bwd(const mirres_radiance_t* net, const float* pos, const float* dirs, long long n, float bound, const float* grad_sigma,
                                const float* grad_rgb, float* grad_table, float* grad_w0, float* grad_w1, float* grad_c0, float* grad_c1, float* grad_c2,
                                void* workspace, long long workspace_bytes, int max_blocks, void* stream);
+/* The POSITION adjoint of mirres_radiance_points (radiance_pos.hip), what --enable_offset_nerf_grad lets reach the vertices through self.rgb(xyzs, dirs)
+ * (nerf/renderer.py:1046-1052): pos, dirs f32[n,3], grad_sigma f32[n] (NULL: zeros), grad_rgb f32[n,3] -> grad_pos f32[n,3], OVERWRITTEN.  One thread per point, no
+ * atomics: equal inputs give equal bits.  The forward is recomputed; the cotangent goes back through the two MLPs under mirres_radiance_points_bwd's rules (d_pre,
+ * ReLU, trunc_exp's backward as above; every adjoint sum an fmaf chain from 0 over the layer's outputs ascending) to d_feat[32].  Then the encoder's input
+ * gradient, the reference's dy_dx (gridencoder/src/gridencoder.cu:198-243), in this FIXED order, every operation rounded on its own, no FMA, fp32:
+ *   levels l ascending; f, 1 - f, the cell and the eight entries are the forward's (dense and hashed levels alike; each corner gathered once);
+ *   axes a = 0, 1, 2; lo < hi the two other axes; r[ch] = 0; pairs p = 0 .. 3 ascending: w = scale_l; w = w * (p & 1 ? f[lo] : 1 - f[lo]);
+ *   w = w * (p & 2 ? f[hi] : 1 - f[hi]); r[ch] = r[ch] + w * (table[right][ch] - table[left][ch]) for ch = 0, 1 (left / right: the pair's corners at a = 0 / 1);
+ *   grad_u[a] = grad_u[a] + d_feat[2 l] * r[0]; grad_u[a] = grad_u[a] + d_feat[2 l + 1] * r[1];
+ *   after the last level grad_pos[a] = grad_u[a] / (2 * bound) (gridencoder/grid.py:156), an IEEE division.
+ * A point out of bounds (or not finite) has constant features: exactly 0, 0, 0.  On a cell face the derivative is the one-sided one of the cell the forward picks.
+ * Directions get no gradient.  Refused before a device is touched: a NULL net or weight or a bad layout, n < 0 or n > 2^38, NULL pos / dirs / grad_rgb / grad_pos
+ * with n > 0, a bound that is not positive and finite.  n == 0 launches nothing.                                                                                */
+int mirres_radiance_points_bwd_pos(const mirres_radiance_t* net, const float* pos, const float* dirs, long long n, float bound, const float* grad_sigma,
+                                   const float* grad_rgb, float* grad_pos, void* stream);
 /* GridEncoder.grad_total_variation (gridencoder/grid.py:170-192) over kernel_grad_tv (gridencoder/src/gridencoder.cu:505-609), grid_tv.hip: the in-place
  * total-variation regulariser of the hash grid.  pos f32[n,3] in world coordinates, as for mirres_density_points; grad_table f32[entries,2] is ACCUMULATED into;
  * net->w0 and net->w1 are not read and may be NULL.  Per point and level: c = the encoder's corner 0 (floorf(u * scale + 0.5f) per axis), e = its entry; for

@@ -167,6 +167,7 @@ SIGNATURES = {
     "mirres_sh_encode": (C.c_int, [vp, C.c_longlong, vp, vp]),
     "mirres_radiance_bwd_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
     "mirres_radiance_points_bwd": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_int, vp]),
+    "mirres_radiance_points_bwd_pos": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp]),
     "mirres_grid_tv_workspace_bytes": (C.c_longlong, [C.POINTER(DensityNet)]),
     "mirres_grid_tv_grad": (C.c_int, [C.POINTER(DensityNet), vp, C.c_longlong, f32, f32, vp, vp, C.c_longlong, vp]),
     "mirres_rm_near_far": (C.c_int, [vp, vp, vp, C.c_longlong, f32, vp, vp, vp]),

@@ -212,6 +212,13 @@ def read_checkpoint(path, map_location="cpu"):
                 material_config=top.get("material_config"), train_state=_train_state_of(top))
 
 
+def stage0_model_of(path, map_location="cpu"):
+    """The `model` state dict of a checkpoint file (or the file's dict when it is a bare state dict): what stage0.RadianceField.from_checkpoint reads when the file
+    holds STAGE0_WEIGHT_KEYS — a stage-0 checkpoint, or a stage-1 checkpoint written with save_checkpoint(field=...)."""
+    ck = torch.load(path, map_location=map_location, weights_only=False)
+    return ck["model"] if isinstance(ck, dict) and "model" in ck else ck
+
+
 def apply_checkpoint(ck, mlp_mat=None, n_vertices=None, device="cuda"):
     """Copy a read_checkpoint() result into an MLPTexture3D and return (vertices_offsets, light_base) on `device` (None where the file had none).
     `light_base` replaces the model's map as load_checkpoint does (:1962-1964); the caller clamps / trains it as before."""
@@ -248,13 +255,16 @@ TRAIN_STATE_KEYS = ("optimizer", "lr_scheduler", "optimizer_mat", "optimizer_lig
 _LEGACY_TRAIN_STATE_KEYS = {"lr_scheduler_mat": "scheduler_mat", "lr_scheduler_light": "scheduler_light"}
 
 
-def save_checkpoint(path, mlp_mat, vertices_offsets, light_base, epoch=0, global_step=0, stage=1, material_config=None, train_state=None):
+def save_checkpoint(path, mlp_mat, vertices_offsets, light_base, epoch=0, global_step=0, stage=1, material_config=None, train_state=None, field=None):
     """The same file layout, written from this engine's objects (Trainer.save_checkpoint, :1843-1854, 1912-1920), plus one extra
     top-level key the reference's loader ignores: `material_config` (the AABB / output-range constants the field was trained with, read back from the
     module when not given) so that an evaluation of this file cannot silently decode it with another run's `--bound` / `--me_max`.
     `train_state` (a `full=True` checkpoint, :1856-1866): state dicts under the reference's keys `optimizer`, `lr_scheduler`, `optimizer_mat`,
     `optimizer_light`, `scheduler_mat`, `scheduler_light` (LambdaLR state dicts, :1863-1867) so that a resumed run — here or through the reference's own
-    `load_checkpoint` (:2003-2022) — continues the Adam moments and the learning-rate schedules where they were."""
+    `load_checkpoint` (:2003-2022) — continues the Adam moments and the learning-rate schedules where they were.
+    `field` (a stage0.RadianceField, the NeRF colour branch stage 1 keeps training): `model` then also holds STAGE0_WEIGHT_KEYS and encoder.offsets, as
+    save_stage0_checkpoint writes them — the reference's stage-1 state dict carries the whole NeRFNetwork — and stage0.RadianceField.from_checkpoint reads them
+    back from this file."""
     if material_config is None:
         lo, hi = (t.detach().cpu().tolist() for t in mlp_mat.AABB)
         mn, mx = (t.detach().cpu().tolist() for t in mlp_mat.min_max)
@@ -264,6 +274,10 @@ def save_checkpoint(path, mlp_mat, vertices_offsets, light_base, epoch=0, global
     model = {"vertices_offsets": vertices_offsets.detach().cpu(), _MAT + "encoder.params": mlp_mat.encoder.params.detach().cpu()}
     for i in (0, 2, 4):
         model[_MAT + "net.net.%d.weight" % i] = mlp_mat.net.net[i].weight.detach().cpu()
+    if field is not None:
+        for k, name in zip(STAGE0_WEIGHT_KEYS, field.PARAMETER_NAMES):
+            model[k] = getattr(field, name).detach().to("cpu").clone()
+        model["encoder.offsets"] = torch.tensor([int(field.net.offsets[k]) for k in range(field.net.num_levels + 1)], dtype=torch.int32)
     state = {"epoch": epoch, "global_step": global_step, "stats": {}, "stage": stage, "light_base": light_base.detach().cpu(), "model": model,
              "material_config": dict(material_config)}
     for k, v in (train_state or {}).items():

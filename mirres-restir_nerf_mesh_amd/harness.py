@@ -235,15 +235,22 @@ def albedo_view(worker, mlp_mat, pose, intrinsics, H, W, ssaa=1, gbuffer_consts=
 
 def render_stage1_outputs(worker, vertices, voffsets, triangles, mlp_mat, env_map, mods, H, W, spp, ssaa=1, azimuth_deg=30.0, elevation_deg=30.0,
                           jitter_std=0.01, bg_color=1.0, gb_depth=None, with_normal_ao=False, de=2, c=2.0, n=0.1, p=0.001, pose=None, intrinsics=None,
-                          topology=None, pos_gradient_boost=1.0, exposure=None):
+                          topology=None, pos_gradient_boost=1.0, exposure=None, field=None, offset_nerf_grad=False):
     """`render_stage1` for `--stage 1 --use_brdf --use_restir` training (nerf/renderer.py:960-1302) as far as the material / light / geometry
     branch goes: moved mesh -> BVH update -> G-buffer front half (build_gbuffer_stage1) -> jittered material taps (:1016-1022) ->
     run_restir_di_with_pt (:1112-1123) -> clamp, tone curve (:1125-1129, 1162-1164) -> dr.antialias of alpha and of every output image (:1184-1200;
     the indirect images detached, as there) -> alpha (:1208-1240) -> SSAA down-scale to H x W when ssaa > 1 (:1265-1297) -> background (:1301).  Returns the entries of the reference's `outputs` dict that losses.stage1_loss
-    reads, except `image` (the NeRF colour branch belongs to stage 0).  With a dataset camera (`pose`, `intrinsics`) the antialias step runs and the
+    reads; `image` (the NeRF colour branch) and `weights_sum` only with `field`, see below.  With a dataset camera (`pose`, `intrinsics`) the antialias step runs and the
     image loss reaches the vertex positions through visibility; with the synthetic orbit camera (no projection matrix) it is skipped.  `topology` =
     raster.antialias_topology(triangles) (built per call when None).  `gb_depth` ([N, 2]: z, |dz|; :1070-1081) selects the --use_bi_de bilateral
-    finish, None the a-trous one.  `exposure` (a float: --use_hdr --exposure E) multiplies the radiance by 2**E before the clamp (:1125-1127).  (normal_grad, which needs the perturbed-normal texture the --use_brdf path never enables, is zero)."""
+    finish, None the a-trous one.  `exposure` (a float: --use_hdr --exposure E) multiplies the radiance by 2**E before the clamp (:1125-1127).  (normal_grad, which needs the perturbed-normal texture the --use_brdf path never enables, is zero).
+    `field` (a stage0.RadianceField; None: every output is what it was without the argument) adds the NeRF colour branch (:935-946, 1028-1052, 1160, 1184-1185,
+    1208, 1266-1269, 1301, 1327-1329): the stage-0 network's colour at the rasterised surface points, rgbs[idx] = field.rgb_train(xyzs[idx], dirs[idx]) for
+    idx = nonzero(occ), with the directions the reference shades with (view_dirs of the H x W rays for a dataset camera, the normalised orbit rays otherwise);
+    `image` = alpha * aa(rgbs), down-scaled and composed over `bg_color` (a scalar or [H W, 3]) like image_brdf, differentiable in field.parameters() and, through
+    dr.antialias, in the vertices; `weights_sum` [H W] is the down-scaled alpha (1 - T).  `offset_nerf_grad` (--enable_offset_nerf_grad): xyzs reaches the field
+    un-detached, so the colour's position gradient (csrc/radiance_pos.hip) reaches the vertices as well.  --contract is not built; `shading` and `ind_code` are
+    ignored, as NeRFNetwork.rgb ignores them."""
     from . import renderer_restir as RR
     from . import raster
     moved = vertices + voffsets
@@ -285,11 +292,45 @@ def render_stage1_outputs(worker, vertices, voffsets, triangles, mlp_mat, env_ma
     res = dict(image_brdf=alpha * aa(brdf_rgbs), diffuse_light=alpha * aa(out[1]), specular_light=alpha * aa(out[2]),                      # :1186, 1209-1240
                img_brdf_indirect=(alpha * aa(out[3].detach())).detach(), kd_grad=kd_grad * g["occ"], ks_grad=ks_grad * g["occ"],
                normal_grad=torch.zeros((N, 1), device=dev), occ=alpha, **extra)
+    if field is not None:
+        if pose is not None:
+            dirs = view_dirs(get_rays(pose.to(dev), intrinsics, H, W)[1], H, W, ssaa)                               # :935-946
+        else:
+            dirs = g["ray_dir"] / torch.sqrt(torch.clamp(torch.sum(g["ray_dir"] * g["ray_dir"], -1, keepdim=True), min=1e-20))
+        idx = torch.nonzero(g["occ"].view(-1) > 0).view(-1)                                                          # mask_flatten (:1028-1029)
+        rgbs = torch.zeros((N, 3), dtype=torch.float32, device=dev)                                                  # :1038
+        if idx.numel():
+            pts = xyzs[idx] if offset_nerf_grad else xyzs[idx].detach()                                             # :1049
+            rgbs = rgbs.index_put((idx,), field.rgb_train(pts, dirs[idx], pos_grad=offset_nerf_grad))               # :1052
+        res["image"] = alpha * aa(rgbs)                                                                              # :1185, 1208
     if ssaa > 1:      # every image goes through the SSAA down-scale before the losses see it (:1265-1297); T = 1 - alpha is scaled like the images
         res = {k: scale_img_hwc(v.view(fy, fx, v.shape[-1]), (H, W)).reshape(H * W, v.shape[-1]) for k, v in res.items()}
         fx, fy = W, H
     res["image_brdf"] = res["image_brdf"] + (1 - res["occ"]) * bg_color                                            # :1301
+    if field is not None:
+        res["image"] = res["image"] + (1 - res["occ"]) * bg_color                                                    # :1301
+        res["weights_sum"] = res["occ"].reshape(-1)                                                                  # 1 - T (:1241, 1269, 1329)
     return dict(res, fx=fx, fy=fy)                                                                                 # :1350-1352
+
+
+def nerf_view(worker, field, pose, intrinsics, H, W, ssaa=1, bg_color=1.0):
+    """The `image` of render_stage1_outputs(field=...) for evaluation, without autograd: test_view's G-buffer for the dataset camera
+    (build_gbuffer_from_pose: primary hits by ray cast, the reference's shading directions), field.rgb at the hit points, alpha, SSAA down-scale, background
+    (`bg_color`: a scalar or [H W, 3]).  Like test_view it has no raster record and so no dr.antialias step.  Returns [H, W, 3] in [0, 1]."""
+    with torch.no_grad():
+        g = build_gbuffer_from_pose(worker, pose, intrinsics, H, W, ssaa)
+        h, w = g["fy"], g["fx"]
+        idx = torch.nonzero(g["occ"].view(-1) > 0.5).view(-1)
+        rgbs = torch.zeros((h * w, 3), dtype=torch.float32, device=g["pos"].device)
+        if idx.numel():
+            rgbs[idx] = field.rgb(g["pos"][idx], g["ray_dir"][idx])
+        alpha = (g["occ"] > 0.5).float()
+        img = (alpha * rgbs.clamp(0, 1)).view(h, w, 3)
+        alpha = alpha.view(h, w, 1)
+        if ssaa > 1:
+            img = scale_img_hwc(img, (H, W)); alpha = scale_img_hwc(alpha, (H, W))
+        bg = bg_color.view(H, W, 3) if torch.is_tensor(bg_color) and bg_color.dim() > 0 else bg_color
+        return img + (1 - alpha) * bg
 
 
 def srgb_to_linear(x):

@@ -117,22 +117,27 @@ def offsets_loss(voffsets, n_inner=None):
     return (voffsets[:n_inner].abs() ** 2).sum(-1).mean() + 0.1 * (voffsets[n_inner:].abs() ** 2).sum(-1).mean()
 
 
-def stage1_loss(outputs, gt_rgb, gt_rgb_linear, opt, vertices=None, voffsets=None, triangles=None, n_inner=None, criterion_lpips=None, frame_hw=None):
+def stage1_loss(outputs, gt_rgb, gt_rgb_linear, opt, vertices=None, voffsets=None, triangles=None, n_inner=None, criterion_lpips=None, frame_hw=None, gt_mask=None):
     """The stage-1 scalar of Trainer.train_step (nerf/utils.py:1003-1017, 1043-1126) from render_stage1's outputs.
 
     `opt` carries the reference's --lambda_* fields (main.py:81-113) and use_brdf; missing fields take main.py's defaults.  The perceptual term
     (--lambda_lpips > 0, default 0; utils.py:1079-1082) needs `criterion_lpips` (meters.LPIPS with the user's pretrained weights; the reference calls it
-    on the [0, 1] images without `normalize`, kept) and the frame's (H, W); mask and refine-error terms need the reference's data loader and are outside
-    this path."""
+    on the [0, 1] images without `normalize`, kept) and the frame's (H, W).  `gt_mask` ([H W] or [H W, 1], the image's alpha): the mask term
+    lambda_mask (0.1) * (outputs["weights_sum"] - gt_mask)^2 joins the per-pixel loss before its mean (utils.py:1014-1016, 1021), when lambda_mask > 0;
+    None: the scalar is what it was without the argument.  The refine-error terms need the reference's data loader and are outside this path."""
     g = lambda k, d: getattr(opt, k, d)
     use_brdf = g("use_brdf", True)
     loss = 0.0
-    if "image" in outputs:     # the NeRF colour branch (stage 0's product); harness.render_stage1_outputs does not produce it
+    if "image" in outputs:     # the NeRF colour branch (stage 0's product): harness.render_stage1_outputs(field=...)
         loss = g("lambda_rgb", 1.0) * ((outputs["image"] - gt_rgb) ** 2).mean(-1)               # criterion = MSELoss(reduction='none'), main.py:231
     if use_brdf:
         loss = loss + g("lambda_rgb_brdf", 0.02) * (outputs["image_brdf"] - gt_rgb).abs().mean(-1)   # criterion_brdf = L1Loss, utils.py:788
     if not torch.is_tensor(loss):
         raise ValueError("stage1_loss: neither `image` nor (use_brdf and `image_brdf`) in outputs")
+    if gt_mask is not None and g("lambda_mask", 0.1) > 0:
+        if "weights_sum" not in outputs:
+            raise ValueError("stage1_loss: gt_mask needs outputs['weights_sum'] (harness.render_stage1_outputs(field=...))")
+        loss = loss + g("lambda_mask", 0.1) * (outputs["weights_sum"].reshape(-1) - gt_mask.reshape(-1)) ** 2
     loss = loss.mean()
     if use_brdf:
         loss = loss + shading_loss(outputs["diffuse_light"], outputs["specular_light"], gt_rgb_linear - outputs["img_brdf_indirect"],

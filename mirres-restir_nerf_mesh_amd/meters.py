@@ -239,9 +239,10 @@ def write_png(path, img_u8):
         fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
-def write_test_frame(save_path, name, index, image_brdf, depth=None):
+def write_test_frame(save_path, name, index, image_brdf, depth=None, image=None):
     """The per-frame files Trainer.test writes for the BRDF branch with write_video off (:1361-1366): `<name>_<i>_rgb_brdf.png` and, when a depth
-    map is given, `<name>_<i>_depth.png` (min-max normalised with the 1e-6 guard)."""
+    map is given, `<name>_<i>_depth.png` (min-max normalised with the 1e-6 guard); with `image` (the NeRF colour branch's frame, harness.nerf_view) also
+    `<name>_<i>_rgb.png`, Trainer.test's name for it, last in the returned list."""
     os.makedirs(save_path, exist_ok=True)
     out = [os.path.join(save_path, "%s_%04d_rgb_brdf.png" % (name, index))]
     write_png(out[0], to_uint8(image_brdf))
@@ -250,6 +251,9 @@ def write_test_frame(save_path, name, index, image_brdf, depth=None):
         d = (d - d.min()) / (d.max() - d.min() + 1e-6)
         out.append(os.path.join(save_path, "%s_%04d_depth.png" % (name, index)))
         write_png(out[1], (d * 255).astype(np.uint8))
+    if image is not None:
+        out.append(os.path.join(save_path, "%s_%04d_rgb.png" % (name, index)))
+        write_png(out[-1], to_uint8(image))
     return out
 
 

@@ -834,6 +834,33 @@ class RadianceField(DensityField):
         mirres_radiance_points launch; nothing but x and d is kept, the backward recomputes (backward_points)."""
         return _RadianceTrain.apply(self, self._n3(x, "positions").detach(), self._n3(d, "directions").detach(), *[getattr(self, k) for k in self.PARAMETER_NAMES])
 
+    def backward_pos(self, x, d, grad_sigma, grad_rgb):
+        """The position adjoint of forward (csrc/radiance_pos.hip), one mirres_radiance_points_bwd_pos call: x, d [n, 3], grad_sigma [n] or None (zeros),
+        grad_rgb [n, 3] -> d / dx f32 [n, 3]; exactly 0 for a point out of bounds.  No atomics: equal inputs give equal bits.  Directions get no gradient."""
+        x, d = self._n3(x, "positions"), self._n3(d, "directions")
+        n = int(x.shape[0])
+        grad_rgb = torch.as_tensor(grad_rgb).to(x.device, torch.float32).contiguous()
+        if d.shape[0] != n or tuple(grad_rgb.shape) != (n, 3):
+            raise ValueError("RadianceField: %d positions, %d directions and grad_rgb of %s" % (n, d.shape[0], tuple(grad_rgb.shape)))
+        if grad_sigma is not None:
+            grad_sigma = torch.as_tensor(grad_sigma).to(x.device, torch.float32).contiguous()
+            if tuple(grad_sigma.shape) != (n,):
+                raise ValueError("RadianceField: grad_sigma of %s for %d points" % (tuple(grad_sigma.shape), n))
+        out = torch.empty((n, 3), dtype=torch.float32, device=x.device)
+        p = (lambda t: ptr(t) if (t is not None and n) else None)
+        check(lib().mirres_radiance_points_bwd_pos(C.byref(self.rnet), p(x), p(d), n, self.bound, p(grad_sigma), p(grad_rgb), p(out), stream_ptr()),
+              "mirres_radiance_points_bwd_pos")
+        return out
+
+    def rgb_train(self, x, d, pos_grad=False):
+        """rgb with gradients, what stage 1 asks of self.rgb(xyzs, dirs) (nerf/renderer.py:1046-1052): rgb()'s bits from one mirres_radiance_points launch without
+        sigma, differentiable in parameters() (backward_points with no grad_sigma) and, with pos_grad (--enable_offset_nerf_grad) and x.requires_grad, in x
+        (backward_pos); otherwise x gets no gradient.  d never does."""
+        x = self._n3(x, "positions")
+        if not pos_grad:
+            x = x.detach()
+        return _RadianceRgbTrain.apply(self, x, self._n3(d, "directions").detach(), *[getattr(self, k) for k in self.PARAMETER_NAMES])
+
 
 class _RadianceTrain(torch.autograd.Function):
     @staticmethod
@@ -850,6 +877,26 @@ class _RadianceTrain(torch.autograd.Function):
             grad_rgb = torch.zeros((x.shape[0], 3), dtype=torch.float32, device=x.device)
         grads = ctx.field.backward_points(x, d, grad_sigma, grad_rgb)
         return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+class _RadianceRgbTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, x, d, *params):
+        rgb = field._query(x, d, want_sigma=False)[1]
+        ctx.field = field
+        ctx.save_for_backward(x, d)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, grad_rgb):
+        x, d = ctx.saved_tensors
+        grad_rgb = grad_rgb.contiguous()
+        gp = (None,) * 6
+        if any(ctx.needs_input_grad[3:]):
+            grads = ctx.field.backward_points(x, d, None, grad_rgb)
+            gp = tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+        gx = ctx.field.backward_pos(x, d, None, grad_rgb) if ctx.needs_input_grad[1] else None
+        return (None, gx, None) + gp
 
 
 def _safe_normalize(x, eps=1e-20):

@@ -93,6 +93,9 @@ def build_parser():
     p.add_argument("--shard", choices=("views", "strips", "spp"), default="views", help="how N > 1 ranks (torch.distributed.run) divide the work")
     p.add_argument("--lpips_vgg", default=None, help="torchvision vgg16 state dict (or a state dict of lpips.LPIPS): adds the reference's LPIPS (vgg) meter; no weights ship with the image")
     p.add_argument("--lpips_lin", default=None, help="the lpips package's weights/v0.1/vgg.pth (the five linear heads)")
+    p.add_argument("--nerf_image", action="store_true", help="also write <name>_<i>_rgb.png, the NeRF colour branch's frame (Trainer.test's `image`: the stage-0 network's colour "
+                   "at the surface), and print its PSNR; the network comes from --ckpt when it holds it, else from --stage0_ckpt")
+    p.add_argument("--stage0_ckpt", default=None, help="--nerf_image: a stage-0 checkpoint, or `random` (RadianceField.init_random)")
     p.add_argument("--export_mesh", action="store_true", help="after the views, export the stage-1 textured mesh to <workspace>/mesh_stage1 (main.py:256-258; off by default)")
     p.add_argument("--texture_size", type=int, default=4096, help="main.py --texture_size: texture side of the first cascade of --export_mesh (baked at --ssaa)")
     p.add_argument("--textured_mesh", default=None, help="render the views from this exported stage-1 asset (mesh_{cas}.obj, feat0/feat1_{cas}.png|.jpg); with "
@@ -162,6 +165,19 @@ def main():
     intr = (focal, focal, Ww * 0.5, Hh * 0.5)
     frames = tf["frames"][: a.limit] if a.limit > 0 else tf["frames"]
     pm, sm = meters.PSNRMeter(), meters.SSIMMeter()
+    nerf = None
+    if a.nerf_image:
+        from mirres_restir_nerf_mesh_amd.stage0 import RadianceField
+        ck_model = CK.stage0_model_of(a.ckpt)
+        if all(k in ck_model for k in CK.STAGE0_WEIGHT_KEYS):
+            nerf = RadianceField.from_checkpoint(ck_model, bound=cfg["bound"])
+        elif a.stage0_ckpt == "random" or (a.synthetic and not a.stage0_ckpt):      # the synthetic workspace has no stage 0: a freshly initialised network
+            nerf = RadianceField.init_random(bound=cfg["bound"])
+        elif a.stage0_ckpt:
+            nerf = RadianceField.from_checkpoint(torch.load(a.stage0_ckpt, map_location="cpu", weights_only=False), bound=cfg["bound"])
+        else:
+            p.error("--nerf_image: %s holds no stage-0 network; give --stage0_ckpt" % a.ckpt)
+    pm_nerf = meters.PSNRMeter()
     lm = meters.LPIPSMeter(vgg=a.lpips_vgg, lin=a.lpips_lin) if a.lpips_vgg else None        # main.py:250: [PSNRMeter(), SSIMMeter(), LPIPSMeter(device=device)]
     name = os.path.splitext(os.path.basename(a.ckpt))[0]
     if world == 1 or a.shard == "views":
@@ -189,7 +205,8 @@ def main():
             field_imgs[i] = img
         if world > 1 and a.shard != "views" and rank != 0:
             continue                                                       # every rank holds the whole frame; rank 0 writes and scores it
-        files = meters.write_test_frame(out_dir, name, i, img)
+        img_nerf = harness.nerf_view(W, nerf, torch.from_numpy(pose), intr, Hh, Ww, a.ssaa) if nerf is not None else None
+        files = meters.write_test_frame(out_dir, name, i, img, image=img_nerf)
         if maps is not None:                                               # kd / ks / normal / env_map / diffuse + specular light as EXR (utils.py:1372-1377)
             files += meters.write_test_maps(out_dir, name, i, maps)
         gt_path = os.path.join(base, fr["file_path"] + ".png")
@@ -203,19 +220,24 @@ def main():
             note = "  PSNR %.3f  SSIM %.4f" % (pm.update(img, gt_t), sm.update(img, gt_t))
             if lm is not None:
                 note += "  LPIPS %.4f" % lm.update(img, gt_t)
+            if img_nerf is not None:
+                note += "  PSNR(rgb) %.3f" % pm_nerf.update(img_nerf, gt_t)
         print("[%d/%d] %s%s" % (i + 1, len(frames), os.path.basename(files[0]), note), flush=True)
     n = len(frames)
     if world > 1:      # wall time of the job = the slowest rank; metric sums over the ranks that scored frames
-        red = torch.tensor([t_render, pm.V, float(pm.N), sm.V, float(sm.N), lm.V if lm else 0.0, float(lm.N) if lm else 0.0], dtype=torch.float64, device="cuda")
+        red = torch.tensor([t_render, pm.V, float(pm.N), sm.V, float(sm.N), lm.V if lm else 0.0, float(lm.N) if lm else 0.0, pm_nerf.V, float(pm_nerf.N)], dtype=torch.float64, device="cuda")
         tmax = red[:1].clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX); dist.all_reduce(red, op=dist.ReduceOp.SUM)
         t_render = float(tmax.item()); pm.V, pm.N, sm.V, sm.N = float(red[1]), int(red[2]), float(red[3]), int(red[4])
         if lm:
             lm.V, lm.N = float(red[5]), int(red[6])
+        pm_nerf.V, pm_nerf.N = float(red[7]), int(red[8])
     if rank == 0:
         print("rendered %d views %dx%d ssaa %d spp %d on %d GPU(s)%s: %.1f ms/view (%.1f Msamples/s)" % (
             n, Ww, Hh, a.ssaa, a.spp, world, (" [%s]" % a.shard) if world > 1 else "", 1e3 * t_render / max(n, 1), n * Ww * Hh * a.ssaa ** 2 * a.spp / max(t_render, 1e-9) / 1e6))
         if pm.N:
             print(pm.report(), sm.report(), lm.report() if lm and lm.N else "")
+        if pm_nerf.N:
+            print("NeRF colour branch (_rgb.png): " + pm_nerf.report())
         if a.export_mesh:          # trainer.export_stage1(resolution=opt.texture_size) after the test views (main.py:256-258)
             from mirres_restir_nerf_mesh_amd import export as EX
             EX.export_stage1(os.path.join(a.workspace, "mesh_stage1"), verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa)

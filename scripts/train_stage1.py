@@ -7,16 +7,19 @@ the reference's learning-rate schedules (main.py:285, nerf/utils.py:820-829), ch
     python scripts/train_stage1.py --workspace <ws> --transforms <data>/transforms_train.json [--iters 7500 --spp 32 --ssaa 1 --downscale 1
         --bound 2 --roughness_min 0.08 --me_max 0 --scale 1 --offset 0 0 0 --ckpt <file.pth> --save_interval 500]
     python scripts/train_stage1.py --synthetic [--iters 60 --spp 8 --H 96 --W 96]      # fits a hidden synthetic scene; prints PSNR before / after
+    python scripts/train_stage1.py ... --stage0_ckpt <ws>/checkpoints/ngp.pth [--lr 1e-2 --lambda_rgb 1 --lambda_mask 0.1 --enable_offset_nerf_grad
+        --background white|random --freeze nerf]      # + the NeRF colour branch: `image` = the stage-0 network's colour at the surface (nerf/renderer.py:1046-1052),
+        # its six tensors trained by the geometry optimiser at --lr (NeRFNetwork.get_params, nerf/network.py:278-291); `--stage0_ckpt random`: init_random(seed)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_stage1.py ...   # data parallel: one view per rank
 
-Not here (the reference's Trainer / data loader / NeRF stage 0 are out of scope): the NeRF colour branch (`image`), mask / LPIPS / refine-error terms,
-tensorboard, EMA, mesh export.  `np.random.seed` / `torch.manual_seed` (--seed) fix the view order, the jitter of the smoothness taps and the frame seeds."""
+Not here (the reference's Trainer / data loader are out of scope): LPIPS / refine-error terms, --contract, --sdf, tensorboard, EMA, mesh export.  `np.random.seed` / `torch.manual_seed` (--seed) fix the view order, the jitter of the smoothness taps and the frame seeds."""
 import argparse, json, os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
 import mirres_restir_nerf_mesh_amd as M
 from mirres_restir_nerf_mesh_amd import renderer_restir as RR, harness, losses, raster, checkpoint as CK, dist as MD
 from mirres_restir_nerf_mesh_amd.render_helper import MLPTexture3D
+from mirres_restir_nerf_mesh_amd.stage0 import RadianceField
 
 
 srgb_to_linear = harness.srgb_to_linear      # nerf/utils.py:57-58 (pinned to the reference's function in tests/test_losses.py)
@@ -71,7 +74,13 @@ def main():
     p.add_argument("--scale", type=float, default=1.0); p.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0])
     p.add_argument("--save_interval", type=int, default=500); p.add_argument("--seed", type=int, default=0); p.add_argument("--H", type=int, default=96); p.add_argument("--W", type=int, default=96)
     p.add_argument("--mesh_error", type=float, default=0.0, help="--synthetic: relative error of the starting mesh against the one the images show")
-    p.add_argument("--freeze", nargs="*", default=[], choices=["geometry", "material", "light"], help="parameter groups left untouched (their learning rate set to 0)")
+    p.add_argument("--freeze", nargs="*", default=[], choices=["geometry", "material", "light", "nerf"], help="parameter groups left untouched (their learning rate set to 0)")
+    p.add_argument("--stage0_ckpt", default=None, help="the stage-0 checkpoint of the NeRF colour branch (`image`, nerf/renderer.py:1046-1052), or `random` for RadianceField.init_random(seed); "
+                   "without it (and without a --ckpt that holds the network) the branch is off")
+    p.add_argument("--lr", type=float, default=1e-2, help="main.py --lr: the NeRF network's learning rate in the geometry optimiser")
+    p.add_argument("--lambda_rgb", type=float, default=1.0); p.add_argument("--lambda_mask", type=float, default=0.1)
+    p.add_argument("--enable_offset_nerf_grad", action="store_true", help="the colour's position gradient reaches the vertices (csrc/radiance_pos.hip); \"lead to more sharp texture\"")
+    p.add_argument("--background", default="white", choices=["white", "random"], help="random: per-pixel torch.rand(N, 3) under images with alpha (nerf/utils.py:949-956)")
     p.add_argument("--pos_gradient_boost", type=float, default=1.0); p.add_argument("--lambda_extra_kd", type=float, default=0.0); p.add_argument("--quiet", action="store_true")
     p.add_argument("--use_hdr", action="store_true", help="main.py --use_hdr: radiance x 2**exposure before the clamp (nerf/renderer.py:1125-1127)"); p.add_argument("--exposure", type=float, default=0.0)
     a = p.parse_args()
@@ -110,6 +119,15 @@ def main():
             if vo is not None: voff.copy_(vo)
             if lb is not None: env.copy_(lb)
         step0 = int(ck.get("global_step") or 0)
+    # ---- the NeRF colour branch: the stage-0 network, from --stage0_ckpt, or from a stage-1 checkpoint that holds it (checkpoint.save_checkpoint(field=...))
+    field = None
+    ck_model = CK.stage0_model_of(a.ckpt) if a.ckpt else {}
+    if all(k in ck_model for k in CK.STAGE0_WEIGHT_KEYS):
+        field = RadianceField.from_checkpoint(ck_model, bound=cfg["bound"])
+    elif a.stage0_ckpt == "random":
+        field = RadianceField.init_random(bound=cfg["bound"], seed=a.seed)
+    elif a.stage0_ckpt:
+        field = RadianceField.from_checkpoint(torch.load(a.stage0_ckpt, map_location="cpu", weights_only=False), bound=cfg["bound"])
     Wk = RR.restirbvhWorker((verts + voff.detach()).contiguous(), tris); Wk.update_mesh(Wk.vrt, Wk.v_ind)
     topo = raster.antialias_topology(tris)
     # ---- data
@@ -124,15 +142,18 @@ def main():
         if a.downscale > 1: im = im.resize((Wd, H), Image.BILINEAR)
         x = torch.from_numpy(np.asarray(im).astype(np.float32) / 255.0).cuda().view(H * Wd, -1)
         lin = srgb_to_linear(x[:, :3])                                               # images_linear (utils.py:927)
-        if x.shape[1] == 4:                                                          # white background (utils.py:948-955)
-            return x[:, :3] * x[:, 3:] + (1 - x[:, 3:]), lin * x[:, 3:]
-        return x[:, :3], lin
+        if x.shape[1] == 4:                                                          # white background (utils.py:948-955); the alpha is gt_mask, the last entry the colour before compositing
+            return x[:, :3] * x[:, 3:] + (1 - x[:, 3:]), lin * x[:, 3:], x[:, 3:].contiguous(), x[:, :3]
+        return x[:, :3], lin, None, None
     data = [(torch.from_numpy(np.array(fr["transform_matrix"], np.float32)), load(fr)) for fr in frames]
     for pose, _ in data:
         pose[:3, 3] = pose[:3, 3] * a.scale + torch.tensor(a.offset)
     mods = RR.load_m_for_restir(Wd * a.ssaa, H * a.ssaa)
     # ---- optimisers and schedules (main.py:267-285, utils.py:820-829)
-    o_geo = torch.optim.Adam([{"params": [voff], "lr": 0.0 if "geometry" in a.freeze else a.lr_vert, "weight_decay": 0}], eps=1e-15)
+    geo_groups = [{"params": [voff], "lr": 0.0 if "geometry" in a.freeze else a.lr_vert, "weight_decay": 0}]
+    if field is not None:      # the reference's single `optimizer` holds the NeRF network at --lr beside the offsets (network.py:278-291, main.py:267), under the same schedule
+        geo_groups.append({"params": field.parameters(), "lr": 0.0 if "nerf" in a.freeze else a.lr})
+    o_geo = torch.optim.Adam(geo_groups, eps=1e-15)
     o_mat = torch.optim.Adam([{"params": mlp.parameters(), "lr": 0.0 if "material" in a.freeze else a.learning_rate_mat}])
     o_lgt = torch.optim.Adam([{"params": [env], "lr": 0.0 if "light" in a.freeze else a.learning_rate_lgt}])
     s_geo = torch.optim.lr_scheduler.LambdaLR(o_geo, lambda it: 0.01 + 0.99 * (it / 500) if it <= 500 else 0.1 ** ((it - 500) / max(1, a.iters - 500)))
@@ -145,8 +166,11 @@ def main():
     if ck is not None:
         ts = ck.get("train_state") or {}
         for k_, o_ in optims.items():
-            if k_ in ts:
+            if k_ in ts and len(ts[k_]["param_groups"]) == len(o_.param_groups):
                 o_.load_state_dict(ts[k_])
+            elif k_ in ts and rank == 0:      # e.g. a checkpoint written without the NeRF branch, resumed with --stage0_ckpt: one geometry group there, two here
+                print("[resume] %s: `%s` holds %d parameter group(s), this run has %d: its Adam moments restart at step %d" % (
+                    a.ckpt, k_, len(ts[k_]["param_groups"]), len(o_.param_groups), step0), flush=True)
         for k_, s_ in scheds.items():
             if k_ in ts:
                 s_.load_state_dict(ts[k_])
@@ -157,25 +181,41 @@ def main():
                 s_._last_lr = [g_["lr"] for g_ in s_.optimizer.param_groups]
         if rank == 0 and not all(k_ in ts for k_ in optims):
             print("[resume] %s holds no optimiser state: Adam moments restart at step %d (learning-rate schedules continue)" % (a.ckpt, step0), flush=True)
-    opt = types.SimpleNamespace(use_brdf=True, lambda_extra_kd=a.lambda_extra_kd)
-    sync = (lambda: MD.allreduce_gradients([voff] + list(mlp.parameters()) + [env])) if world > 1 else None
+    opt = types.SimpleNamespace(use_brdf=True, lambda_extra_kd=a.lambda_extra_kd, lambda_rgb=a.lambda_rgb, lambda_mask=a.lambda_mask)
+    nerf_params = field.parameters() if field is not None else []
+    sync = (lambda: MD.allreduce_gradients([voff] + list(mlp.parameters()) + [env] + nerf_params)) if world > 1 else None
 
     def psnr_of(view):
-        pose, (gt, _) = data[view]
+        pose, (gt, _, _, _) = data[view]
         with torch.no_grad():
             img = harness.test_view(Wk, mlp, env.detach(), pose, intr, H, Wd, max(a.spp, 16), a.ssaa, random_offset=4242).view(-1, 3)
         return float(-10 * torch.log10(((img - gt) ** 2).mean()))
+
+    def psnr_image_of(view):      # the NeRF colour branch's frame (Trainer.test's _rgb.png) against the same view
+        pose, (gt, _, _, _) = data[view]
+        img = harness.nerf_view(Wk, field, pose, intr, H, Wd, a.ssaa).view(-1, 3)
+        return float(-10 * torch.log10(((img - gt) ** 2).mean()))
     psnr0 = psnr_of(0)
+    psnr_img0 = psnr_image_of(0) if field is not None else None
     order = np.random.permutation(len(data))
-    t0 = time.perf_counter(); hist = []
+    t0 = time.perf_counter(); hist = []; hist_img = []
     for it in range(step0, a.iters):
         k = (it * world + rank) % len(data)
         if k == 0 and rank == 0: order = np.random.permutation(len(data))
-        pose, (gt, gt_lin) = data[int(order[k]) if world == 1 else k]
+        pose, (gt, gt_lin, gt_mask, raw) = data[int(order[k]) if world == 1 else k]
+        extra, loss_extra = {}, {}
+        if field is not None:
+            extra = dict(field=field, offset_nerf_grad=a.enable_offset_nerf_grad)
+            loss_extra = dict(gt_mask=gt_mask)
+            if a.background == "random" and gt_mask is not None:      # utils.py:949-956: the image with alpha over per-pixel noise, the frame over the same noise
+                extra["bg_color"] = torch.rand(H * Wd, 3, device="cuda")
+                gt = raw * gt_mask + extra["bg_color"] * (1 - gt_mask)
         for o in (o_geo, o_mat, o_lgt): o.zero_grad(set_to_none=True)
         out = harness.render_stage1_outputs(Wk, verts, voff, tris, mlp, env, mods, H, Wd, a.spp, a.ssaa, pose=pose, intrinsics=intr, topology=topo,
-                                            pos_gradient_boost=a.pos_gradient_boost, with_normal_ao=a.lambda_extra_kd > 0, exposure=a.exposure if a.use_hdr else None)
-        loss = losses.stage1_loss(out, gt, gt_lin, opt, vertices=verts, voffsets=voff, triangles=tris)
+                                            pos_gradient_boost=a.pos_gradient_boost, with_normal_ao=a.lambda_extra_kd > 0, exposure=a.exposure if a.use_hdr else None, **extra)
+        loss = losses.stage1_loss(out, gt, gt_lin, opt, vertices=verts, voffsets=voff, triangles=tris, **loss_extra)
+        if field is not None:
+            hist_img.append(((out["image"].detach() - gt) ** 2).mean())
         val = losses.stage1_optimizer_step(loss, o_geo, o_mat, o_lgt, light_base=env, encoder_params=mlp.encoder.params, scheduler=s_geo, scheduler_mat=s_mat,
                                            scheduler_light=s_lgt, grad_sync=sync)
         hist.append(val)
@@ -183,11 +223,15 @@ def main():
             print("[%5d/%d] loss %.5f  lr vert %.2e mat %.2e light %.2e" % (it, a.iters, val, o_geo.param_groups[0]["lr"], o_mat.param_groups[0]["lr"], o_lgt.param_groups[0]["lr"]), flush=True)
         if rank == 0 and a.save_interval > 0 and ((it + 1) % a.save_interval == 0 or it == a.iters - 1):
             os.makedirs(os.path.join(a.workspace, "checkpoints"), exist_ok=True)
-            CK.save_checkpoint(os.path.join(a.workspace, "checkpoints", "ngp_stage1_ep%04d.pth" % (it + 1)), mlp, voff, env, epoch=it + 1, global_step=it + 1, material_config=cfg,
+            CK.save_checkpoint(os.path.join(a.workspace, "checkpoints", "ngp_stage1_ep%04d.pth" % (it + 1)), mlp, voff, env, epoch=it + 1, global_step=it + 1, material_config=cfg, field=field,
                                train_state={**{k_: o_.state_dict() for k_, o_ in optims.items()}, **{k_: s_.state_dict() for k_, s_ in scheds.items()}})
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     Wk.update_mesh((verts + voff.detach()).contiguous(), tris)
     psnr1 = psnr_of(0)
+    if rank == 0 and field is not None:
+        hi = [float(x) for x in hist_img]; win = max(1, min(10, len(hi) // 2))
+        print("NeRF colour branch (`image`): loss first-window %.6f last-window %.6f (windows of %d); PSNR of view 0: %.2f -> %.2f dB" % (
+            float(np.mean(hi[:win])) if hi else float("nan"), float(np.mean(hi[-win:])) if hi else float("nan"), win, psnr_img0, psnr_image_of(0)))
     if rank == 0:
         n = max(1, a.iters - step0)
         print("stage-1 training %d iterations at %dx%d ssaa %d spp %d on %d GPU(s): %.1f ms/iteration; loss %.5f -> %.5f; PSNR of view 0: %.2f -> %.2f dB" % (
