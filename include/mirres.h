@@ -607,6 +607,50 @@ int mirres_grid_tv_grad(const mirres_density_t* net, const float* pos, long long
                         long long workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------------------------------------------------------
+ * torch-ngp's GridEncoder as an operator of its own (gridenc.hip; encoding.py's GridEncoder): what the fused entries above hold for one configuration, for any of
+ * input_dim D in {2, 3}, level_dim C in {1, 2, 4, 8}, 1 .. 16 levels, gridtype hash / tiled, align_corners, linear / smoothstep interpolation.  fp32 only.  The table
+ * is passed beside the layout: f32 [offsets[num_levels], C], 16-byte aligned.  The arithmetic is FIXED, every operation rounded on its own:
+ *   u[d] = (x[d] + bound) / (2.0f * bound); a point is in bounds when every u[d] >= 0 && u[d] <= 1 (NaN: outside);
+ *   per level: p = u[d] * scale; p = p + (align_corners ? 0.0f : 0.5f); cell = floorf(p); f = p - cell; smoothstep: s = (f * f) * (3.0f - 2.0f * f) with derivative
+ *   (6.0f * f) * (1.0f - f); linear: s = f, derivative 1; corners idx ascending: w = 1; for d ascending w = w * (bit d of idx ? s[d] : 1.0f - s[d]);
+ *   r[ch] = r[ch] + w * table[entry][ch]; entry = get_grid_index (gridencoder.cu:66-84) in uint32 arithmetic: the stride loop stops adding axes once the stride
+ *   exceeds the level's size, the factor is align_corners ? resolution : resolution + 1, the hash (primes 1, 2654435761, 805459861) only for gridtype 0 with a final
+ *   stride above the level's size, then % size.  At u = 1 with align_corners the index is one past the last row, wrapped by the modulo, as in the reference.
+ * For D = 3, C = 2, hash, align_corners 0, linear the features have mirres_density_points' bits and grad_pos mirres_radiance_points_bwd_pos' encoder part's.        */
+typedef struct {
+    int input_dim;                                    /* D: 2 or 3                                                                                              */
+    int level_dim;                                    /* C: 1, 2, 4 or 8                                                                                        */
+    int num_levels;                                   /* 1 .. 16                                                                                                */
+    int gridtype;                                     /* 0 hash, 1 tiled                                                                                        */
+    int align_corners;                                /* 0 or 1                                                                                                 */
+    int interpolation;                                /* 0 linear, 1 smoothstep                                                                                 */
+    int offsets[MIRRES_DENSITY_MAX_LEVELS + 1];       /* as mirres_density_t                                                                                    */
+    int resolution[MIRRES_DENSITY_MAX_LEVELS];        /* the KERNEL's resolution, ceil(scale) + 1                                                               */
+    int hashed[MIRRES_DENSITY_MAX_LEVELS];            /* 1: the level's index is the hash (gridtype 0 and a final stride above the level's size)                */
+    float scale[MIRRES_DENSITY_MAX_LEVELS];           /* gridencoder.cu:138, computed once on the host                                                          */
+} mirres_gridenc_t;
+/* GridEncoder.__init__ (gridencoder/grid.py:104-135) and gridencoder.cu:137-139 on the host, under mirres_density_layout's rules: per_level_scale in double,
+ * S = float(log2 per_level_scale), a correctly rounded exp2f, the level's size = min(2^log2_hashmap_size, (r if align_corners else r + 1)^D) with r = ceil(base pls^l),
+ * rounded up to a multiple of 8.  Fills every field of `g` and returns the number of table entries, or a negative error.  For D = 3, hash, align_corners 0 and
+ * per_level_scale = exp2(log2(desired / base) / (L - 1)) it fills mirres_density_layout's numbers.                                                                 */
+long long mirres_gridenc_layout(int input_dim, int level_dim, int num_levels, double per_level_scale, int base_resolution, int log2_hashmap_size, int gridtype,
+                                int align_corners, int interpolation, mirres_gridenc_t* g);
+/* pos f32[n, D] -> out f32[n, L * C] (feature l * C + ch; 16-byte aligned), every element written: a point out of bounds and every level >= max_level give 0
+ * (max_level above num_levels counts as num_levels).  One thread per (point, level), launched level-major.                                                        */
+int mirres_grid_encode_fwd(const mirres_gridenc_t* g, const float* table, const float* pos, long long n, float bound, int max_level, float* out, void* stream);
+/* The adjoint: grad_out f32[n, L * C] (16-byte aligned) -> grad_table f32[entries, C], ACCUMULATED INTO with fp32 atomics in no fixed order (NULL: not wanted), term
+ * w * grad_out[l * C + ch] per corner, one entry's C channels by C adjacent lanes, launched level-major; grad_pos f32[n, D], OVERWRITTEN (NULL: not wanted): the
+ * reference's dy_dx (gridencoder.cu:198-243) recomputed, one thread per point, no atomics, equal inputs give equal bits — levels l ascending, axes a ascending; the
+ * pairs of corners that differ in a alone, ascending (bit k of the pair: the k-th other axis): w = scale_l; w = w * (s or 1 - s) per other axis ascending;
+ * r[ch] = r[ch] + (w * (table[right][ch] - table[left][ch])) * derivative[a]; then for ch ascending g[a] = g[a] + grad_out[l * C + ch] * r[ch]; last
+ * grad_pos[a] = g[a] / (2.0f * bound).  A point out of bounds scatters nothing and gets exactly 0; levels >= max_level carry no gradient.
+ * Both entries refuse, before a device is touched: a NULL layout, a D, C, level count or switch outside the sets above, a layout mirres_gridenc_layout would not
+ * have filled, n < 0 or n > 2^31, a NULL table / pos / out / grad_out with n > 0, a misaligned pointer, a negative max_level, a bound that is not positive and
+ * finite.  n == 0 launches nothing.                                                                                                                              */
+int mirres_grid_encode_bwd(const mirres_gridenc_t* g, const float* table, const float* pos, long long n, float bound, int max_level, const float* grad_out,
+                           float* grad_table, float* grad_pos, void* stream);
+
+/* --------------------------------------------------------------------------------------------------------------------------------------------
  * The stage-0 ray-marching operators (raymarch.hip): torch-ngp's raymarching module (raymarching/src/raymarching.cu), fp32 only, and the upkeep of the
  * occupancy grid the marchers read (nerf/renderer.py:1438-1595).  The arithmetic is FIXED (csrc/device_march.hpp): no contraction, IEEE
  * division, the reference's own C++ promotions, mrf_exp where the reference has __expf.  Deviations: march_rays_train hands out point offsets as the exclusive

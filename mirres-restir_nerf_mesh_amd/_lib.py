@@ -71,6 +71,11 @@ class RadianceNet(C.Structure):
     _fields_ = [("grid", DensityNet), ("w1", vp), ("c0", vp), ("c1", vp), ("c2", vp)]
 
 
+class GridEnc(C.Structure):
+    _fields_ = [("input_dim", C.c_int), ("level_dim", C.c_int), ("num_levels", C.c_int), ("gridtype", C.c_int), ("align_corners", C.c_int), ("interpolation", C.c_int),
+                ("offsets", C.c_int * 17), ("resolution", C.c_int * 16), ("hashed", C.c_int * 16), ("scale", C.c_float * 16)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int, vp)   # int halo(void* user, float* records, int sample, void* stream)
 
 
@@ -170,6 +175,9 @@ SIGNATURES = {
     "mirres_radiance_points_bwd_pos": (C.c_int, [C.POINTER(RadianceNet), vp, vp, C.c_longlong, f32, vp, vp, vp, vp]),
     "mirres_grid_tv_workspace_bytes": (C.c_longlong, [C.POINTER(DensityNet)]),
     "mirres_grid_tv_grad": (C.c_int, [C.POINTER(DensityNet), vp, C.c_longlong, f32, f32, vp, vp, C.c_longlong, vp]),
+    "mirres_gridenc_layout": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GridEnc)]),
+    "mirres_grid_encode_fwd": (C.c_int, [C.POINTER(GridEnc), vp, vp, C.c_longlong, f32, C.c_int, vp, vp]),
+    "mirres_grid_encode_bwd": (C.c_int, [C.POINTER(GridEnc), vp, vp, C.c_longlong, f32, C.c_int, vp, vp, vp, vp]),
     "mirres_rm_near_far": (C.c_int, [vp, vp, vp, C.c_longlong, f32, vp, vp, vp]),
     "mirres_rm_morton3d": (C.c_int, [vp, C.c_longlong, vp, vp]),
     "mirres_rm_morton3d_invert": (C.c_int, [vp, C.c_longlong, vp, vp]),
