@@ -236,6 +236,40 @@ int mirres_texture_inpaint(int W, int H, int radius, const uint8_t* mask, const 
 /* (:420-422) cv2.resize(INTER_LINEAR) of in u8[H*W*3] to (W / ssaa) x (H / ssaa) (both divisible): odd ssaa the centre texel, even ssaa the mean of
  * the 2 x 2 centre texels rounded half up.                                                                                                */
 int mirres_texture_downsample(int W, int H, int ssaa, const uint8_t* in, uint8_t* out, void* stream);
+/* Chart atlas of the stage-1 mesh export (export.chart_atlas; csrc/atlas.hip; DESIGN.md section 5.7 "Chart atlas"): xatlas in the reference (nerf/renderer.py:334-347), here
+ * charts of faces that look along one coordinate axis, projected along it.  verts f32[V,3], tris i32[T,3] (T < 2^24); all pointers are device memory (NULL allowed
+ * where the count is 0); all calls only enqueue work; no floating-point number is added atomically: equal inputs give equal bytes.
+ * Buckets: k = 0..5 = +x, -x, +y, -y, +z, -z; (U, V) of a bucket = the coordinates (y,z) (z,y) (z,x) (x,z) (x,y) (y,x): (U, V, d_k) is right-handed.
+ *
+ * mirres_atlas_classify: normal f32[T,3] = cross(v1 - v0, v2 - v0) in fp32, e1 = v1 - v0, e2 = v2 - v0, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ * every difference and product rounded once; bucket i32[T] = the k with the largest n . d_k (the largest |component| with its sign), ties to the lowest k.
+ * A face is DEGENERATE (bucket -1, normal 0) when an index is outside [0, V) or repeated, a vertex coordinate or a normal component is not finite, or n = 0.  */
+int mirres_atlas_classify(const float* verts, int V, const int32_t* tris, int T, float* normal, int32_t* bucket, void* stream);
+/* One Jacobi round of relabelling, bucket_in -> bucket_out (different buffers): nbr i32[T,3] = the face across edge (v_k, v_k+1) when exactly two face corners
+ * carry that edge, else -1.  Bucket k is ELIGIBLE for a face when n . d_k > 0 and (n . d_k)^2 >= cos_min^2 ((nx^2 + ny^2) + nz^2), evaluated in fp64 on the
+ * fp32 normal (squares exact, the two sums and the product rounded once); cos_min in [0, 1].  Votes: the face's own bucket 1.5, each neighbour's bucket 1
+ * (a degenerate neighbour none), counted for eligible buckets only.  The face takes the bucket with the most votes; its own when that is among the tied or
+ * when nothing received a vote, else the lowest tied k.  A degenerate face stays -1.                                                              */
+int mirres_atlas_smooth(const float* normal, const int32_t* bucket_in, const int32_t* nbr, int T, float cos_min, int32_t* bucket_out, void* stream);
+/* bounds f32[n_charts,4] = (min U, min V, max U, max V) over the three vertices of every face f with chart[f] in [0, n_charts) and a bucket in 0..5 (the projection
+ * is bucket[f]'s: all faces of a chart hold one bucket), by atomicMin / atomicMax on the order-preserving integer image of the float (so -0 < +0); the
+ * coordinates are selected, not computed.  A chart without such a face gets NaN.  Faces with chart -1 take no part.                               */
+int mirres_atlas_bounds(const float* verts, int V, const int32_t* tris, int T, const int32_t* bucket, const int32_t* chart, int n_charts, float* bounds, void* stream);
+/* vt f32[n_uv,2]: UV vertex i is mesh vertex uv_vertex[i] in chart c = uv_chart[i] (one per pair: a chart's interior edges share both UV vertices):
+ * u = ((origin[c].x + 0.5) + (U - bounds[c].minU) * density) / w0, v likewise with V, minV, origin[c].y, h0 — in fp32: the subtraction, the multiplication,
+ * the addition and the division each rounded once ((origin + 0.5) is exact).  origin i32[n_charts,2] = the chart rectangle's first export texel (column, row),
+ * chart_bucket i32[n_charts]; the rectangle is ceil((max - min) * density) + 1 texels a side (the same fp32 subtraction and product), so the geometry sits
+ * half a texel inside it.  A pair that names no chart or no vertex gets NaN (such a triangle covers nothing).                                      */
+int mirres_atlas_emit(const float* verts, int V, const int32_t* uv_chart, const int32_t* uv_vertex, int n_uv, const int32_t* chart_bucket, const float* bounds,
+                      const int32_t* origin, int n_charts, float density, int w0, int h0, float* vt, void* stream);
+/* The overlap check on the W x H bake grid with the coverage rule of mirres_uv_rasterize (shared code: 1/256-texel snap, int64 edge functions, top-left rule),
+ * over the same balanced (triangle, 32-texel chunk) work items.  Pass 1: every triangle marks the centres it covers, one bit per texel (atomicOr); a centre found
+ * marked is recorded in a second bit plane.  Pass 2: flagged u8[n_charts + 1]: [c] = 1 when a triangle of chart c = face_chart[t] covers a centre covered more
+ * than once, [n_charts] likewise for the triangles of no chart (face_chart -1); 0 otherwise.  Every chart that takes part in an overlap is flagged, whatever
+ * the order the triangles ran in.  scratch: mirres_atlas_verify_scratch(T, W, H) device bytes (-1 when out of range; grid limits as mirres_uv_rasterize). */
+long long mirres_atlas_verify_scratch(int T, int W, int H);
+int mirres_atlas_verify(const float* vt, int n_uv, const int32_t* ft, int T, const int32_t* face_chart, int n_charts, int W, int H, uint8_t* flagged,
+                        void* scratch, long long scratch_bytes, void* stream);
 /* dr.antialias (nerf/renderer.py:1184-1206; nvdiffrast is un-vendored: the published algorithm, csrc/antialias.hip): color f32[H*W,C], rast f32[H*W,4]
  * (mirres_raster_raycast's record: .z orders the two triangles of a pixel pair by distance, .w = triangle id + 1), pos_clip f32[V,4] clip-space
  * vertex positions (pixel (i, j)'s centre is NDC ((2i + 1) / W - 1, (2j + 1) / H - 1)), tri i32[T,3], opp i32[T,3] the vertex across each edge

@@ -130,6 +130,12 @@ SIGNATURES = {
     "mirres_bake_quantise": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "mirres_texture_inpaint": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mirres_texture_downsample": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "mirres_atlas_classify": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "mirres_atlas_smooth": (C.c_int, [vp, vp, vp, C.c_int, f32, vp, vp]),
+    "mirres_atlas_bounds": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
+    "mirres_atlas_emit": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, f32, C.c_int, C.c_int, vp, vp]),
+    "mirres_atlas_verify_scratch": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "mirres_atlas_verify": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong, vp]),
     "mirres_antialias": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mirres_antialias_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]),
     "mirres_dump_render": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),

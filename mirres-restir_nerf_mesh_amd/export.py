@@ -1,7 +1,8 @@
 """Stage-1 mesh export (nerf/renderer.py:319-476 `NeRFRenderer.export_stage1`, driven by Trainer.export_stage1, nerf/utils.py:1271-1281): per mesh
 cascade an OBJ with UVs, its MTL and two baked textures of the material field — feat0 (kd, channels 0-2, the MTL's map_Kd) and feat1 (channels 3-5).
 
-    vt, ft, fill = uv_atlas(v, f, h0, w0)                                   # xatlas in the reference (:334-347): a deterministic pair atlas here
+    vt, ft, fill = uv_atlas(v, f, h0, w0)                                   # xatlas in the reference (:334-347): a deterministic pair atlas here,
+    vt, ft, info = chart_atlas(v, f, h0, w0, ssaa)                          # or axis-projected charts built on csrc/atlas.hip (atlas="charts")
     feat0, feat1 = bake_textures(mlp.sample_no_di, v, f, vt, ft, h0, w0, ssaa)["feat"]     # :349-422 on csrc/bake.hip
     export_stage1(path, vertices, triangles, v_cumsum, f_cumsum, mlp, texture_size=4096, ssaa=2)   # the cascade loop (:464-476)
 
@@ -184,12 +185,21 @@ def uv_atlas(v, f, h0, w0):
                 break
         packed = _shelf_pack(side(lo), w0, h0)
     S = side(lo); x, y = packed
+    vt, ft = _cell_uvs(f, pairs, singles, S, x, y, w0, h0)
+    fill = float((S[:P] ** 2).sum() + 0.5 * (S[P:] ** 2).sum()) / float(w0 * h0)
+    return vt, ft.astype(np.int32), fill
+
+
+def _cell_uvs(f, pairs, singles, S, x, y, w0, h0):
+    """UVs of pair and single cells (sides S, origins (x, y) in export texels; the pairs' cells first): vt f32[4 P + 3 Sg, 2] and ft i64[T,3], of which
+    only the rows of the faces in `pairs` / `singles` are set."""
+    P, Sg = pairs.shape[0], singles.shape[0]
     # corners of a cell: A (x, y), B (x + S, y + S) on the diagonal, C (x + S, y) below it, D (x, y + S) above it
     corner = lambda dx, dy, sel: np.stack(((x[sel] + dx * S[sel]) / w0, (y[sel] + dy * S[sel]) / h0), -1)
     ps, ss = np.arange(P), P + np.arange(Sg)
     vt = np.concatenate((np.stack((corner(0, 0, ps), corner(1, 1, ps), corner(1, 0, ps), corner(0, 1, ps)), 1).reshape(-1, 2),
                          np.stack((corner(0, 0, ss), corner(1, 0, ss), corner(1, 1, ss)), 1).reshape(-1, 2))).astype(np.float32)
-    ft = np.empty((T, 3), np.int64)
+    ft = np.empty((f.shape[0], 3), np.int64)
     if P:
         t, u, a, b = pairs.T
         base = 4 * np.arange(P)
@@ -199,8 +209,262 @@ def uv_atlas(v, f, h0, w0):
             ft[tri] = np.where(f[tri] == b[:, None], base[:, None] + 1, ft[tri])
     if Sg:
         ft[singles] = 4 * P + 3 * np.arange(Sg)[:, None] + np.arange(3)[None, :]
-    fill = float((S[:P] ** 2).sum() + 0.5 * (S[P:] ** 2).sum()) / float(w0 * h0)
-    return vt, ft.astype(np.int32), fill
+    return vt, ft
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- chart atlas
+N_BUCKETS = 6                  # +x, -x, +y, -y, +z, -z (include/mirres.h)
+
+
+def seam_edges(f, ft):
+    """How many mesh edges carried by exactly two faces are UV seams: the two faces do not use the same two UV vertices along it.  Boundary edges and
+    edges of more than two faces are not counted; a face with a repeated index carries no edge.  One rule for every atlas."""
+    f = np.asarray(f, np.int64).reshape(-1, 3); ft = np.asarray(ft, np.int64).reshape(-1, 3)
+    if f.shape[0] == 0:
+        return 0
+    a = f.reshape(-1); b = f[:, [1, 2, 0]].reshape(-1); ua = ft.reshape(-1); ub = ft[:, [1, 2, 0]].reshape(-1)
+    swap = a > b
+    lo, hi = np.where(swap, b, a), np.where(swap, a, b)
+    ulo, uhi = np.where(swap, ub, ua), np.where(swap, ua, ub)
+    ok = (lo != hi) & ~(f[:, [0, 0, 1]] == f[:, [1, 2, 2]]).any(1).repeat(3)
+    lo, hi, ulo, uhi = lo[ok], hi[ok], ulo[ok], uhi[ok]
+    order = np.lexsort((hi, lo))
+    lo, hi, ulo, uhi = lo[order], hi[order], ulo[order], uhi[order]
+    new = np.concatenate(([True], (lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1])))
+    start = np.nonzero(new)[0]; count = np.diff(np.concatenate((start, [lo.shape[0]])))
+    s2 = start[count == 2]
+    return int(((ulo[s2] != ulo[s2 + 1]) | (uhi[s2] != uhi[s2 + 1])).sum())
+
+
+def _pack_rects(w, h, w0, h0, gap=CELL_GAP):
+    """Rectangles w x h (export texels) on shelves, tallest first (stable), `gap` texels apart: origins (x, y) i64 or None when they do not fit w0 x h0."""
+    n = w.shape[0]
+    x = np.empty(n, np.int64); y = np.empty(n, np.int64)
+    if n and int(w.max()) > w0:
+        return None
+    order = np.argsort(-h, kind="stable"); ws = w[order]; hs = h[order]
+    cum = np.concatenate(([0], np.cumsum(ws + gap)))
+    i = 0; ycur = 0
+    while i < n:
+        if ycur + hs[i] > h0:
+            return None
+        j = max(int(np.searchsorted(cum, cum[i] + w0 + gap, side="right")) - 1, i + 1)
+        x[order[i:j]] = cum[i:j] - cum[i]; y[order[i:j]] = ycur
+        ycur += int(hs[i]) + gap; i = j
+    return x, y
+
+
+@torch.no_grad()
+def atlas_classify(v, f):
+    """mirres_atlas_classify: (normal f32[T,3], bucket i32[T]) of device tensors v f32[V,3], f i32[T,3]."""
+    T = int(f.shape[0])
+    normal = torch.empty((T, 3), dtype=torch.float32, device=f.device); bucket = torch.empty(T, dtype=torch.int32, device=f.device)
+    check(lib().mirres_atlas_classify(_lib.ptr(v) if v.numel() else None, int(v.shape[0]), _lib.ptr(f) if T else None, T, _lib.ptr(normal) if T else None,
+                                      _lib.ptr(bucket) if T else None, stream_ptr()), "mirres_atlas_classify")
+    return normal, bucket
+
+
+@torch.no_grad()
+def manifold_neighbours(f, V):
+    """nbr i32[T,3] of device triangles f i32[T,3]: the face across edge (v_k, v_k+1) when exactly two face corners carry that edge, else -1.  A corner's edge
+    counts when its two indices differ and lie in [0, V)."""
+    T = int(f.shape[0])
+    t64 = f.to(torch.int64)
+    a = t64.reshape(-1); b = t64[:, [1, 2, 0]].reshape(-1)
+    lo, hi = torch.minimum(a, b), torch.maximum(a, b)
+    corner = torch.nonzero((lo != hi) & (lo >= 0) & (hi < V)).squeeze(1)
+    keys, order = torch.sort((lo[corner] << 32) | hi[corner], stable=True)
+    corner = corner[order]
+    nbr = torch.full((3 * T,), -1, dtype=torch.int32, device=f.device)
+    if keys.numel():
+        _, inv, counts = torch.unique_consecutive(keys, return_inverse=True, return_counts=True)
+        start = (torch.cumsum(counts, 0) - counts)[inv]
+        pos = torch.arange(keys.shape[0], device=f.device)
+        two = counts[inv] == 2
+        partner = torch.where(pos == start, pos + 1, pos - 1)[two]
+        nbr[corner[two]] = (corner[partner] // 3).to(torch.int32)
+    return nbr.reshape(T, 3)
+
+
+@torch.no_grad()
+def atlas_smooth(normal, bucket, nbr, cos_min):
+    """mirres_atlas_smooth: one relabelling round -> a new bucket tensor."""
+    T = int(bucket.shape[0])
+    out = torch.empty_like(bucket)
+    check(lib().mirres_atlas_smooth(_lib.ptr(normal) if T else None, _lib.ptr(bucket) if T else None, _lib.ptr(nbr.contiguous()) if T else None, T, float(cos_min),
+                                    _lib.ptr(out) if T else None, stream_ptr()), "mirres_atlas_smooth")
+    return out
+
+
+@torch.no_grad()
+def atlas_charts(f, V, bucket, nbr):
+    """(chart i32[T], n_charts): the connected components of faces joined across manifold edges whose two faces hold one bucket (mirres_mesh_components on edge
+    keys whose lower vertex id carries the bucket), numbered in the order of each chart's smallest face; -1 for a degenerate face (bucket -1)."""
+    T = int(f.shape[0])
+    chart = torch.full((T,), -1, dtype=torch.int32, device=f.device)
+    if T == 0:
+        return chart, 0
+    if N_BUCKETS * V >= 1 << 31:
+        raise ValueError("chart_atlas: %d vertices: the edge keys carry the bucket in the vertex id (fewer than 2^31 / 6 vertices)" % V)
+    t64 = f.to(torch.int64)
+    a = t64.reshape(-1); b = t64[:, [1, 2, 0]].reshape(-1)
+    bk = bucket.to(torch.int64).repeat_interleave(3)
+    corner = torch.nonzero((nbr.reshape(-1) >= 0) & (bk >= 0)).squeeze(1)
+    lo, hi = torch.minimum(a[corner], b[corner]), torch.maximum(a[corner], b[corner])
+    keys, order = torch.sort(((bk[corner] * V + lo) << 32) | hi, stable=True)
+    face = (corner[order] // 3).to(torch.int32).contiguous(); keys = keys.contiguous()
+    label = torch.empty(T, dtype=torch.int32, device=f.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=f.device)
+    check(lib().mirres_mesh_components(_lib.ptr(keys) if keys.numel() else None, _lib.ptr(face) if keys.numel() else None, int(keys.shape[0]), T, _lib.ptr(label),
+                                       _lib.ptr(flag), 0, None, stream_ptr()), "mirres_mesh_components")
+    good = bucket >= 0
+    roots = torch.unique(label[good])                                        # ascending = by smallest face
+    chart[good] = torch.searchsorted(roots, label[good]).to(torch.int32)
+    return chart, int(roots.shape[0])
+
+
+@torch.no_grad()
+def atlas_bounds(v, f, bucket, chart, n_charts):
+    """mirres_atlas_bounds: f32[n_charts,4] = (min U, min V, max U, max V) of every chart's projected vertices."""
+    T = int(f.shape[0])
+    bounds = torch.empty((n_charts, 4), dtype=torch.float32, device=f.device)
+    check(lib().mirres_atlas_bounds(_lib.ptr(v) if v.numel() else None, int(v.shape[0]), _lib.ptr(f) if T else None, T, _lib.ptr(bucket) if T else None,
+                                    _lib.ptr(chart) if T else None, n_charts, _lib.ptr(bounds) if n_charts else None, stream_ptr()), "mirres_atlas_bounds")
+    return bounds
+
+
+@torch.no_grad()
+def atlas_emit(v, uv_chart, uv_vertex, chart_bucket, bounds, origin, density, w0, h0):
+    """mirres_atlas_emit: vt f32[n_uv,2] of the (chart, mesh vertex) pairs."""
+    n_uv = int(uv_chart.shape[0]); n_charts = int(chart_bucket.shape[0])
+    vt = torch.empty((n_uv, 2), dtype=torch.float32, device=v.device)
+    p = lambda t: _lib.ptr(t.contiguous()) if t.numel() else None
+    check(lib().mirres_atlas_emit(p(v), int(v.shape[0]), p(uv_chart), p(uv_vertex), n_uv, p(chart_bucket), p(bounds), p(origin), n_charts, float(density), int(w0), int(h0),
+                                  p(vt), stream_ptr()), "mirres_atlas_emit")
+    return vt
+
+
+@torch.no_grad()
+def atlas_verify(vt, ft, face_chart, n_charts, W, H):
+    """mirres_atlas_verify on the W x H bake grid: flagged u8[n_charts + 1] (device), the last entry for the faces of no chart."""
+    dev = torch.device("cuda")
+    uv = torch.as_tensor(vt, dtype=torch.float32).to(dev).contiguous(); t = torch.as_tensor(ft).to(dev, torch.int32).contiguous()
+    fc = torch.as_tensor(face_chart).to(dev, torch.int32).contiguous()
+    T = int(t.shape[0])
+    if fc.shape[0] != T:
+        raise ValueError("atlas_verify: %d chart labels for %d faces" % (fc.shape[0], T))
+    nbytes = int(lib().mirres_atlas_verify_scratch(T, int(W), int(H)))
+    if nbytes < 0:
+        raise ValueError("atlas_verify: %d triangles on a %d x %d grid are out of range" % (T, W, H))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    flagged = torch.empty(n_charts + 1, dtype=torch.uint8, device=dev)
+    check(lib().mirres_atlas_verify(uv.data_ptr() if T else None, int(uv.shape[0]), t.data_ptr() if T else None, T, fc.data_ptr() if T else None, int(n_charts), int(W), int(H),
+                                    flagged.data_ptr(), scratch.data_ptr(), nbytes, stream_ptr()), "mirres_atlas_verify")
+    return flagged
+
+
+def _chart_layout(v, f, fallback, bounds, h0, w0):
+    """The host step of chart_atlas: one density for the chart rectangles (ceil(extent x density) + 1 texels a side, extent and product in fp32) and the
+    fallback faces' pair / single cells (max(2, ceil(density x longest edge))), shelf-packed together; the density (an fp32 number) is the largest, by
+    bisection as in uv_atlas, whose packing fits.  Returns (density, chart origins i64[C,2], cell vt, cell ft rows i64[T,3])."""
+    C = bounds.shape[0]
+    ext = (bounds[:, 2:4] - bounds[:, 0:2]).astype(np.float32) if C else np.zeros((0, 2), np.float32)
+    if not np.isfinite(ext).all():
+        raise ValueError("chart_atlas: a chart without finite bounds")
+    fl = f[fallback]
+    fl = np.where(((fl >= 0) & (fl < v.shape[0])).all(1, keepdims=True), fl, 0)       # a face with an index out of range: a single cell of the smallest size
+    pairs, singles = pair_triangles(fl)
+    elen = lambda t: np.linalg.norm(v[fl[t][:, [1, 2, 0]]] - v[fl[t]], axis=-1).max(axis=-1) if len(t) else np.zeros(0)
+    L = np.concatenate((np.maximum(elen(pairs[:, 0]), elen(pairs[:, 1])), elen(singles)))
+    L = np.where(np.isfinite(L), L, 0.0)
+
+    def sizes(d):
+        s = np.float32(d)
+        wh = np.ceil(ext * s).astype(np.int64) + 1
+        S = np.maximum(2, np.ceil(float(s) * L)).astype(np.int64)
+        return np.concatenate((wh[:, 0], S)), np.concatenate((wh[:, 1], S))
+    fits = lambda d: _pack_rects(*sizes(d), w0, h0)
+    packed = fits(0.0)
+    if packed is None:
+        raise ValueError("chart_atlas: %d charts and %d cells do not fit a %d x %d texture even at the smallest size" % (C, L.shape[0], w0, h0))
+    lo = 0.0
+    area = float((ext[:, 0].astype(np.float64) * ext[:, 1]).sum() + (L * L).sum())
+    if area > 0:
+        hi = 2.0 * math.sqrt(w0 * h0 / area)
+        for _ in range(64):
+            if fits(hi) is None:
+                break
+            lo, hi = hi, 2.0 * hi
+        for _ in range(48):
+            mid = 0.5 * (lo + hi)
+            if fits(mid) is None:
+                hi = mid
+            else:
+                lo = mid
+            if hi - lo <= 1e-7 * hi:
+                break
+        packed = fits(lo)                                                              # sizes() rounds the density to fp32 itself
+    w, h = sizes(lo); x, y = packed
+    cell_vt, cell_ft = _cell_uvs(fl, pairs, singles, w[C:], x[C:], y[C:], w0, h0)
+    ft_rows = np.full((f.shape[0], 3), -1, np.int64)
+    ft_rows[fallback] = cell_ft
+    return np.float32(lo), np.stack((x[:C], y[:C]), 1), cell_vt, ft_rows
+
+
+@torch.no_grad()
+def chart_atlas(v, f, h0, w0, ssaa=1, cos_min=0.5, smooth_rounds=2):
+    """UV atlas of axis-projected charts (DESIGN.md section 5.7 "Chart atlas"; the rules are written out in include/mirres.h), in uv_atlas's
+    conventions.  On the device: face normals and buckets (the axis direction a face looks along), `smooth_rounds` relabelling rounds, charts = connected faces of one bucket across
+    manifold edges, per-chart bounds, one UV vertex per (chart, mesh vertex), and the overlap check on the (h0 ssaa) x (w0 ssaa) bake grid.  On the host:
+    the shelf packing at one shared density.  Degenerate faces and the faces of charts the check flags (a chart that projects onto itself) fall back to
+    uv_atlas's pair / single cells; after that second packing the check must pass.  Returns (vt f32[Nt,2], ft i32[T,3], info): fill (UV area of the
+    triangles), density (export texels per world unit), n_charts, fallback_faces, seam_edges, face_chart i32[T] (-1 = fallback), host_s."""
+    vn = np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1, 3)); fn = np.ascontiguousarray(np.asarray(f, np.int64).reshape(-1, 3))
+    T, V = fn.shape[0], vn.shape[0]
+    _check_sizes(T, h0, w0, ssaa)
+    if not 0.0 <= float(cos_min) <= 1.0 or int(smooth_rounds) < 0:
+        raise ValueError("chart_atlas: cos_min in [0, 1] and smooth_rounds >= 0 (got %s, %s)" % (cos_min, smooth_rounds))
+    if T and (fn.max() >= 1 << 31 or fn.min() < -(1 << 31)):
+        raise ValueError("chart_atlas: a face index does not fit 32 bits")
+    dev = torch.device("cuda")
+    vd = torch.from_numpy(vn).to(dev); fd = torch.from_numpy(fn).to(dev, torch.int32).contiguous()
+    normal, bucket = atlas_classify(vd, fd)
+    nbr = manifold_neighbours(fd, V)
+    for _ in range(int(smooth_rounds)):
+        bucket = atlas_smooth(normal, bucket, nbr, cos_min)
+    chart, n_charts = atlas_charts(fd, V, bucket, nbr)
+    host_s = 0.0
+    v64 = vn.astype(np.float64)
+    for attempt in (0, 1):
+        bounds = atlas_bounds(vd, fd, bucket, chart, n_charts)
+        chart_np = chart.cpu().numpy()
+        t0 = time.perf_counter()
+        density, origin, cell_vt, ft_rows = _chart_layout(v64, fn, np.nonzero(chart_np < 0)[0], bounds.cpu().numpy(), h0, w0)
+        host_s += time.perf_counter() - t0
+        faces = torch.nonzero(chart >= 0).squeeze(1)
+        pair_key, inv = torch.unique((chart[faces].to(torch.int64)[:, None] * max(V, 1) + fd[faces].to(torch.int64)).reshape(-1), return_inverse=True)
+        first = torch.full((n_charts,), T, dtype=torch.int64, device=dev).scatter_reduce(0, chart[faces].long(), faces, "amin")
+        vt_c = atlas_emit(vd, (pair_key // max(V, 1)).to(torch.int32), (pair_key % max(V, 1)).to(torch.int32), bucket[first], bounds,
+                          torch.from_numpy(origin).to(dev, torch.int32), density, w0, h0)
+        ft = torch.from_numpy(ft_rows).to(dev) + int(pair_key.shape[0])
+        ft[faces] = inv.reshape(-1, 3)
+        vt = torch.cat((vt_c, torch.from_numpy(cell_vt).to(dev).reshape(-1, 2)))
+        ft = ft.to(torch.int32)
+        flagged = atlas_verify(vt, ft, chart, n_charts, w0 * ssaa, h0 * ssaa).bool()
+        if not bool(flagged.any()):
+            break
+        if attempt or bool(flagged[n_charts]):
+            raise RuntimeError("chart_atlas: the layout still covers a bake texel twice after the fallback (%d charts flagged)" % int(flagged.sum()))
+        keep = ~flagged[:n_charts]                                                  # the flagged charts' faces join the fallback; the rest stay in order
+        new_id = torch.where(keep, torch.cumsum(keep, 0) - 1, -1).to(torch.int32)
+        chart = torch.where(chart >= 0, new_id[chart.clamp(min=0).long()], chart)
+        n_charts = int(keep.sum())
+    vt_np, ft_np, chart_np = vt.cpu().numpy(), ft.cpu().numpy(), chart.cpu().numpy()
+    q = vt_np[ft_np.astype(np.int64)].astype(np.float64) if T else np.zeros((0, 3, 2))
+    fill = float(0.5 * np.abs((q[:, 1, 0] - q[:, 0, 0]) * (q[:, 2, 1] - q[:, 0, 1]) - (q[:, 1, 1] - q[:, 0, 1]) * (q[:, 2, 0] - q[:, 0, 0])).sum())
+    info = {"fill": fill, "density": float(density), "n_charts": n_charts, "fallback_faces": int((chart_np < 0).sum()), "seam_edges": seam_edges(fn, ft_np),
+            "face_chart": chart_np.astype(np.int32), "host_s": host_s}
+    return vt_np, ft_np, info
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------- bake
@@ -318,11 +582,14 @@ def cascade_sizes(texture_size, cascades):
     return out
 
 
-def export_stage1(path, vertices, triangles, v_cumsum, f_cumsum, mlp, texture_size=4096, ssaa=2, uv=None, field=None, log=print):
+def export_stage1(path, vertices, triangles, v_cumsum, f_cumsum, mlp, texture_size=4096, ssaa=2, uv=None, field=None, log=print, atlas="pairs"):
     """NeRFRenderer.export_stage1 (renderer.py:319-476) with h0 = w0 = texture_size (Trainer.export_stage1(resolution=opt.texture_size)):
     per cascade `mesh_{cas}.obj`, `mesh_{cas}.mtl`, `feat0_{cas}.png`, `feat1_{cas}.png` under `path`.  vertices f32[V,3] already include the
     stage-1 offsets (act_voffsets is the identity); v_cumsum / f_cumsum slice the cascades (CK.load_stage0_mesh).  `uv`: a list of (vt, ft) per
-    cascade (or one pair for a one-cascade mesh) to bake onto instead of uv_atlas.  `field` defaults to mlp.sample_no_di.  Returns the files."""
+    cascade (or one pair for a one-cascade mesh) to bake onto instead of the built-in atlas; `atlas`: which built-in one, "pairs" (uv_atlas) or "charts"
+    (chart_atlas).  `field` defaults to mlp.sample_no_di.  Returns the files."""
+    if atlas not in ("pairs", "charts"):
+        raise ValueError("export_stage1: atlas is 'pairs' or 'charts', got %r" % (atlas,))
     v_cumsum = [int(x) for x in v_cumsum]; f_cumsum = [int(x) for x in f_cumsum]
     ncas = len(v_cumsum) - 1
     if ncas < 1 or len(f_cumsum) != ncas + 1:
@@ -341,7 +608,10 @@ def export_stage1(path, vertices, triangles, v_cumsum, f_cumsum, mlp, texture_si
     for cas in range(ncas):
         h0, w0 = sizes[cas]
         v = V[v_cumsum[cas]:v_cumsum[cas + 1]]; f = F[f_cumsum[cas]:f_cumsum[cas + 1]] - v_cumsum[cas]
-        if uv is None:
+        if uv is None and atlas == "charts":
+            vt, ft, info = chart_atlas(v, f, h0, w0, ssaa)
+            note = "chart atlas fill %.3f, %d charts, %d fallback faces, %d seam edges" % (info["fill"], info["n_charts"], info["fallback_faces"], info["seam_edges"])
+        elif uv is None:
             vt, ft, fill = uv_atlas(v, f, h0, w0)
             note = "atlas fill %.3f" % fill
         else:

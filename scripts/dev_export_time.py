@@ -5,7 +5,7 @@ bench mesh, 335,872 triangles), `clustered` = scene.make_mesh_clustered() (~3e5 
 initialised MLPTexture3D (its cost does not depend on the weights).  Kernel rows: run this under `rocprofv3 --kernel-trace --stats -- python ...`
 in a run of its own.
 
-    python scripts/dev_export_time.py [--mesh sphere clustered --texture_size 4096 --ssaa 2 --repeat 2 --out <dir for the files> --json X.json]"""
+    python scripts/dev_export_time.py [--mesh sphere clustered --atlas {pairs,charts} --texture_size 4096 --ssaa 2 --repeat 2 --out <dir for the files> --json X.json]"""
 import argparse, json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -20,9 +20,19 @@ def field_module():
     return MLPTexture3D(aabb, channels=6, min_max=(mn.cuda(), mx.cuda()), seed=1)
 
 
-def one(name, v, f, mlp, size, ssaa, repeat, out):
-    row = {"mesh": name, "V": int(v.shape[0]), "T": int(f.shape[0]), "texture": size, "ssaa": ssaa}
-    t0 = time.perf_counter(); vt, ft, fill = EX.uv_atlas(v, f, size, size); row["host_atlas_s"] = time.perf_counter() - t0
+def one(name, v, f, mlp, size, ssaa, repeat, out, atlas="pairs"):
+    row = {"mesh": name, "V": int(v.shape[0]), "T": int(f.shape[0]), "texture": size, "ssaa": ssaa, "atlas": atlas}
+    if atlas == "charts":
+        for it in range(repeat):                   # as below: the last run is reported
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            vt, ft, info = EX.chart_atlas(v, f, size, size, ssaa)
+            torch.cuda.synchronize(); total = time.perf_counter() - t0
+        # host = the shelf packing and the fallback cells (numpy); device = everything else: kernels, torch's sorts and uniques, the copies of the results
+        row["host_atlas_s"] = info["host_s"]; row["device_atlas_s"] = total - info["host_s"]; fill = info["fill"]
+        row.update({k: info[k] for k in ("density", "n_charts", "fallback_faces", "seam_edges")})
+    else:
+        t0 = time.perf_counter(); vt, ft, fill = EX.uv_atlas(v, f, size, size); row["host_atlas_s"] = time.perf_counter() - t0
+        row["device_atlas_s"] = 0.0; row["seam_edges"] = EX.seam_edges(f, ft)
     row["atlas_fill"] = fill
     for it in range(repeat):                       # the first run pays allocator growth and first-launch costs; the last one is reported
         ev = []
@@ -54,7 +64,7 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--mesh", nargs="+", default=["sphere", "clustered"]); p.add_argument("--texture_size", type=int, default=4096)
     p.add_argument("--ssaa", type=int, default=2); p.add_argument("--repeat", type=int, default=2); p.add_argument("--out", default=None)
-    p.add_argument("--json", default=None)
+    p.add_argument("--json", default=None); p.add_argument("--atlas", choices=("pairs", "charts"), default="pairs")
     a = p.parse_args()
     mlp = field_module()
     rows = []
@@ -62,9 +72,11 @@ def main():
         v, f = M.scene.make_mesh(7, 64) if name == "sphere" else M.scene.make_mesh_clustered()
         out = a.out or tempfile.mkdtemp(prefix="export_time_")
         os.makedirs(out, exist_ok=True)
-        row = one(name, v, f, mlp, a.texture_size, a.ssaa, a.repeat, out)
+        row = one(name, v, f, mlp, a.texture_size, a.ssaa, a.repeat, out, a.atlas)
         rows.append(row)
         print("%s: T=%d, %d^2 x ssaa %d, atlas fill %.3f, texel coverage %.3f" % (name, row["T"], a.texture_size, a.ssaa, row["atlas_fill"], row["texel_coverage"]))
+        print("  %s atlas: device %.3f s, %d seam edges%s" % (a.atlas, row["device_atlas_s"], row["seam_edges"], "" if a.atlas == "pairs" else
+              ", density %.1f, %d charts, %d fallback faces" % (row["density"], row["n_charts"], row["fallback_faces"])))
         print("  host  atlas %.3f s | copy back %.3f s | PNG x2 %.3f s (%.1f MB, zlib level 6) | OBJ %.3f s (%.1f MB)" % (
             row["host_atlas_s"], row["host_copy_back_s"], row["host_png_s"], row["png_bytes"] / 1e6, row["host_obj_s"], row["obj_bytes"] / 1e6))
         print("  device bake %.2f ms (wall %.3f s):" % (row["bake_device_ms"], row["bake_wall_s"]))

@@ -98,6 +98,7 @@ def build_parser():
     p.add_argument("--stage0_ckpt", default=None, help="--nerf_image: a stage-0 checkpoint, or `random` (RadianceField.init_random)")
     p.add_argument("--export_mesh", action="store_true", help="after the views, export the stage-1 textured mesh to <workspace>/mesh_stage1 (main.py:256-258; off by default)")
     p.add_argument("--texture_size", type=int, default=4096, help="main.py --texture_size: texture side of the first cascade of --export_mesh (baked at --ssaa)")
+    p.add_argument("--atlas", choices=("pairs", "charts"), default="pairs", help="--export_mesh: the UV atlas, triangle pairs (export.uv_atlas) or axis-projected charts (export.chart_atlas)")
     p.add_argument("--textured_mesh", default=None, help="render the views from this exported stage-1 asset (mesh_{cas}.obj, feat0/feat1_{cas}.png|.jpg); with "
                    "--ckpt also report each textured frame's PSNR against the field's frame")
     return p
@@ -240,7 +241,7 @@ def main():
             print("NeRF colour branch (_rgb.png): " + pm_nerf.report())
         if a.export_mesh:          # trainer.export_stage1(resolution=opt.texture_size) after the test views (main.py:256-258)
             from mirres_restir_nerf_mesh_amd import export as EX
-            EX.export_stage1(os.path.join(a.workspace, "mesh_stage1"), verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa)
+            EX.export_stage1(os.path.join(a.workspace, "mesh_stage1"), verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa, atlas=a.atlas)
     if a.textured_mesh:
         if world > 1:
             dist.barrier()                                                 # the asset may just have been written by rank 0

@@ -3,11 +3,11 @@ at the end of training, main.py:314-315, and by `--test` unless `--test_no_mesh`
 the baked material textures `feat0_{cas}.png` (kd, the MTL's map_Kd) and `feat1_{cas}.png` (channels 3-5), on the HIP bake (csrc/bake.hip).
 
     python scripts/export_stage1.py --workspace <ws> --ckpt <ws>/checkpoints/ngp_stage1_ep0100.pth \
-        [--texture_size 4096 --ssaa 2 --bound 2 --cascade N --uv_obj A.obj [B.obj ...] --out <ws>/mesh_stage1 --synthetic]
+        [--texture_size 4096 --ssaa 2 --bound 2 --cascade N --atlas {pairs,charts} --uv_obj A.obj [B.obj ...] --out <ws>/mesh_stage1 --synthetic]
 
 The checkpoint is read exactly as scripts/evaluate.py reads it (stage-0 mesh + stage-1 vertex offsets, material field with the training run's
 constants: `--bound`, `--roughness_min`, `--me_max`, `--kd_min`, `--kd_max`).  `--uv_obj`: bake onto UV layouts made elsewhere (one OBJ per cascade,
-whose faces are the cascade's triangles) instead of the built-in atlas.  `--synthetic` exports scripts/evaluate.py's throw-away workspace, made in a
+whose faces are the cascade's triangles) instead of the built-in atlas, which `--atlas` selects (default: the pair atlas).  `--synthetic` exports scripts/evaluate.py's throw-away workspace, made in a
 new temporary directory unless `--workspace` names one."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "scripts"))
@@ -39,6 +39,7 @@ def main(argv=None):
     p.add_argument("--me_max", type=float, default=None)
     p.add_argument("--kd_min", type=float, nargs=3, default=None); p.add_argument("--kd_max", type=float, nargs=3, default=None)
     p.add_argument("--uv_obj", nargs="+", default=None, help="OBJ files (one per cascade) whose texture coordinates to bake onto")
+    p.add_argument("--atlas", choices=("pairs", "charts"), default="pairs", help="the built-in UV atlas: triangle pairs (export.uv_atlas) or axis-projected charts (export.chart_atlas)")
     p.add_argument("--synthetic", action="store_true")
     a = p.parse_args(argv)
     if a.texture_size <= 0 or a.ssaa < 1:
@@ -58,7 +59,7 @@ def main(argv=None):
         uv = [EX.uv_from_obj(path, t[f_cumsum[c]:f_cumsum[c + 1]] - v_cumsum[c]) for c, path in enumerate(a.uv_obj)]
     out = a.out or os.path.join(a.workspace, "mesh_stage1")
     t0 = time.perf_counter()
-    files = EX.export_stage1(out, verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa, uv=uv)
+    files = EX.export_stage1(out, verts, t, v_cumsum, f_cumsum, mlp, texture_size=a.texture_size, ssaa=a.ssaa, uv=uv, atlas=a.atlas)
     print("[export] %d files in %s (%.1f s)" % (len(files), out, time.perf_counter() - t0))
     return files
 
