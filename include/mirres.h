@@ -666,7 +666,8 @@ typedef struct {
 /* GridEncoder.__init__ (gridencoder/grid.py:104-135) and gridencoder.cu:137-139 on the host, under mirres_density_layout's rules: per_level_scale in double,
  * S = float(log2 per_level_scale), a correctly rounded exp2f, the level's size = min(2^log2_hashmap_size, (r if align_corners else r + 1)^D) with r = ceil(base pls^l),
  * rounded up to a multiple of 8.  Fills every field of `g` and returns the number of table entries, or a negative error.  For D = 3, hash, align_corners 0 and
- * per_level_scale = exp2(log2(desired / base) / (L - 1)) it fills mirres_density_layout's numbers.                                                                 */
+ * per_level_scale = exp2(log2(desired / base) / (L - 1)) it fills mirres_density_layout's numbers (one routine computes both), but for the `hashed` flag
+ * of a level whose uint32 stride product wraps (its square or cube passes 2^32): indexed densely with wrapped strides here, as in the reference, hashed there.          */
 long long mirres_gridenc_layout(int input_dim, int level_dim, int num_levels, double per_level_scale, int base_resolution, int log2_hashmap_size, int gridtype,
                                 int align_corners, int interpolation, mirres_gridenc_t* g);
 /* pos f32[n, D] -> out f32[n, L * C] (feature l * C + ch; 16-byte aligned), every element written: a point out of bounds and every level >= max_level give 0

@@ -2,7 +2,8 @@
 // --mcubes_reso differs from the density grid's size.  One fused query per point:
 //   torch-ngp GridEncoder forward (gridencoder/src/gridencoder.cu:87-196; gridtype 'hash', align_corners False, linear interpolation, D = 3, C = 2, fp32 table)
 //   -> sigma_net, bias-free 32 -> 64 (ReLU) -> row 0 of the 64 -> 16 layer -> trunc_exp's forward, a plain exp (activation.py:8-10), here mrf_exp.
-//   mirres_density_layout   the level table of GridEncoder.__init__ (gridencoder/grid.py:104-135) and the kernel's per-level quantities (gridencoder.cu:137-139);
+//   mirres_density_layout   the level table of GridEncoder.__init__ (gridencoder/grid.py:104-135) and the kernel's per-level quantities (gridencoder.cu:137-139):
+//                           grid_layout.hpp's routine, which mirres_gridenc_layout calls too;
 //   mirres_density_points   sigma (and optionally the 32 features) of n points;
 //   mirres_density_volume   sigma on the lattice xs x ys x zs (z fastest), optionally masked by the nearest cell of the density grid (renderer.py:532-541).
 // The encoder's arithmetic is FIXED so that numpy float32 restates it bit for bit: u = (x + bound) / (2 bound) by IEEE division,
@@ -64,35 +65,11 @@ extern "C" long long mirres_density_layout(int num_levels, int base_resolution, 
                   num_levels, DN_LEVELS, base_resolution, desired_resolution, log2_hashmap_size);
         return MIRRES_E_ARG;
     }
-    // grid.py:108: per_level_scale in double; grid.py:128-130: the level's size from the Python-side resolution
+    // grid.py:108: per_level_scale in double
     const double pls = num_levels > 1 ? exp2(log2(desired_resolution / (double)base_resolution) / (double)(num_levels - 1)) : 1.0;
-    const float S = (float)log2(pls);                               // the `const float S` gridencoder.cu's kernel receives
-    const long long max_params = 1LL << log2_hashmap_size;
-    long long offset = 0;
     net->num_levels = num_levels;
-    for (int l = 0; l < DN_LEVELS; l++) { net->offsets[l + 1] = 0; net->resolution[l] = 0; net->hashed[l] = 0; net->scale[l] = 0.f; }
-    for (int l = 0; l < num_levels; l++) {
-        const long long res = (long long)ceil((double)base_resolution * pow(pls, (double)l));
-        long long params = (res + 1) * (res + 1) * (res + 1);
-        if (params > max_params) params = max_params;
-        params = (params + 7) / 8 * 8;
-        net->offsets[l] = (int)offset;
-        offset += params;
-        if (offset > 0x7FFFFFFFLL) { set_error("mirres_density_layout: %lld entries do not fit the 32-bit offsets of the reference's table", offset); return MIRRES_E_ARG; }
-        // gridencoder.cu:138-139 with exp2f correctly rounded: t = float(l) * S, e = float(exp2(double(t))), scale = e * float(H) - 1.0f, each step rounded to fp32
-        const float t = (float)l * S;
-        const float e = (float)exp2((double)t);
-        const float scale = e * (float)base_resolution - 1.0f;
-        net->scale[l] = scale;
-        net->resolution[l] = (int)ceilf(scale) + 1;
-        // gridencoder.cu:68-81: stride *= resolution + 1 while stride <= hashmap_size, at most three times; the hash replaces the index when the final stride exceeds it
-        unsigned long long stride = 1;
-        for (int d = 0; d < 3 && stride <= (unsigned long long)params; d++) stride *= (unsigned long long)net->resolution[l] + 1ull;
-        net->hashed[l] = stride > (unsigned long long)params ? 1 : 0;
-    }
-    net->offsets[num_levels] = (int)offset;
-    for (int l = num_levels + 1; l <= DN_LEVELS; l++) net->offsets[l] = (int)offset;
-    return offset;
+    return grid_layout("mirres_density_layout", 3, false, true, false, num_levels, pls, base_resolution, log2_hashmap_size, net->offsets, net->resolution, net->hashed,
+                       net->scale);
 }
 
 extern "C" int mirres_density_points(const mirres_density_t* net, const float* pos, long long n, float bound, float* sigma_out, float* feat_out, void* stream) {

@@ -1,39 +1,25 @@
 // device_gridenc.hpp — torch-ngp's GridEncoder as an operator of its own (gridencoder/src/gridencoder.cu: kernel_grid :87-244, kernel_grid_backward :247-339,
 // kernel_input_backward :343-368), restated for D in {2, 3} and C in {1, 2, 4, 8} channels with gridtype, align_corners, interpolation and max_level at run time.
-// The arithmetic is FIXED and is dn_encode's (device_density.hpp) wherever the two overlap, so that for D = 3, C = 2, hash, align_corners
-// False, linear the features have dn_encode's bits and the input gradient k_radiance_points_bwd_pos' (radiance_pos.hip):
+// The arithmetic is FIXED and is that of device_density.hpp's cell primitives (dn_unit, dn_cell, dn_corner, dn_weight) wherever the two
+// overlap, so that for D = 3, C = 2, hash, align_corners False, linear the features have dn_encode's bits and the input gradient k_radiance_points_bwd_pos'
+// (radiance_pos.hip).  The two stay separate implementations: the switches here are run-time values, and each is the other's check (tests/test_gpu_gridenc.py):
 //   u[d] = (x[d] + bound) / (2.0f * bound); in bounds: every u[d] >= 0 && u[d] <= 1 (NaN: outside);
 //   per level: p = u[d] * scale; p = p + (align_corners ? 0.0f : 0.5f); cell = floorf(p); f = p - cell;
 //              smoothstep: s = (f * f) * (3.0f - 2.0f * f), ds = (6.0f * f) * (1.0f - f); linear: s = f, ds = 1;
 //   corners idx ascending: w = 1; for d ascending: w = w * (bit d of idx ? s[d] : 1.0f - s[d]); r[ch] = r[ch] + w * table[entry][ch];
-//   entry = get_grid_index (gridencoder.cu:66-84) in uint32 arithmetic (gn_strides / gn_index below).
+//   entry = get_grid_index (gridencoder.cu:66-84) in uint32 arithmetic (gn_strides of grid_layout.hpp, gn_index below).
 // Every operation rounds once (the library is built with -ffp-contract=off).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include "engine.hpp"
 #include "device_math.hpp"
+#include "grid_layout.hpp"
 
 namespace mr {
 
 #define GN_BLOCK 256
 #define GN_LEVELS MIRRES_DENSITY_MAX_LEVELS
-#define GN_HD __host__ __device__ __forceinline__
-
-// get_grid_index's stride loop (gridencoder.cu:68-75), which depends on the level alone: stride[d] = the factor of axis d, 0 for an axis the loop no longer reaches
-// (stride > hashmap_size: that axis adds nothing to the index).  Returns the final stride; uint32 arithmetic as in the reference, wrap-around included.
-// Written without an early exit (once s > hs it stays so, because s no longer changes), so that the three strides stay in registers: a loop with a data-dependent
-// exit indexes the array dynamically, and the compiler then moves it to LDS.
-GN_HD uint32_t gn_strides(int D, uint32_t factor, uint32_t hs, uint32_t stride[3]) {
-    uint32_t s = 1;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const bool on = d < D && s <= hs;
-        stride[d] = on ? s : 0u;
-        s = on ? s * factor : s;
-    }
-    return s;
-}
 
 // what a level needs besides the point: wave-uniform
 struct GnLevel {

@@ -8,8 +8,8 @@
 //     dense levels merge equal cells inside the wave with ballots before one global add per distinct cell (k_tv_points) — then one thread per entry with a
 //     count computes the value ONCE and stores grad + (float)count * value (k_tv_apply).  No fp32 atomic: one fixed set of bits per multiset of points.
 //   HASHED levels: fp32 atomics of the value (k_tv_points); the lanes of a wave that hold the same cell are merged first ((float)k * value, k <= 64), an entry's
-//     two channels are issued by a lane pair as one request (radiance_bwd.hip's rb_scatter).  The order of the adds is not fixed.
-// The term's arithmetic is FIXED and restated by tests/tv_refs.py: u and c are dn_encode's; e = dn_index(c); for d = 0, 1, 2: the right neighbour (c[d] + 1, when
+//     two channels are issued by a lane pair as one request (dn_pair_add, as in radiance_bwd.hip's rb_scatter).  The order of the adds is not fixed.
+// The term's arithmetic is FIXED and restated by tests/tv_refs.py: u and c are the encoder's (dn_unit, dn_cell of device_density.hpp); e = dn_index(c); for d = 0, 1, 2: the right neighbour (c[d] + 1, when
 // c[d] < resolution), then the left (c[d] - 1, when c[d] > 0), per channel diff = t[e] - t[nb], res = res + diff, idelta = idelta + diff * diff;
 // value = (w * res) * mr_rcp(mr_sqrt(idelta + 1e-9f)), w = weight / 6.0f — IEEE 1 / sqrt where the reference has the approximate rsqrtf.
 #include <math.h>
@@ -33,26 +33,13 @@ struct TvPlan {
     int dense[DN_LEVELS], n_dense;                                 // the levels k_tv_apply takes
 };
 
-// dn_encode's coordinates of one point; false when a coordinate is out of bounds or not finite
-MR_DEV bool tv_unit(const float* __restrict__ pos, long long i, float bound, float u[3]) {
-    const float den = 2.0f * bound;
-    u[0] = (pos[3 * i] + bound) / den; u[1] = (pos[3 * i + 1] + bound) / den; u[2] = (pos[3 * i + 2] + bound) / den;
-    return u[0] >= 0.f && u[0] <= 1.f && u[1] >= 0.f && u[1] <= 1.f && u[2] >= 0.f && u[2] <= 1.f;
-}
-
-// dn_encode's corner 0
-MR_DEV uint32_t tv_cell(float u, float scale) {
-    float p = u * scale;
-    p = p + 0.5f;
-    return (uint32_t)floorf(p);
-}
-
-// the term of cell (c0, c1, c2) whose entry is e; g: the level's part of the table.  A neighbour that is not taken is read at e (a valid address) and not added.
-MR_DEV void tv_value(const float2* __restrict__ g, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t e, uint32_t s1, uint32_t hs, bool hashed, uint32_t res, float w,
-                     float& v0, float& v1) {
-    const bool take[6] = {c0 < res, c0 > 0u, c1 < res, c1 > 0u, c2 < res, c2 > 0u};
-    const uint32_t nb[6] = {dn_index(c0 + 1u, c1, c2, s1, hs, hashed), dn_index(c0 - 1u, c1, c2, s1, hs, hashed), dn_index(c0, c1 + 1u, c2, s1, hs, hashed),
-                            dn_index(c0, c1 - 1u, c2, s1, hs, hashed), dn_index(c0, c1, c2 + 1u, s1, hs, hashed), dn_index(c0, c1, c2 - 1u, s1, hs, hashed)};
+// the term of cell c whose entry is e; hashed: V.hashed, as the constant the caller knows it to be.  A neighbour that is not taken is read at e (a valid address) and not added.
+MR_DEV void tv_value(const float2* __restrict__ table, const DnLevel& V, bool hashed, const uint32_t c[3], uint32_t e, float w, float& v0, float& v1) {
+    const float2* __restrict__ g = table + (size_t)V.first;
+    const uint32_t s1 = V.s1, hs = V.hs, res = V.s1 - 1u;
+    const bool take[6] = {c[0] < res, c[0] > 0u, c[1] < res, c[1] > 0u, c[2] < res, c[2] > 0u};
+    const uint32_t nb[6] = {dn_index(c[0] + 1u, c[1], c[2], s1, hs, hashed), dn_index(c[0] - 1u, c[1], c[2], s1, hs, hashed), dn_index(c[0], c[1] + 1u, c[2], s1, hs, hashed),
+                            dn_index(c[0], c[1] - 1u, c[2], s1, hs, hashed), dn_index(c[0], c[1], c[2] + 1u, s1, hs, hashed), dn_index(c[0], c[1], c[2] - 1u, s1, hs, hashed)};
     const float2 t = g[e];
     float2 q[6];
 #pragma unroll
@@ -81,14 +68,15 @@ MR_DEV uint64_t tv_match(uint32_t key, bool valid, int bits) {
 __global__ void __launch_bounds__(TV_BLOCK) k_tv_count_lds(mirres_density_t N, TvPlan P, const float* __restrict__ pos, long long n, float bound, uint32_t* __restrict__ ws) {
     __shared__ uint32_t hist[TV_LDS_WORDS];
     const int l = P.lds[blockIdx.y];
-    const float scale = N.scale[l];
-    const uint32_t s1 = (uint32_t)N.resolution[l] + 1u, cells = s1 * s1 * s1;       // <= TV_LDS_WORDS: the host chose the level
+    const DnLevel V = dn_level(N, l);
+    const uint32_t cells = V.s1 * V.s1 * V.s1;                                       // <= TV_LDS_WORDS: the host chose the level
     for (uint32_t k = threadIdx.x; k < cells; k += TV_BLOCK) hist[k] = 0u;
     __syncthreads();
     for (long long i = (long long)blockIdx.x * TV_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * TV_BLOCK) {
-        float u[3];
-        if (!tv_unit(pos, i, bound, u)) continue;
-        const uint32_t idx = tv_cell(u[0], scale) + tv_cell(u[1], scale) * s1 + tv_cell(u[2], scale) * (s1 * s1);
+        float u[3], f[3], o[3]; uint32_t c[3];
+        if (!dn_unit(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], bound, u)) continue;
+        dn_cell(V, u, c, f, o);
+        const uint32_t idx = c[0] + c[1] * V.s1 + c[2] * (V.s1 * V.s1);
         if (idx < cells) atomicAdd(&hist[idx], 1u);                                  // u in [0, 1]: c <= resolution - 1 on every axis, so the guard never fires
     }
     __syncthreads();
@@ -104,13 +92,15 @@ __global__ void __launch_bounds__(TV_BLOCK) k_tv_points(mirres_density_t N, TvPl
     const int mode = P.mode[l];
     if (mode == TV_DENSE_LDS) return;                                                // block-uniform
     const long long i = (long long)blockIdx.x * TV_BLOCK + threadIdx.x;
-    float u[3] = {0.f, 0.f, 0.f};
-    const bool valid = i < n && tv_unit(pos, i, bound, u);
-    const float scale = N.scale[l];
-    const uint32_t s1 = (uint32_t)N.resolution[l] + 1u, hs = (uint32_t)(N.offsets[l + 1] - N.offsets[l]);
-    const bool hashed = mode == TV_HASHED;
-    const uint32_t c0 = valid ? tv_cell(u[0], scale) : 0u, c1 = valid ? tv_cell(u[1], scale) : 0u, c2 = valid ? tv_cell(u[2], scale) : 0u;
-    const uint32_t e = dn_index(c0, c1, c2, s1, hs, hashed);                         // < hs: inside the level
+    float u[3] = {0.f, 0.f, 0.f}, f[3], o[3];
+    const bool valid = i < n && dn_unit(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], bound, u);
+    const DnLevel V = dn_level(N, l);
+    const bool hashed = mode == TV_HASHED;                                           // tv_plan's word for V.hashed
+    uint32_t c[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) u[d] = valid ? u[d] : 0.f;                           // a lane that is not valid holds cell 0 and adds nothing
+    dn_cell(V, u, c, f, o);
+    const uint32_t e = dn_index(c[0], c[1], c[2], V.s1, V.hs, hashed);                                         // < hs: inside the level
     const int lane = lane_id();
     const uint64_t m = tv_match(e, valid, P.bits[l]);
     const int leader = valid ? __builtin_ctzll(m) : lane;
@@ -119,37 +109,31 @@ __global__ void __launch_bounds__(TV_BLOCK) k_tv_points(mirres_density_t N, TvPl
         return;
     }
     // two cells of a hashed level may share an entry: only the lanes that hold the leader's cell are merged into it, the others add their own term
-    const bool same = valid && c0 == (uint32_t)__shfl((int)c0, leader, 64) && c1 == (uint32_t)__shfl((int)c1, leader, 64) && c2 == (uint32_t)__shfl((int)c2, leader, 64);
+    const bool same = valid && c[0] == (uint32_t)__shfl((int)c[0], leader, 64) && c[1] == (uint32_t)__shfl((int)c[1], leader, 64) && c[2] == (uint32_t)__shfl((int)c[2], leader, 64);
     const uint64_t merged = m & __ballot(same);
     const bool ok = valid && (lane == leader || !same);
     float v0 = 0.f, v1 = 0.f;
     if (ok) {
-        tv_value((const float2*)N.table + (size_t)N.offsets[l], c0, c1, c2, e, s1, hs, true, (uint32_t)N.resolution[l], w, v0, v1);
+        tv_value((const float2*)N.table, V, true, c, e, w, v0, v1);
         const float k = lane == leader ? (float)__popcll(merged) : 1.0f;             // <= 64: exact; 1 * v = v
         v0 = k * v0; v1 = k * v1;
     }
-    // rb_scatter's lane pair: the even lane issues channel 0, the odd lane channel 1 of the same entry — first the even lane's entry, then the odd lane's
-    float* const g = grad + 2 * (size_t)N.offsets[l];
-    const int odd = lane & 1;
-    const uint32_t pe = (uint32_t)__shfl_xor((int)e, 1, 64);
-    const int pok = __shfl_xor(ok ? 1 : 0, 1, 64);
-    const float px = __shfl_xor(odd ? v0 : v1, 1, 64);
-    if (odd ? pok : (int)ok) atomicAdd(g + 2 * (size_t)(odd ? pe : e) + odd, odd ? px : v0);
-    if (odd ? (int)ok : pok) atomicAdd(g + 2 * (size_t)(odd ? e : pe) + odd, odd ? v1 : px);
+    dn_pair_add(grad + 2 * (size_t)V.first, e, ok, v0, v1);
 }
 
 // pass 2 of the dense levels: one thread per entry, blockIdx.y = which dense level; an entry no point fell into is not touched
 __global__ void __launch_bounds__(TV_BLOCK) k_tv_apply(mirres_density_t N, TvPlan P, float w, float* __restrict__ grad, const uint32_t* __restrict__ ws) {
     const int l = P.dense[blockIdx.y];
-    const uint32_t s1 = (uint32_t)N.resolution[l] + 1u, hs = (uint32_t)(N.offsets[l + 1] - N.offsets[l]);
+    const DnLevel V = dn_level(N, l);                                                // P.dense holds dense levels only: hashed is the constant false below
+    const uint32_t s1 = V.s1;
     const uint32_t e = blockIdx.x * TV_BLOCK + threadIdx.x;
     if (e >= s1 * s1 * s1) return;                                                   // <= hs (dn_net_ok); the level's padding holds no cell
     const uint32_t count = ws[P.base[l] + e];
     if (!count) return;
-    const uint32_t c0 = e % s1, c1 = (e / s1) % s1, c2 = e / (s1 * s1);
+    const uint32_t c[3] = {e % s1, (e / s1) % s1, e / (s1 * s1)};
     float v0, v1;
-    tv_value((const float2*)N.table + (size_t)N.offsets[l], c0, c1, c2, e, s1, hs, false, (uint32_t)N.resolution[l], w, v0, v1);
-    float2* const g = (float2*)grad + (size_t)N.offsets[l] + e;
+    tv_value((const float2*)N.table, V, false, c, e, w, v0, v1);
+    float2* const g = (float2*)grad + (size_t)V.first + e;
     const float2 old = *g;
     const float k = (float)count;                                                    // rounds above 2^24 points in one cell
     *g = make_float2(old.x + k * v0, old.y + k * v1);

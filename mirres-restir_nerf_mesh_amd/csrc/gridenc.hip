@@ -1,6 +1,7 @@
 // gridenc.hip — torch-ngp's GridEncoder as a stand-alone operator (encoding.py's GridEncoder): any of D in {2, 3}, C in {1, 2, 4, 8}, 1 .. 16 levels, gridtype
 // hash / tiled, align_corners, linear / smoothstep, max_level.  The fused kernels (density.hip, radiance*.hip) stay the fast path of the one configuration the
-// reference's network uses; for that configuration the kernels here give the same bits (device_gridenc.hpp restates dn_encode's arithmetic), so each checks the other.
+// reference's network uses; for that configuration the kernels here give the same bits (device_gridenc.hpp restates the arithmetic of device_density.hpp's cell primitives), so each checks the other.
+// The level table behind mirres_gridenc_layout and the range checks of gn_ok are grid_layout.hpp's, shared with mirres_density_layout and dn_net_ok.
 //   mirres_gridenc_layout    GridEncoder.__init__'s level table (gridencoder/grid.py:104-135) and the kernel's per-level quantities (gridencoder.cu:137-139);
 //   mirres_grid_encode_fwd   kernel_grid (:87-196): one thread per (point, level), blockIdx.y the level as in the reference, so the blocks that run together gather
 //                            from one level's slice of the table; out is [n, L * C] directly (no [L, n, C] and permute).  Measured against one thread per point
@@ -138,12 +139,8 @@ static bool gn_ok(const mirres_gridenc_t* G, const char* who) {
         return false;
     }
     if (G->offsets[0] != 0) { set_error("%s: the first level starts at entry %d, not 0", who, G->offsets[0]); return false; }
+    if (!grid_levels_ok(who, "mirres_gridenc_layout", G->num_levels, G->offsets, G->resolution, G->scale)) return false;
     for (int l = 0; l < G->num_levels; l++) {
-        if (G->offsets[l + 1] <= G->offsets[l] || G->resolution[l] < 1 || G->resolution[l] > (1 << 24) + 1 || !(G->scale[l] >= 0.f) || !(G->scale[l] <= 16777216.f)) {
-            set_error("%s: bad level %d (offsets %d .. %d, resolution %d, scale %g): fill the layout with mirres_gridenc_layout", who, l, G->offsets[l], G->offsets[l + 1],
-                      G->resolution[l], (double)G->scale[l]);
-            return false;
-        }
         const GnLevel V = gn_level(*G, G->input_dim, l);
         if ((G->hashed[l] != 0) != V.hash) { set_error("%s: level %d is marked %s but get_grid_index %s there", who, l, G->hashed[l] ? "hashed" : "not hashed", V.hash ? "hashes" : "does not hash"); return false; }
     }
@@ -193,35 +190,9 @@ extern "C" long long mirres_gridenc_layout(int input_dim, int level_dim, int num
                   base_resolution, log2_hashmap_size, gridtype, align_corners, interpolation);
         return MIRRES_E_ARG;
     }
-    const float S = (float)log2(per_level_scale);                   // the `const float S` gridencoder.cu's kernels receive (grid.py:38)
-    const long long max_params = 1LL << log2_hashmap_size;
-    long long offset = 0;
     g->input_dim = input_dim; g->level_dim = level_dim; g->num_levels = num_levels; g->gridtype = gridtype; g->align_corners = align_corners; g->interpolation = interpolation;
-    for (int l = 0; l < GN_LEVELS; l++) { g->offsets[l + 1] = 0; g->resolution[l] = 0; g->hashed[l] = 0; g->scale[l] = 0.f; }
-    g->offsets[0] = 0;
-    for (int l = 0; l < num_levels; l++) {
-        // grid.py:128-130: the level's size from the Python-side resolution
-        const double res = ceil((double)base_resolution * pow(per_level_scale, (double)l));
-        const double full = pow(align_corners ? res : res + 1.0, (double)input_dim);
-        long long params = full >= (double)max_params ? max_params : (long long)full;
-        params = (params + 7) / 8 * 8;
-        g->offsets[l] = (int)offset;
-        offset += params;
-        // gridencoder.cu:138-139 with exp2f correctly rounded, as mirres_density_layout has it
-        const float t = (float)l * S;
-        const float e = (float)exp2((double)t);
-        const float scale = e * (float)base_resolution - 1.0f;
-        if (params < 8 || !(scale >= 0.f) || !(scale <= 16777216.f)) {
-            set_error("mirres_gridenc_layout: level %d has scale %g and %lld entries (a scale in [0, 2^24] and at least one entry are needed)", l, (double)scale, params);
-            return MIRRES_E_ARG;
-        }
-        g->scale[l] = scale;
-        g->resolution[l] = (int)ceilf(scale) + 1;
-        g->offsets[l + 1] = (int)offset;
-        g->hashed[l] = gn_level(*g, input_dim, l).hash ? 1 : 0;
-    }
-    for (int l = num_levels + 1; l <= GN_LEVELS; l++) g->offsets[l] = (int)offset;
-    return offset;
+    return grid_layout("mirres_gridenc_layout", input_dim, align_corners != 0, gridtype == 0, true, num_levels, per_level_scale, base_resolution, log2_hashmap_size, g->offsets,
+                       g->resolution, g->hashed, g->scale);
 }
 
 static bool gn_args_ok(const char* who, const mirres_gridenc_t* g, const float* table, const float* pos, long long n, float bound) {

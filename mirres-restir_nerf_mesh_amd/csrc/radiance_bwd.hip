@@ -1,6 +1,6 @@
 // radiance_bwd.hip — the adjoint of mirres_radiance_points (radiance.hip): from the cotangents of sigma and rgb to the gradients of the hash table and of the five
 // weight matrices, what torch-ngp's training step asks of NeRFNetwork.forward (nerf/network.py:146-174).  Nothing is taped: the forward is recomputed from pos / dirs
-// with the shared device functions (dn_encode, rd_sigma_net, rd_sh and the chains of rd_color_net).
+// with the shared device functions (dn_encode, rd_sigma_net, rd_sh and the chains of rd_color_net); the scatter walks the same cells with dn_encode's primitives.
 //   colour net   d_pre = grad_rgb * rgb (1 - rgb); a ReLU passes the cotangent where its output is > 0 (an output of exactly 0 passes nothing, as torch's
 //                threshold_backward); the first layer's d_in[16..30] is d_geo_feat; the direction gets no gradient;
 //   sigma        d_h16[0] = grad_sigma * mrf_exp(clamp(h16[0], -15, 15)) (trunc_exp's backward, activation.py:14-16), d_h16[1..15] = d_geo_feat;
@@ -57,41 +57,24 @@ MR_DEV void rb_gemm(const float* sB, const float* sA, int b0, int a0, float (&ac
     }
 }
 
-// the table scatter of one point's d_feat, by lane pairs; every lane of the wave walks every level and corner (ok = false contributes nothing)
+// the table scatter of one point's d_feat, by lane pairs (dn_pair_add).  Every lane of the wave walks every level and corner, so that all reach the shuffles: a lane
+// that is not ok runs on u = 0 (cell 0 of every level) and adds nothing
 MR_DEV void rb_scatter(const mirres_density_t& N, float x, float y, float z, float bound, const float dfeat[DN_FEAT], bool ok, float* __restrict__ gtable) {
-    const float den = 2.0f * bound;
-    const float u[3] = {(x + bound) / den, (y + bound) / den, (z + bound) / den};
-    const int odd = threadIdx.x & 1;
+    float u[3];
+    dn_unit(x, y, z, bound, u);
+#pragma unroll
+    for (int d = 0; d < 3; d++) u[d] = ok ? u[d] : 0.f;
 #pragma unroll
     for (int l = 0; l < DN_LEVELS; l++) {
         if (l >= N.num_levels) continue;
-        const float scale = N.scale[l];
-        const uint32_t s1 = (uint32_t)N.resolution[l] + 1u, hs = (uint32_t)(N.offsets[l + 1] - N.offsets[l]);
-        const bool hashed = N.hashed[l] != 0;
-        float* const g = gtable + 2 * (size_t)N.offsets[l];
+        const DnLevel V = dn_level(N, l);
         float f[3], o[3]; uint32_t c[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {                               // dn_encode's arithmetic; a lane that is not ok may hold anything here and adds nothing
-            float p = (ok ? u[d] : 0.f) * scale;
-            p = p + 0.5f;
-            const float cell = floorf(p);
-            f[d] = p - cell; o[d] = 1.0f - f[d];
-            c[d] = (uint32_t)cell;
-        }
+        dn_cell(V, u, c, f, o);
         const float g0 = dfeat[2 * l], g1 = dfeat[2 * l + 1];
 #pragma unroll
         for (int idx = 0; idx < 8; idx++) {
-            float w = 1.0f;
-            w = w * ((idx & 1) ? f[0] : o[0]);
-            w = w * ((idx & 2) ? f[1] : o[1]);
-            w = w * ((idx & 4) ? f[2] : o[2]);
-            const uint32_t e = dn_index(c[0] + (idx & 1), c[1] + ((idx >> 1) & 1), c[2] + ((idx >> 2) & 1), s1, hs, hashed);     // < hs: inside the level
-            const float v0 = w * g0, v1 = w * g1;
-            const uint32_t pe = (uint32_t)__shfl_xor((int)e, 1, 64);
-            const int pok = __shfl_xor(ok ? 1 : 0, 1, 64);
-            const float px = __shfl_xor(odd ? v0 : v1, 1, 64);      // the even lane receives the odd lane's channel 0, the odd lane the even lane's channel 1
-            if (odd ? pok : (int)ok) atomicAdd(g + 2 * (size_t)(odd ? pe : e) + odd, odd ? px : v0);        // the even lane's entry
-            if (odd ? (int)ok : pok) atomicAdd(g + 2 * (size_t)(odd ? e : pe) + odd, odd ? v1 : px);        // the odd lane's entry
+            const float w = dn_weight(f, o, idx);
+            dn_pair_add(gtable + 2 * (size_t)V.first, dn_corner(V, c, idx), ok, w * g0, w * g1);
         }
     }
 }

@@ -2,7 +2,7 @@
 // asks of self.rgb(xyzs, dirs) under --enable_offset_nerf_grad (nerf/renderer.py:1046-1052: xyzs[mask] is not detached), carried there by the grid encoder's dy_dx
 // (gridencoder/src/gridencoder.cu:198-243, 343-368) and divided by 2 bound (gridencoder/grid.py:156).  The parameters' gradients are radiance_bwd.hip's; the
 // direction gets none (in stage 1 it comes from the camera, not from the mesh).
-// One thread per point, no atomics, nothing taped: the forward is recomputed with the shared device functions (dn_encode, rd_sh, the chains of rd_sigma_net and
+// One thread per point, no atomics, nothing taped: the forward is recomputed with the shared device functions (dn_encode and the cell primitives under it, rd_sh, the chains of rd_sigma_net and
 // rd_color_net on the weights rd_stage_weights put into LDS) and the cotangent goes back under mirres_radiance_points_bwd's rules:
 //   colour net   d_pre = grad_rgb * (rgb (1 - rgb)); a ReLU passes the cotangent where its output is > 0; every adjoint sum is an fmaf chain from 0 over the layer's
 //                outputs ascending (the chains of k_radiance_points_bwd); the first layer's d_in[16..30] is d_h16[1..15];
@@ -121,31 +121,18 @@ __global__ void __launch_bounds__(DN_BLOCK) k_radiance_points_bwd_pos(mirres_rad
 #pragma unroll
         for (int k = 0; k < DN_FEAT; k++) dfeat[k] = fmaf(sw[RD_LDS_W0 + o * DN_FEAT + k], s, dfeat[k]);
     }
-    // the encoder's input gradient: dn_encode's cell, fractions and entries again (the point is in bounds)
-    const float den = 2.0f * bound;
-    const float u[3] = {(x + bound) / den, (y + bound) / den, (z + bound) / den};
-    const float2* __restrict__ table = (const float2*)N.grid.table;
+    // the encoder's input gradient over the forward's cell, fractions and entries (device_density.hpp's primitives; the point is in bounds)
+    float u[3];
+    dn_unit(x, y, z, bound, u);
     float gu[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int l = 0; l < DN_LEVELS; l++) {
         if (l >= N.grid.num_levels) continue;
-        const float scale = N.grid.scale[l];
-        const uint32_t s1 = (uint32_t)N.grid.resolution[l] + 1u, hs = (uint32_t)(N.grid.offsets[l + 1] - N.grid.offsets[l]);
-        const bool hashed = N.grid.hashed[l] != 0;
-        const float2* __restrict__ g = table + (size_t)N.grid.offsets[l];
+        const DnLevel V = dn_level(N.grid, l);
         float f[3], o[3]; uint32_t c[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            float p = u[d] * scale;
-            p = p + 0.5f;
-            const float cell = floorf(p);
-            f[d] = p - cell; o[d] = 1.0f - f[d];
-            c[d] = (uint32_t)cell;
-        }
+        dn_cell(V, u, c, f, o);
         float2 v[8];
-#pragma unroll
-        for (int idx = 0; idx < 8; idx++)
-            v[idx] = g[dn_index(c[0] + (idx & 1), c[1] + ((idx >> 1) & 1), c[2] + ((idx >> 2) & 1), s1, hs, hashed)];
+        dn_gather((const float2*)N.grid.table, V, c, v);
         const float g0 = dfeat[2 * l], g1 = dfeat[2 * l + 1];
 #pragma unroll
         for (int a = 0; a < 3; a++) {
@@ -153,7 +140,7 @@ __global__ void __launch_bounds__(DN_BLOCK) k_radiance_points_bwd_pos(mirres_rad
             float r0 = 0.f, r1 = 0.f;
 #pragma unroll
             for (int pr = 0; pr < 4; pr++) {
-                float w = scale;
+                float w = V.scale;
                 w = w * ((pr & 1) ? f[lo] : o[lo]);
                 w = w * ((pr & 2) ? f[hi] : o[hi]);
                 const int left = ((pr & 1) << lo) | (((pr >> 1) & 1) << hi), right = left | (1 << a);
@@ -164,6 +151,7 @@ __global__ void __launch_bounds__(DN_BLOCK) k_radiance_points_bwd_pos(mirres_rad
             gu[a] = gu[a] + g1 * r1;
         }
     }
+    const float den = 2.0f * bound;
     grad_pos[3 * i] = gu[0] / den; grad_pos[3 * i + 1] = gu[1] / den; grad_pos[3 * i + 2] = gu[2] / den;
 }
 

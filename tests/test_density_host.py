@@ -41,6 +41,61 @@ def test_layout_with_a_small_hash_table_and_bad_arguments():
             stage0.density_layout(1.0, **kw)
 
 
+def _levels(t, n=16):
+    return ([t.offsets[i] for i in range(n + 1)], [t.resolution[i] for i in range(n)], [bool(t.hashed[i]) for i in range(n)],
+            np.array([t.scale[i] for i in range(n)], np.float32).view(np.uint32).tolist())
+
+
+def _want(desired):
+    L = D.layout(desired=desired)
+    assert all(b > a for a, b in zip(L["offsets"].tolist(), L["offsets"].tolist()[1:])) and L["offsets"][-1] == L["total"]
+    return L["total"], (L["offsets"].tolist(), L["resolution"].tolist(), L["hashed"].tolist(), L["scale"].view(np.uint32).tolist())
+
+
+@pytest.mark.parametrize("desired", [2 ** 21, 2 ** 22, 2 ** 24])
+def test_layout_of_a_fine_grid_does_not_overflow(desired):
+    """(resolution + 1)^3 passes 2^63 from a finest resolution of 2^21: taken in 64-bit integers before the clamp to 2^19 it wrapped to a negative level size at 2^21
+    (at 2^22 and 2^24 the wrapped value happened to lie above the clamp).  The restatement's Python integers cannot overflow."""
+    from mirres_restir_nerf_mesh_amd import stage0
+    total, want = _want(desired)
+    net, n = stage0.density_layout(1.0, desired_resolution=float(desired))
+    assert n == total and net.num_levels == 16 and _levels(net) == want
+
+
+@pytest.mark.parametrize("desired,wrapped", [(2 ** 21, []), (2 ** 22, [10]), (2 ** 24, [9])])
+def test_gridenc_layout_of_a_fine_grid_has_the_density_layouts_numbers(desired, wrapped):
+    """mirres_gridenc_layout with the same per_level_scale against the same restatement: total, offsets, resolutions and scale words of every level, and the hashed
+    flag of every level but those whose stride product does not fit 32 bits.  There the two entries may differ, by design (csrc/grid_layout.hpp's `wrap`): the reference's
+    uint32 product wraps (resolution + 1 = 65537: 65537^2 = 2^32 + 131073) and the level is indexed densely with wrapped strides, which mirres_gridenc_layout and its
+    kernels restate and tests/gridenc_refs.py, the restatement of that loop, holds; density_refs.layout multiplies in Python integers and calls the level hashed.  Which
+    levels those are is worked out here in Python integers, not read from either layout."""
+    from mirres_restir_nerf_mesh_amd import encoding
+    import gridenc_refs as GR
+    total, want = _want(desired)
+    pls = np.exp2(np.log2(desired / 16) / 15)
+    g, m = encoding.gridenc_layout(per_level_scale=pls)
+    got = _levels(g)
+    assert m == total and g.num_levels == 16 and got[0] == want[0] and got[1] == want[1] and got[3] == want[3]
+    sizes = np.diff(want[0]).tolist()
+    over = [l for l in range(16) if any((want[1][l] + 1) ** k <= sizes[l] and (want[1][l] + 1) ** (k + 1) >= 2 ** 32 for k in (1, 2))]
+    assert [got[2][l] for l in range(16) if l not in over] == [want[2][l] for l in range(16) if l not in over]
+    differ = [l for l in range(16) if got[2][l] != want[2][l]]                      # an overflowed product matters only where what is left of it is below the size
+    assert differ == wrapped and set(differ) <= set(over) and all(want[2][l] and not got[2][l] for l in differ)
+    assert got[2] == GR.layout(pls=pls)["hashed"].tolist()
+
+
+def test_the_largest_layout_fits_the_32_bit_offsets():
+    """Both entries refuse a table of more than 2^31 - 1 entries, whose offsets would not fit an int.  Their own argument limits (16 levels, log2_hashmap_size <= 26)
+    cap a table at 16 * 2^26 = 2^30 entries, so no accepted argument list reaches the refusal; what can be held is that the largest one comes out exact."""
+    from mirres_restir_nerf_mesh_amd import stage0, encoding
+    sizes = [min(2 ** 26, (10000 + 1) ** 3)] * 16                                  # per_level_scale 1: every level at the base resolution
+    assert sizes == [2 ** 26] * 16 and sum(sizes) == 2 ** 30 < 2 ** 31 - 1
+    g, m = encoding.gridenc_layout(per_level_scale=1.0, base_resolution=10000, log2_hashmap_size=26)
+    assert m == 2 ** 30 and [g.offsets[i] for i in range(17)] == [i * 2 ** 26 for i in range(17)] and all(g.hashed[i] for i in range(16))
+    net, n = stage0.density_layout(1.0, base_resolution=10000, log2_hashmap_size=26, desired_resolution=10000.0)
+    assert n == 2 ** 30 and [net.offsets[i] for i in range(17)] == [i * 2 ** 26 for i in range(17)] and all(net.hashed[i] for i in range(16))
+
+
 def test_affine_vertex_values_are_reproduced_at_the_half_cell_offset():
     """Not drawn from any code: trilinear interpolation reproduces an affine function exactly, so with a * v + b stored at the integer vertex v of a dense level the
     encoding of a point is a * (u * scale + 0.5) + b.  A wrong half-cell offset shifts it, a wrong corner order or stride permutes the axes' coefficients."""
