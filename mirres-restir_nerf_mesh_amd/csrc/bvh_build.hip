@@ -4,7 +4,7 @@
 //   * scene extent by wave reduction + order-preserving atomics instead of 6 host-synchronising torch reductions;
 //   * device-wide stable radix sort (k_rs_*: multi-workgroup, wave64 digit matching) instead of the single-256-thread-block sort
 //     (lbvh_single_radixsort.slang, hard-coded 32-wide subgroups) — same stable ascending order;
-//   * one-launch bottom-up refit with agent-scope arrival counters instead of tree_height launches + a host sync
+//   * a refit without arrival counters (refit_boxes: every node's box is a range query on a union pyramid) instead of tree_height launches + a host sync
 //     (fmin/fmax unions are exact and order independent, so the boxes are bit-identical);
 //   * a packing pass that emits the 64-byte two-child traversal records used by bvh_trace.hip.
 #include "engine.hpp"
@@ -31,6 +31,20 @@ int check_hip(hipError_t e, const char* what) {
 
 MR_DEV uint32_t f2ord(float f) { uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 MR_DEV float ord2f(uint32_t u) { uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; return __uint_as_float(b); }
+
+// ---- boxes: float[6] = (min xyz, max xyz). The empty box, the union (fmin / fmax: exact and order-free, so a box does not depend on who united it in which
+// order), half the surface area, and the centre along an axis (the reference's own expression, k_morton) as a float or as an order-preserving key.
+MR_DEV void box_clear(float* b) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { b[k] = INFINITY; b[3 + k] = -INFINITY; }
+}
+MR_DEV void box_grow(float* b, const float* __restrict__ o) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { b[k] = fminf(b[k], o[k]); b[3 + k] = fmaxf(b[3 + k], o[3 + k]); }
+}
+MR_DEV float box_half_area(const float* b) { const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2]; return dx * dy + dy * dz + dz * dx; }
+MR_DEV float box_centre(const float* b, int a) { return b[a] + 0.5f * (b[3 + a] - b[a]); }
+MR_DEV uint32_t box_ckey(const float* b, int a) { return f2ord(box_centre(b, a)); }
 
 MR_DEV float wave_min(float v) {
 #pragma unroll
@@ -191,61 +205,65 @@ static void radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* tmp_k
     }
 }
 
-// delta / determineRange / findSplit (lbvh_hierarchy.slang:40-109)
-MR_DEV int delta(int i, uint32_t codeI, int j, int n, const uint32_t* __restrict__ codes) {
+// Karras' internal node g over n sorted keys: delta / determineRange / findSplit (lbvh_hierarchy.slang:40-109), for the reference's 32-bit Morton codes and
+// for the private hierarchy's 64-bit keys. Equal keys are told apart by position: the key's width + the common prefix of the two positions.
+MR_DEV int key_clz(uint32_t x) { return __clz(x); }
+MR_DEV int key_clz(unsigned long long x) { return __clzll(x); }
+template <typename K>
+MR_DEV int delta(int i, K ki, int j, int n, const K* __restrict__ keys) {
     if (j < 0 || j > n - 1) return -1;
-    uint32_t codeJ = codes[j];
-    if (codeI == codeJ) return 32 + __clz((uint32_t)i ^ (uint32_t)j);  // 32 + 31 - msb ; i != j here
-    return __clz(codeI ^ codeJ);                                         // 31 - msb
+    const K kj = keys[j];
+    if (ki == kj) return 8 * (int)sizeof(K) + __clz((uint32_t)i ^ (uint32_t)j);   // i != j here
+    return key_clz(ki ^ kj);
+}
+struct KarrasNode { int first, last, cA, cB; };      // the sorted leaves [first, last] below the node; its children (node ids: leaf p is node n - 1 + p)
+template <typename K>
+MR_DEV KarrasNode karras_node(int g, int n, const K* __restrict__ keys) {
+    const K key = keys[g];
+    const int dL = delta(g, key, g - 1, n, keys), dR = delta(g, key, g + 1, n, keys);
+    const int d = (dR >= dL) ? 1 : -1;
+    const int dMin = min(dL, dR);
+    int lMax = 2;
+    while (delta(g, key, g + lMax * d, n, keys) > dMin) lMax <<= 1;
+    int l = 0;
+    for (int t = lMax >> 1; t > 0; t >>= 1)
+        if (delta(g, key, g + (l + t) * d, n, keys) > dMin) l += t;
+    const int j = g + l * d;
+    KarrasNode N;
+    N.first = min(g, j); N.last = max(g, j);
+    const K firstKey = keys[N.first];
+    const int common = delta(N.first, firstKey, N.last, n, keys);
+    int split = N.first, stride = N.last - N.first;
+    do {
+        stride = (stride + 1) >> 1;
+        const int ns = split + stride;
+        if (ns < N.last && delta(N.first, firstKey, ns, n, keys) > common) split = ns;
+    } while (stride > 1);
+    const int LEAF = n - 1;
+    N.cA = (split == N.first) ? LEAF + split : split;
+    N.cB = (split + 1 == N.last) ? LEAF + split + 1 : split + 1;
+    return N;
 }
 
-// hierarchy (lbvh_hierarchy.slang:111-245)
+// hierarchy (lbvh_hierarchy.slang:111-245): the leaf entries, and per internal node its children and its leaf range (the boxes: refit_boxes)
 __global__ void __launch_bounds__(256) k_hierarchy(int T, const uint32_t* __restrict__ codes, const uint32_t* __restrict__ elem,
                                                    const float* __restrict__ ele, int32_t* __restrict__ info, float* __restrict__ aabb,
-                                                   int32_t* __restrict__ parent, uint32_t* __restrict__ flags, int32_t* __restrict__ sorted_out) {
+                                                   uint32_t* __restrict__ range, int32_t* __restrict__ sorted_out) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= T) return;
-    const int LEAF = T - 1;
     {
         uint32_t e = elem[g];
-        size_t n = (size_t)LEAF + g;
+        size_t n = (size_t)(T - 1) + g;
         info[3 * n] = 0; info[3 * n + 1] = 0; info[3 * n + 2] = (int32_t)e;
 #pragma unroll
         for (int k = 0; k < 6; k++) aabb[6 * n + k] = ele[6 * (size_t)e + k];
         if (sorted_out) { sorted_out[2 * g] = (int32_t)codes[g]; sorted_out[2 * g + 1] = (int32_t)e; }
     }
     if (g < T - 1) {
-        uint32_t code = codes[g];
-        int dL = delta(g, code, g - 1, T, codes), dR = delta(g, code, g + 1, T, codes);
-        int d = (dR >= dL) ? 1 : -1;
-        int dMin = min(dL, dR);
-        int lMax = 2;
-        while (delta(g, code, g + lMax * d, T, codes) > dMin) lMax <<= 1;
-        int l = 0;
-        for (int t = lMax >> 1; t > 0; t >>= 1)
-            if (delta(g, code, g + (l + t) * d, T, codes) > dMin) l += t;
-        int j = g + l * d;
-        int first = min(g, j), last = max(g, j);
-        uint32_t firstCode = codes[first];
-        int common = delta(first, firstCode, last, T, codes);
-        int split = first, stride = last - first;
-        do {
-            stride = (stride + 1) >> 1;
-            int ns = split + stride;
-            if (ns < last) {
-                int sp = delta(first, firstCode, ns, T, codes);
-                if (sp > common) split = ns;
-            }
-        } while (stride > 1);
-        int cA = (split == first) ? LEAF + split : split;
-        int cB = (split + 1 == last) ? LEAF + split + 1 : split + 1;
-        info[3 * (size_t)g] = cA; info[3 * (size_t)g + 1] = cB; info[3 * (size_t)g + 2] = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { aabb[6 * (size_t)g + k] = 1e9f; aabb[6 * (size_t)g + 3 + k] = -1e9f; }
-        parent[cA] = g; parent[cB] = g;
-        flags[2 * (size_t)g] = (uint32_t)first; flags[2 * (size_t)g + 1] = (uint32_t)last;
+        const KarrasNode N = karras_node(g, T, codes);
+        info[3 * (size_t)g] = N.cA; info[3 * (size_t)g + 1] = N.cB; info[3 * (size_t)g + 2] = 0;
+        range[2 * (size_t)g] = (uint32_t)N.first; range[2 * (size_t)g + 1] = (uint32_t)N.last;
     }
-    if (g == 0) parent[0] = 0;
 }
 
 // Refit: same boxes as get_bbox x tree_height + set_root (lbvh_bounding_boxes.slang:151-389). An LBVH node covers a contiguous range
@@ -257,12 +275,9 @@ __global__ void __launch_bounds__(256) k_refit_level(int n_src, const float* __r
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int n_dst = (n_src + 63) >> 6;
     if (e >= n_dst) return;
-    float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    float b[6]; box_clear(b);
     const int i1 = min(64 * e + 64, n_src);
-    for (int i = 64 * e; i < i1; i++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { b[k] = fminf(b[k], src[6 * (size_t)i + k]); b[3 + k] = fmaxf(b[3 + k], src[6 * (size_t)i + 3 + k]); }
-    }
+    for (int i = 64 * e; i < i1; i++) box_grow(b, src + 6 * (size_t)i);
 #pragma unroll
     for (int k = 0; k < 6; k++) dst[6 * (size_t)e + k] = b[k];
 }
@@ -271,13 +286,10 @@ __global__ void __launch_bounds__(256) k_refit_ranges(int T, const uint32_t* __r
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= T - 1) return;
     uint32_t lo = range[2 * (size_t)g], hi = range[2 * (size_t)g + 1] + 1u;   // [lo, hi) at the current level
-    float b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    float b[6]; box_clear(b);
     for (int l = 0; l < Lv.n; l++) {
         const float* __restrict__ A = Lv.a[l];
-        auto take = [&](uint32_t i) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) { b[k] = fminf(b[k], A[6 * (size_t)i + k]); b[3 + k] = fmaxf(b[3 + k], A[6 * (size_t)i + 3 + k]); }
-        };
+        auto take = [&](uint32_t i) { box_grow(b, A + 6 * (size_t)i); };
         while (lo < hi && (lo & 63u)) take(lo++);
         while (lo < hi && (hi & 63u)) take(--hi);
         if (lo >= hi) break;
@@ -287,9 +299,29 @@ __global__ void __launch_bounds__(256) k_refit_ranges(int T, const uint32_t* __r
 #pragma unroll
     for (int k = 0; k < 6; k++) aabb[6 * (size_t)g + k] = b[k];
 }
+// the boxes of the T - 1 internal nodes into `aabb`, from the T sorted leaf boxes `leaf` and the nodes' ranges; `pyramid` = mirres_bvh::lvl
+static void refit_boxes(int T, const float* leaf, const uint32_t* range, float* pyramid, float* aabb, hipStream_t s) {
+    const int blk = 256;
+    RefitLevels Lv; Lv.n = 1; Lv.a[0] = leaf;
+    int n = T;
+    while (n > 64 && Lv.n < 5) {
+        const int nd = (n + 63) >> 6;
+        k_refit_level<<<grid_for(nd, blk), blk, 0, s>>>(n, Lv.a[Lv.n - 1], pyramid);
+        Lv.a[Lv.n++] = pyramid; pyramid += 6 * (size_t)nd; n = nd;
+    }
+    k_refit_ranges<<<grid_for(T, blk), blk, 0, s>>>(T, range, Lv, aabb);
+}
 
-// Pack the traversal layout: 64-byte two-child records + per-leaf triangle records (v0, e1, e2 pre-subtracted:
-// the same fp32 subtraction triangle_hit performs, helperDi.slang:175-176).
+// The triangle of a leaf record (TriRec, LeafRec): v0, e1, e2 pre-subtracted — the same fp32 subtraction triangle_hit performs, helperDi.slang:175-176.
+template <typename Rec>
+MR_DEV void tri_record(Rec& r, const float* __restrict__ vert, const int32_t* __restrict__ tri, int prim) {
+    const int32_t* ti = tri + 3 * (size_t)prim;
+    v3 a = ld3(vert, ti[0]), b = ld3(vert, ti[1]), c = ld3(vert, ti[2]);
+    v3 e1 = b - a, e2 = c - a;
+    r.v0[0] = a.x; r.v0[1] = a.y; r.v0[2] = a.z; r.e1[0] = e1.x; r.e1[1] = e1.y; r.e1[2] = e1.z; r.e2[0] = e2.x; r.e2[1] = e2.y; r.e2[2] = e2.z;
+    r.prim = prim;
+}
+// Pack the traversal layout: 64-byte two-child records + per-leaf triangle records.
 __global__ void __launch_bounds__(256) k_pack(int T, const int32_t* __restrict__ info, const float* __restrict__ aabb,
                                               const float* __restrict__ vert, const int32_t* __restrict__ tri, WideNode* __restrict__ nodes,
                                               TriRec* __restrict__ tris, float* __restrict__ root_box) {
@@ -297,13 +329,9 @@ __global__ void __launch_bounds__(256) k_pack(int T, const int32_t* __restrict__
     if (g >= T) return;
     const int LEAF = T - 1;
     {
-        int prim = info[3 * ((size_t)LEAF + g) + 2];
-        const int32_t* ti = tri + 3 * (size_t)prim;
-        v3 a = ld3(vert, ti[0]), b = ld3(vert, ti[1]), c = ld3(vert, ti[2]);
-        v3 e1 = b - a, e2 = c - a;
         TriRec r;
-        r.v0[0] = a.x; r.v0[1] = a.y; r.v0[2] = a.z; r.e1[0] = e1.x; r.e1[1] = e1.y; r.e1[2] = e1.z; r.e2[0] = e2.x; r.e2[1] = e2.y; r.e2[2] = e2.z;
-        r.prim = prim; r.pad[0] = 0; r.pad[1] = 0;
+        tri_record(r, vert, tri, info[3 * ((size_t)LEAF + g) + 2]);
+        r.pad[0] = 0; r.pad[1] = 0;
         tris[g] = r;
     }
     if (g < T - 1) {
@@ -339,16 +367,11 @@ __global__ void __launch_bounds__(256) k_pack4q(int T, const int32_t* __restrict
     if (g >= T) return;
     const int LEAF = T - 1;
     {
-        const int prim = rinfo[3 * ((size_t)LEAF + g) + 2];
-        const int32_t* ti = tri + 3 * (size_t)prim;
-        v3 a = ld3(vert, ti[0]), b = ld3(vert, ti[1]), c = ld3(vert, ti[2]);
-        v3 e1 = b - a, e2 = c - a;
         const float* bx = raabb + 6 * ((size_t)LEAF + g);
         LeafRec r;
-        r.v0[0] = a.x; r.v0[1] = a.y; r.v0[2] = a.z; r.e1[0] = e1.x; r.e1[1] = e1.y; r.e1[2] = e1.z; r.e2[0] = e2.x; r.e2[1] = e2.y; r.e2[2] = e2.z;
+        tri_record(r, vert, tri, rinfo[3 * ((size_t)LEAF + g) + 2]);
 #pragma unroll
         for (int k = 0; k < 3; k++) { r.lo[k] = bx[k]; r.hi[k] = bx[3 + k]; }
-        r.prim = prim;
         leaves[g] = r;
         if (g == 0) {   // leaves[T]: the "null leaf" every unused child slot refers to — an inverted box no ray passes, so the traversal kernels need no
                         // test for unused slots (their decoded boxes fail by themselves; should one ever pass, this record's exact test rejects it)
@@ -368,9 +391,7 @@ __global__ void __launch_bounds__(256) k_pack4q(int T, const int32_t* __restrict
         int pick = -1; float best = -1.f;
         for (int k = 0; k < nc; k++) {
             if (c[k] >= LEAF) continue;
-            const float* b = aabb + 6 * (size_t)c[k];
-            const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
-            const float area = dx * dy + dy * dz + dz * dx;
+            const float area = box_half_area(aabb + 6 * (size_t)c[k]);
             if (area > best) { best = area; pick = k; }
         }
         if (pick < 0) break;
@@ -455,39 +476,14 @@ __global__ void __launch_bounds__(256) k_emc_leaves(int T, const uint32_t* __res
 #pragma unroll
     for (int k = 0; k < 6; k++) paabb[6 * n + k] = aabb[6 * ((size_t)(T - 1) + slot) + k];
 }
-MR_DEV int delta64(int i, unsigned long long ki, int j, int n, const unsigned long long* __restrict__ keys) {
-    if (j < 0 || j > n - 1) return -1;
-    const unsigned long long kj = keys[j];
-    if (ki == kj) return 64 + __clz((uint32_t)i ^ (uint32_t)j);
-    return __clzll(ki ^ kj);
-}
+// the private hierarchy's internal nodes; `parent` (the root's: -1) is what k_sah_clusters finds the cluster roots with
 __global__ void __launch_bounds__(256) k_hierarchy64(int T, const unsigned long long* __restrict__ keys, int32_t* __restrict__ info, uint32_t* __restrict__ range, int32_t* __restrict__ parent) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= T - 1) return;
-    const int LEAF = T - 1;
-    const unsigned long long key = keys[g];
-    const int dL = delta64(g, key, g - 1, T, keys), dR = delta64(g, key, g + 1, T, keys);
-    const int d = (dR >= dL) ? 1 : -1;
-    const int dMin = min(dL, dR);
-    int lMax = 2;
-    while (delta64(g, key, g + lMax * d, T, keys) > dMin) lMax <<= 1;
-    int l = 0;
-    for (int t = lMax >> 1; t > 0; t >>= 1)
-        if (delta64(g, key, g + (l + t) * d, T, keys) > dMin) l += t;
-    const int j = g + l * d;
-    const int first = min(g, j), last = max(g, j);
-    const unsigned long long firstKey = keys[first];
-    const int common = delta64(first, firstKey, last, T, keys);
-    int split = first, stride = last - first;
-    do {
-        stride = (stride + 1) >> 1;
-        const int ns = split + stride;
-        if (ns < last && delta64(first, firstKey, ns, T, keys) > common) split = ns;
-    } while (stride > 1);
-    const int cA = (split == first) ? LEAF + split : split, cB = (split + 1 == last) ? LEAF + split + 1 : split + 1;
-    info[3 * (size_t)g] = cA; info[3 * (size_t)g + 1] = cB; info[3 * (size_t)g + 2] = 0;
-    range[2 * (size_t)g] = (uint32_t)first; range[2 * (size_t)g + 1] = (uint32_t)last;
-    parent[cA] = g; parent[cB] = g;
+    const KarrasNode N = karras_node(g, T, keys);
+    info[3 * (size_t)g] = N.cA; info[3 * (size_t)g + 1] = N.cB; info[3 * (size_t)g + 2] = 0;
+    range[2 * (size_t)g] = (uint32_t)N.first; range[2 * (size_t)g + 1] = (uint32_t)N.last;
+    parent[N.cA] = g; parent[N.cB] = g;
     if (g == 0) parent[0] = -1;
 }
 
@@ -502,32 +498,41 @@ __global__ void __launch_bounds__(256) k_hierarchy64(int T, const unsigned long 
 // extended-Morton tree stays as it is (k_sah_install checks). Which ids the atomics hand out varies from run to run; the topology does not, and no result depends on either.
 #define MR_SAH_BINS 8
 #define MR_SAH_MAXC 65536
-struct SahNode { uint32_t count, cb[6], minidx; int32_t axis, bin; float lo, scale; int32_t cl, cr, iid, alias; float box[6]; };      // 24 words
-struct SahBin { uint32_t count, box[6]; };
+// What a node knows of its items before it is split: {count, centroid bounds x 6, smallest item index}, order-preserving bits (f2ord) under integer atomics —
+// in the node itself, or in a workgroup's LDS copy that is merged into it. Empty = count 0, bounds inverted.
+struct SahAcc { uint32_t count, cb[6], minidx; };
+struct SahNode { SahAcc acc; int32_t axis, bin; float lo, scale; int32_t cl, cr, iid, alias; float box[6]; };
+struct SahBin { uint32_t count, box[6]; };      // one of a node's 3 x MR_SAH_BINS bins: items and the union of their boxes, same encoding; empty likewise
+static_assert(sizeof(SahAcc) == 32 && sizeof(SahNode) == 88 && sizeof(SahBin) == 28, "device layout of the SAH-top scratch: 8, 22 and 7 words");
+MR_DEV void sah_acc_clear(SahAcc& A) { A.count = 0; A.minidx = 0xffffffffu; for (int a = 0; a < 3; a++) { A.cb[a] = 0xffffffffu; A.cb[3 + a] = 0u; } }
+MR_DEV void sah_acc_add(SahAcc& A, const float* __restrict__ bx, uint32_t item) {      // one item with box bx
+    atomicAdd(&A.count, 1u); atomicMin(&A.minidx, item);
+#pragma unroll
+    for (int a = 0; a < 3; a++) { const uint32_t c = box_ckey(bx, a); atomicMin(&A.cb[a], c); atomicMax(&A.cb[3 + a], c); }
+}
+MR_DEV void sah_acc_merge(SahAcc& A, const SahAcc& part) {                              // a workgroup's share: one atomic per word instead of one per item
+    atomicAdd(&A.count, part.count); atomicMin(&A.minidx, part.minidx);
+    for (int a = 0; a < 3; a++) { atomicMin(&A.cb[a], part.cb[a]); atomicMax(&A.cb[3 + a], part.cb[3 + a]); }
+}
+__host__ __device__ inline void sah_bin_clear(SahBin& B) { B.count = 0; for (int q = 0; q < 3; q++) { B.box[q] = 0xffffffffu; B.box[3 + q] = 0u; } }
 struct SahState { uint32_t n_items, n_top, n_nodes, n_internal, n_resolved, fail, first[MR_SAH_LEVELS + 3]; };
 MR_DEV int node_prefix(int n, int T, const unsigned long long* __restrict__ key64, const uint32_t* __restrict__ range) {
     if (n >= T - 1) return 128;                                  // a leaf
     const unsigned long long a = key64[range[2 * (size_t)n]], b = key64[range[2 * (size_t)n + 1]];
     return a == b ? 64 : __clzll(a ^ b);
 }
-MR_DEV void sah_accumulate(SahNode* nodes, int k, const float* __restrict__ bx, uint32_t item) {
-    SahNode& N = nodes[k];
-    atomicAdd(&N.count, 1u); atomicMin(&N.minidx, item);
-#pragma unroll
-    for (int a = 0; a < 3; a++) { const uint32_t c = f2ord(bx[a] + 0.5f * (bx[3 + a] - bx[a])); atomicMin(&N.cb[a], c); atomicMax(&N.cb[3 + a], c); }
-}
 __global__ void __launch_bounds__(256) k_sah_reset(SahState* st, SahNode* nodes, int n_nodes) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) { st->n_items = 0; st->n_top = 1; st->n_nodes = 1; st->n_internal = 1; st->n_resolved = 0; st->fail = 0; st->first[0] = 0; st->first[1] = 1; st->first[2] = 1; }
-    if (i < n_nodes) { SahNode z; z.count = 0; z.minidx = 0xffffffffu; for (int a = 0; a < 3; a++) { z.cb[a] = 0xffffffffu; z.cb[3 + a] = 0u; } z.axis = -1; z.bin = 0; z.lo = 0.f; z.scale = 0.f; z.cl = z.cr = -1; z.iid = -1; z.alias = -1;
+    if (i < n_nodes) { SahNode z; sah_acc_clear(z.acc); z.axis = -1; z.bin = 0; z.lo = 0.f; z.scale = 0.f; z.cl = z.cr = -1; z.iid = -1; z.alias = -1;
                        for (int a = 0; a < 6; a++) z.box[a] = 0.f; nodes[i] = z; }
 }
 __global__ void __launch_bounds__(256) k_sah_clusters(int T, const unsigned long long* __restrict__ key64, const uint32_t* __restrict__ range, const int32_t* __restrict__ parent,
                                                       const float* __restrict__ paabb, SahState* st, SahNode* nodes, int32_t* __restrict__ iref, int32_t* __restrict__ inode,
                                                       int32_t* __restrict__ top_ids) {
     // the root's item count and centroid bounds: one set of atomics per workgroup (every cluster would otherwise hit the same eight words)
-    __shared__ uint32_t s_count, s_min, s_cb[6];
-    if (threadIdx.x == 0) { s_count = 0; s_min = 0xffffffffu; for (int a = 0; a < 3; a++) { s_cb[a] = 0xffffffffu; s_cb[3 + a] = 0u; } }
+    __shared__ SahAcc s_acc;
+    if (threadIdx.x == 0) sah_acc_clear(s_acc);
     __syncthreads();
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < 2 * T - 1; n += gridDim.x * blockDim.x) {
         const int cp = node_prefix(n, T, key64, range);
@@ -537,10 +542,7 @@ __global__ void __launch_bounds__(256) k_sah_clusters(int T, const unsigned long
             const uint32_t i = atomicAdd(&st->n_items, 1u);
             if (i < MR_SAH_MAXC) {
                 iref[i] = n; inode[i] = 0;
-                const float* bx = paabb + 6 * (size_t)n;
-                atomicAdd(&s_count, 1u); atomicMin(&s_min, i);
-#pragma unroll
-                for (int a = 0; a < 3; a++) { const uint32_t c = f2ord(bx[a] + 0.5f * (bx[3 + a] - bx[a])); atomicMin(&s_cb[a], c); atomicMax(&s_cb[3 + a], c); }
+                sah_acc_add(s_acc, paabb + 6 * (size_t)n, i);
             } else st->fail = 1;
         } else if (cp < MR_SAH_PREFIX) {                             // an internal node above the cut: its id is reused
             if (n == 0) top_ids[0] = 0; else { const uint32_t j = atomicAdd(&st->n_top, 1u); if (j < MR_SAH_MAXC) top_ids[j] = n; else st->fail = 1; }
@@ -548,10 +550,7 @@ __global__ void __launch_bounds__(256) k_sah_clusters(int T, const unsigned long
         if (n == 0) { for (int a = 0; a < 6; a++) nodes[0].box[a] = paabb[a]; nodes[0].iid = 0; }
     }
     __syncthreads();
-    if (threadIdx.x == 0 && s_count) {
-        atomicAdd(&nodes[0].count, s_count); atomicMin(&nodes[0].minidx, s_min);
-        for (int a = 0; a < 3; a++) { atomicMin(&nodes[0].cb[a], s_cb[a]); atomicMax(&nodes[0].cb[3 + a], s_cb[3 + a]); }
-    }
+    if (threadIdx.x == 0 && s_acc.count) sah_acc_merge(nodes[0].acc, s_acc);
 }
 MR_DEV int sah_bin_of(float c, float lo, float scale) { const int b = (int)((c - lo) * scale); return b < 0 ? 0 : (b > MR_SAH_BINS - 1 ? MR_SAH_BINS - 1 : b); }
 // Levels 0 .. MR_SAH_LDS_LEVELS - 1 have at most 32 nodes (64 children): thousands of items would hammer the same few words with device atomics (the first version
@@ -566,13 +565,13 @@ MR_DEV void sah_bin_item(uint32_t i, int f0, const SahNode* __restrict__ nodes, 
     const int k = inode[i];
     if (k < f0) return;                                      // resolved (-1) — every live item sits in a node of the current level
     const SahNode& N = nodes[k];
-    if (N.count < 2) return;
+    if (N.acc.count < 2) return;
     const float* bx = paabb + 6 * (size_t)iref[i];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const float lo = ord2f(N.cb[a]), hi = ord2f(N.cb[3 + a]);
+        const float lo = ord2f(N.acc.cb[a]), hi = ord2f(N.acc.cb[3 + a]);
         if (!(hi > lo)) continue;
-        const int b = sah_bin_of(bx[a] + 0.5f * (bx[3 + a] - bx[a]), lo, (float)MR_SAH_BINS / (hi - lo));
+        const int b = sah_bin_of(box_centre(bx, a), lo, (float)MR_SAH_BINS / (hi - lo));
         SahBin& B = bins[((size_t)(k - f0) * 3 + a) * MR_SAH_BINS + b];
         atomicAdd(&B.count, 1u);
 #pragma unroll
@@ -586,7 +585,7 @@ __global__ void __launch_bounds__(256) k_sah_bin(int level, const SahState* st, 
     const uint32_t C = st->n_items < MR_SAH_MAXC ? st->n_items : MR_SAH_MAXC;
     const int f0 = (int)st->first[level];
     if (LDS) {
-        for (int j = threadIdx.x; j < MR_SAH_LDS_NODES * 3 * MR_SAH_BINS; j += blockDim.x) { sb[j].count = 0; for (int q = 0; q < 3; q++) { sb[j].box[q] = 0xffffffffu; sb[j].box[3 + q] = 0u; } }
+        for (int j = threadIdx.x; j < MR_SAH_LDS_NODES * 3 * MR_SAH_BINS; j += blockDim.x) sah_bin_clear(sb[j]);
         __syncthreads();
     }
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < C; i += gridDim.x * blockDim.x) sah_bin_item(i, f0, nodes, iref, inode, paabb, LDS ? sb : bins);
@@ -601,46 +600,45 @@ __global__ void __launch_bounds__(256) k_sah_bin(int level, const SahState* st, 
 }
 MR_DEV void sah_split_node(int k, int level, int f0, SahState* st, SahNode* nodes, SahBin* __restrict__ bins) {
     SahNode& N = nodes[k];
-    if (N.count < 2) return;                                     // a single item: resolved by the assign step (count 0 cannot happen: both sides of a split are non-empty)
+    if (N.acc.count < 2) return;                                 // a single item: resolved by the assign step (count 0 cannot happen: both sides of a split are non-empty)
     if (level >= MR_SAH_LEVELS) { st->fail = 1; return; }
     float best = 3.0e38f; int best_axis = -1, best_bin = 0; uint32_t best_nl = 0; float lbox[6], rbox[6];
+    auto grow = [](float* acc, const SahBin& B) { float bb[6]; for (int q = 0; q < 6; q++) bb[q] = ord2f(B.box[q]); box_grow(acc, bb); };
     for (int a = 0; a < 3; a++) {
         SahBin* B = bins + ((size_t)(k - f0) * 3 + a) * MR_SAH_BINS;
-        const float lo = ord2f(N.cb[a]), hi = ord2f(N.cb[3 + a]);
+        const float lo = ord2f(N.acc.cb[a]), hi = ord2f(N.acc.cb[3 + a]);
         if (hi > lo) {
             float racc[MR_SAH_BINS][6]; uint32_t rcnt[MR_SAH_BINS];
-            float acc[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY}; uint32_t c = 0;
+            float acc[6]; box_clear(acc); uint32_t c = 0;
             for (int b = MR_SAH_BINS - 1; b >= 0; b--) {
-                if (B[b].count) { for (int q = 0; q < 3; q++) { acc[q] = fminf(acc[q], ord2f(B[b].box[q])); acc[3 + q] = fmaxf(acc[3 + q], ord2f(B[b].box[3 + q])); } c += B[b].count; }
+                if (B[b].count) { grow(acc, B[b]); c += B[b].count; }
                 for (int q = 0; q < 6; q++) racc[b][q] = acc[q]; rcnt[b] = c;
             }
-            float l[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY}; uint32_t nl = 0;
+            float l[6]; box_clear(l); uint32_t nl = 0;
             for (int b = 0; b + 1 < MR_SAH_BINS; b++) {
-                if (B[b].count) { for (int q = 0; q < 3; q++) { l[q] = fminf(l[q], ord2f(B[b].box[q])); l[3 + q] = fmaxf(l[3 + q], ord2f(B[b].box[3 + q])); } nl += B[b].count; }
+                if (B[b].count) { grow(l, B[b]); nl += B[b].count; }
                 const uint32_t nr = rcnt[b + 1];
                 if (!nl || !nr) continue;
                 const float* r = racc[b + 1];
-                const float al = (l[3] - l[0]) * (l[4] - l[1]) + (l[4] - l[1]) * (l[5] - l[2]) + (l[5] - l[2]) * (l[3] - l[0]);
-                const float ar = (r[3] - r[0]) * (r[4] - r[1]) + (r[4] - r[1]) * (r[5] - r[2]) + (r[5] - r[2]) * (r[3] - r[0]);
-                const float cost = al * (float)nl + ar * (float)nr;
+                const float cost = box_half_area(l) * (float)nl + box_half_area(r) * (float)nr;
                 if (cost < best) { best = cost; best_axis = a; best_bin = b; best_nl = nl; for (int q = 0; q < 6; q++) { lbox[q] = l[q]; rbox[q] = r[q]; } }
             }
         }
-        for (int b = 0; b < MR_SAH_BINS; b++) { B[b].count = 0; for (int q = 0; q < 3; q++) { B[b].box[q] = 0xffffffffu; B[b].box[3 + q] = 0u; } }      // clean for the next level
+        for (int b = 0; b < MR_SAH_BINS; b++) sah_bin_clear(B[b]);      // clean for the next level
     }
     const uint32_t base = atomicAdd(&st->n_nodes, 2u);
     if (base + 2 > 2 * MR_SAH_MAXC) { st->fail = 1; return; }
     N.cl = (int)base; N.cr = (int)base + 1;
     if (best_axis >= 0) {
-        N.axis = best_axis; N.bin = best_bin; N.lo = ord2f(N.cb[best_axis]); N.scale = (float)MR_SAH_BINS / (ord2f(N.cb[3 + best_axis]) - N.lo);
+        N.axis = best_axis; N.bin = best_bin; N.lo = ord2f(N.acc.cb[best_axis]); N.scale = (float)MR_SAH_BINS / (ord2f(N.acc.cb[3 + best_axis]) - N.lo);
         for (int q = 0; q < 6; q++) { nodes[base].box[q] = lbox[q]; nodes[base + 1].box[q] = rbox[q]; }
         if (best_nl >= 2) nodes[base].iid = (int)atomicAdd(&st->n_internal, 1u);
-        if (N.count - best_nl >= 2) nodes[base + 1].iid = (int)atomicAdd(&st->n_internal, 1u);
+        if (N.acc.count - best_nl >= 2) nodes[base + 1].iid = (int)atomicAdd(&st->n_internal, 1u);
     } else {
         // all centroids coincide: peel off the item with the smallest index (the boxes of the two sides are formed by the assign step)
         N.axis = 3;
-        for (int q = 0; q < 3; q++) { nodes[base].box[q] = nodes[base + 1].box[q] = INFINITY; nodes[base].box[3 + q] = nodes[base + 1].box[3 + q] = -INFINITY; }
-        if (N.count - 1 >= 2) nodes[base + 1].iid = (int)atomicAdd(&st->n_internal, 1u);
+        box_clear(nodes[base].box); box_clear(nodes[base + 1].box);
+        if (N.acc.count - 1 >= 2) nodes[base + 1].iid = (int)atomicAdd(&st->n_internal, 1u);
     }
 }
 __global__ void __launch_bounds__(256) k_sah_split(int level, SahState* st, SahNode* nodes, SahBin* __restrict__ bins) {
@@ -656,26 +654,20 @@ MR_DEV void atomic_box_f(float* box, const float* bx) {   // float min / max by 
                        const unsigned int prev = atomicCAS(p, old, __float_as_uint(nv)); if (prev == old) break; old = prev; }
     }
 }
-// per-child accumulators of the assign step: {count, centroid bounds x 6, smallest item index} — in the nodes themselves, or in a workgroup's LDS copy
-struct SahAcc { uint32_t count, cb[6], minidx; };
+// lacc: the workgroup's LDS copy of the children's accumulators (from node c0 on), or NULL: straight into the nodes
 MR_DEV void sah_assign_item(uint32_t i, int f0, int c0, SahState* st, SahNode* nodes, const int32_t* __restrict__ iref, int32_t* __restrict__ inode, const float* __restrict__ paabb, SahAcc* lacc) {
     const int k = inode[i];
     if (k < f0) return;
     SahNode& N = nodes[k];
-    if (N.count == 1) { N.alias = iref[i]; inode[i] = -1; atomicAdd(&st->n_resolved, 1u); return; }
+    if (N.acc.count == 1) { N.alias = iref[i]; inode[i] = -1; atomicAdd(&st->n_resolved, 1u); return; }
     if (N.cl < 0) return;                                    // not split (failure flagged by the split step)
     const float* bx = paabb + 6 * (size_t)iref[i];
     int side;
-    if (N.axis == 3) side = (i == N.minidx) ? 0 : 1;
-    else side = sah_bin_of(bx[N.axis] + 0.5f * (bx[3 + N.axis] - bx[N.axis]), N.lo, N.scale) <= N.bin ? 0 : 1;
+    if (N.axis == 3) side = (i == N.acc.minidx) ? 0 : 1;
+    else side = sah_bin_of(box_centre(bx, N.axis), N.lo, N.scale) <= N.bin ? 0 : 1;
     const int c = side ? N.cr : N.cl;
     inode[i] = c;
-    if (lacc) {
-        SahAcc& A = lacc[c - c0];
-        atomicAdd(&A.count, 1u); atomicMin(&A.minidx, i);
-#pragma unroll
-        for (int a = 0; a < 3; a++) { const uint32_t cc = f2ord(bx[a] + 0.5f * (bx[3 + a] - bx[a])); atomicMin(&A.cb[a], cc); atomicMax(&A.cb[3 + a], cc); }
-    } else sah_accumulate(nodes, c, bx, i);
+    if (lacc) sah_acc_add(lacc[c - c0], bx, i); else sah_acc_add(nodes[c].acc, bx, i);
     if (N.axis == 3) atomic_box_f(nodes[c].box, bx);
 }
 template <bool LDS>
@@ -684,17 +676,14 @@ __global__ void __launch_bounds__(256) k_sah_assign(int level, SahState* st, Sah
     const uint32_t C = st->n_items < MR_SAH_MAXC ? st->n_items : MR_SAH_MAXC;
     const int f0 = (int)st->first[level], c0 = (int)st->first[level + 1];      // this level's nodes start at f0, their children at c0
     if (LDS) {
-        for (int j = threadIdx.x; j < 2 * MR_SAH_LDS_NODES; j += blockDim.x) { sa[j].count = 0; sa[j].minidx = 0xffffffffu; for (int q = 0; q < 3; q++) { sa[j].cb[q] = 0xffffffffu; sa[j].cb[3 + q] = 0u; } }
+        for (int j = threadIdx.x; j < 2 * MR_SAH_LDS_NODES; j += blockDim.x) sah_acc_clear(sa[j]);
         __syncthreads();
     }
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < C; i += gridDim.x * blockDim.x) sah_assign_item(i, f0, c0, st, nodes, iref, inode, paabb, LDS ? sa : nullptr);
     if (LDS) {
         __syncthreads();
         for (int j = threadIdx.x; j < 2 * MR_SAH_LDS_NODES; j += blockDim.x) {
-            if (!sa[j].count) continue;
-            SahNode& N = nodes[c0 + j];
-            atomicAdd(&N.count, sa[j].count); atomicMin(&N.minidx, sa[j].minidx);
-            for (int q = 0; q < 3; q++) { atomicMin(&N.cb[q], sa[j].cb[q]); atomicMax(&N.cb[3 + q], sa[j].cb[3 + q]); }
+            if (sa[j].count) sah_acc_merge(nodes[c0 + j].acc, sa[j]);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) st->first[level + 2] = st->n_nodes;      // no allocation runs concurrently with this kernel
@@ -724,11 +713,11 @@ __global__ void __launch_bounds__(256) k_sah_install(const SahState* st, const S
     const uint32_t n = st->n_nodes;
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         const SahNode& N = nodes[k];
-        if (N.count < 2) continue;
+        if (N.acc.count < 2) continue;
         const int id = top_ids[N.iid];
         const SahNode &L = nodes[N.cl], &R = nodes[N.cr];
-        pinfo[3 * (size_t)id] = L.count == 1 ? L.alias : top_ids[L.iid];
-        pinfo[3 * (size_t)id + 1] = R.count == 1 ? R.alias : top_ids[R.iid];
+        pinfo[3 * (size_t)id] = L.acc.count == 1 ? L.alias : top_ids[L.iid];
+        pinfo[3 * (size_t)id + 1] = R.acc.count == 1 ? R.alias : top_ids[R.iid];
         pinfo[3 * (size_t)id + 2] = 0;
 #pragma unroll
         for (int q = 0; q < 6; q++) paabb[6 * (size_t)id + q] = N.box[q];
@@ -786,7 +775,6 @@ __global__ void __launch_bounds__(256) k_sb_select(int T, const int32_t* __restr
     roots[atomicAdd(&st->n_roots, 1u)] = n;                     // disjoint subtrees of >= 3 leaves: fewer than T / 3 + 1 roots
 }
 MR_DEV int sb_ceil_log2(int x) { return x <= 1 ? 0 : 32 - __clz((uint32_t)(x - 1)); }
-MR_DEV float sb_area(const float* b) { const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2]; return dx * dy + dy * dz + dz * dx; }
 // segmented inclusive scan of the boxes in s_P along the positions: DIR = -1 prefix (from the segment's start), +1 suffix (from its end)
 template <int DIR>
 MR_DEV void sb_scan(float (*s_P)[MR_SB_MAX], const uint16_t* s_lo, const uint16_t* s_hi, int n, int maxlen) {
@@ -879,7 +867,7 @@ __global__ void __launch_bounds__(256) k_sb_rebuild(int T, int32_t* __restrict__
 #pragma unroll
             for (int k = 0; k < 6; k++) s_box[k][i] = bx[k];
 #pragma unroll
-            for (int a = 0; a < 3; a++) s_ckey[a][i] = f2ord(bx[a] + 0.5f * (bx[3 + a] - bx[a]));
+            for (int a = 0; a < 3; a++) s_ckey[a][i] = box_ckey(bx, a);
             s_lo[i] = 0; s_hi[i] = (uint16_t)n; s_par[i] = -1;
         }
         if (t == 0) { s_maxlen[0] = n; s_maxlen[1] = 1; }
@@ -902,7 +890,7 @@ __global__ void __launch_bounds__(256) k_sb_rebuild(int T, int32_t* __restrict__
                 for (int i = t; i < n; i += 256) { float b[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) b[k] = s_P[k][i];
-                    s_suf[i] = sb_area(b); }
+                    s_suf[i] = box_half_area(b); }
                 __syncthreads();
                 for (int i = t; i < n; i += 256) { const int j = s_ord[ob][a][i];
 #pragma unroll
@@ -915,7 +903,7 @@ __global__ void __launch_bounds__(256) k_sb_rebuild(int T, int32_t* __restrict__
                     float b[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) b[k] = s_P[k][i];
-                    const float cost = sb_area(b) * (float)(i - lo + 1) + s_suf[i + 1] * (float)(hi - 1 - i);      // >= 0, or NaN / inf on wild boxes: those sort last
+                    const float cost = box_half_area(b) * (float)(i - lo + 1) + s_suf[i + 1] * (float)(hi - 1 - i);      // >= 0, or NaN / inf on wild boxes: those sort last
                     atomicMin(&s_best[lo], ((unsigned long long)__float_as_uint(cost) << 32) | (unsigned long long)((uint32_t)a << 16 | (uint32_t)i));
                 }
                 __syncthreads();                                 // s_P: the prefix boxes of this axis stay until the next axis loads (after a == 2: until the decision below)
@@ -1044,14 +1032,7 @@ static int private_step1(mirres_bvh* b, int T, const float* aabb, hipStream_t s)
     radix_sort_pairs_u32(b->p_keys, b->p_vals, b->keys_in, b->vals_in, (uint32_t*)b->sort_tmp, T, s);      // keys_in / vals_in: idle halves of the first sort's ping-pong
     k_emc_leaves<<<grd, blk, 0, s>>>(T, b->p_keys, b->p_vals, b->keys_out, aabb, b->p_key64, b->p_info, b->p_aabb);
     k_hierarchy64<<<grd, blk, 0, s>>>(T, b->p_key64, b->p_info, b->p_range, b->p_parent);
-    RefitLevels Lv; Lv.n = 1; Lv.a[0] = b->p_aabb + 6 * (size_t)(T - 1);
-    int n = T; float* dst = b->lvl;                                                                          // the pyramid of the reference refit is done with
-    while (n > 64 && Lv.n < 5) {
-        const int nd = (n + 63) >> 6;
-        k_refit_level<<<grid_for(nd, blk), blk, 0, s>>>(n, Lv.a[Lv.n - 1], dst);
-        Lv.a[Lv.n++] = dst; dst += 6 * (size_t)nd; n = nd;
-    }
-    k_refit_ranges<<<grd, blk, 0, s>>>(T, b->p_range, Lv, b->p_aabb);
+    refit_boxes(T, b->p_aabb + 6 * (size_t)(T - 1), b->p_range, b->lvl, b->p_aabb, s);                    // the pyramid of the reference refit is done with
     MR_LAUNCH_CHECK("bvh_private_step1");
     return 0;
 }
@@ -1090,6 +1071,14 @@ static int private_sah_bottom(mirres_bvh* b, int T, hipStream_t s) {            
     MR_LAUNCH_CHECK("bvh_private_sah_bottom");
     return 0;
 }
+// The closing step of every build: the 4-wide layout of the shadow-ray / ordered closest-hit kernels, collapsed from the private hierarchy (b->private_level >= 1)
+// or from the reference LBVH (`info` / `aabb`, which always supply the leaf records), and its two breadth-first prefixes.
+static void finish_layout(mirres_bvh* b, const float* vert, const int32_t* tri, const int32_t* info, const float* aabb, hipStream_t s) {
+    const int T = b->T, blk = 256, grd = grid_for(T, blk);
+    if (b->private_level >= 1) k_pack4q<true><<<grd, blk, 0, s>>>(T, b->p_info, b->p_aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
+    else k_pack4q<false><<<grd, blk, 0, s>>>(T, info, aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
+    if (T - 1 >= 341 * 4) { k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top85q, 85); k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top341q, 341); }
+}
 
 extern "C" {
 
@@ -1102,57 +1091,65 @@ void mirres_default_config(mirres_config_t* c) {
     c->gather_radius = 30.f; c->max_bounce = 2; c->vis_near = 0.01f;
 }
 
+// Everything a handle holds for its whole life. Each allocation is recorded in mirres_bvh::owned as it is made, so mirres_bvh_destroy needs no list of its own
+// and a handle that stopped half-way here is freed like a complete one.
+#define MR_OWN(p, bytes) do { MR_HIP(hipMalloc(&(p), (bytes))); b->owned.push_back(p); } while (0)
+static int bvh_allocate(mirres_bvh* b) {
+    const size_t T = (size_t)b->max_tris;
+    MR_OWN(b->ele_aabb, sizeof(float) * 6 * T);
+    MR_OWN(b->extent, sizeof(uint32_t) * 8);
+    MR_OWN(b->keys_in, sizeof(uint32_t) * T); MR_OWN(b->keys_out, sizeof(uint32_t) * T);
+    MR_OWN(b->vals_in, sizeof(uint32_t) * T); MR_OWN(b->vals_out, sizeof(uint32_t) * T);
+    MR_OWN(b->flags, sizeof(uint32_t) * 2 * T);
+    MR_OWN(b->lvl, sizeof(float) * 6 * (T / 63 + 256));
+    MR_OWN(b->own_info, sizeof(int32_t) * 3 * (2 * T));
+    MR_OWN(b->own_aabb, sizeof(float) * 6 * (2 * T));
+    MR_OWN(b->nodes, sizeof(WideNode) * T);
+    MR_OWN(b->tris, sizeof(TriRec) * T);
+    MR_OWN(b->nodes4q, sizeof(Node4q) * T);
+    MR_OWN(b->leaves, sizeof(LeafRec) * (T + 1));      // + the null leaf
+    MR_OWN(b->p_keys, sizeof(uint32_t) * T); MR_OWN(b->p_vals, sizeof(uint32_t) * T);
+    MR_OWN(b->p_key64, sizeof(unsigned long long) * T);
+    MR_OWN(b->p_info, sizeof(int32_t) * 3 * (2 * T)); MR_OWN(b->p_aabb, sizeof(float) * 6 * (2 * T));
+    MR_OWN(b->p_range, sizeof(uint32_t) * 2 * T);
+    MR_OWN(b->p_parent, sizeof(int32_t) * 2 * T);
+    {   // scratch of the SAH top (k_sah_*): clusters, rebuilt nodes, one level's bins
+        const size_t C = MR_SAH_MAXC;
+        MR_OWN(b->sah_state, sizeof(SahState));
+        MR_OWN(b->sah_nodes, sizeof(SahNode) * 2 * C);
+        MR_OWN(b->sah_bins, sizeof(SahBin) * C * 3 * MR_SAH_BINS);
+        MR_OWN(b->sah_iref, sizeof(int32_t) * C); MR_OWN(b->sah_inode, sizeof(int32_t) * C); MR_OWN(b->sah_top, sizeof(int32_t) * C);
+        std::vector<SahBin> z(C * 3 * MR_SAH_BINS);
+        for (auto& e : z) sah_bin_clear(e);
+        MR_HIP(hipMemcpy(b->sah_bins, z.data(), sizeof(SahBin) * z.size(), hipMemcpyHostToDevice));      // every split leaves its bins clean again
+    }
+    MR_OWN(b->sb_state, 16); MR_OWN(b->sb_cnt, sizeof(uint32_t) * 2 * T); MR_OWN(b->sb_roots, sizeof(int32_t) * (T / 3 + 2));      // SAH bottom (k_sb_*)
+    MR_OWN(b->top85q, sizeof(Node4q) * 85);
+    MR_OWN(b->top341q, sizeof(Node4q) * 341);
+    MR_OWN(b->root_box, sizeof(float) * 8);
+    MR_OWN(b->work, sizeof(uint32_t) * MR_WSETS * MR_WSET);
+    b->sort_tmp_bytes = sizeof(uint32_t) * 256 * ((T + MR_RS_TILE - 1) / MR_RS_TILE + 1);     // (digit, tile) counters of the radix sort + the digit totals
+    MR_OWN(b->sort_tmp, b->sort_tmp_bytes);
+    MR_HIP(hipHostMalloc((void**)&b->err, 64, hipHostMallocMapped)); *b->err = 0u;
+    return MIRRES_OK;
+}
+#undef MR_OWN
+
 int mirres_bvh_create(mirres_bvh_t** out, int max_tris) {
     if (!out || max_tris < 2) { set_error("mirres_bvh_create: need max_tris >= 2"); return MIRRES_E_ARG; }
     mirres_bvh* b = new mirres_bvh();
     b->max_tris = max_tris;
-    size_t T = (size_t)max_tris;
-    MR_HIP(hipMalloc(&b->ele_aabb, sizeof(float) * 6 * T));
-    MR_HIP(hipMalloc(&b->extent, sizeof(uint32_t) * 8));
-    MR_HIP(hipMalloc(&b->keys_in, sizeof(uint32_t) * T)); MR_HIP(hipMalloc(&b->keys_out, sizeof(uint32_t) * T));
-    MR_HIP(hipMalloc(&b->vals_in, sizeof(uint32_t) * T)); MR_HIP(hipMalloc(&b->vals_out, sizeof(uint32_t) * T));
-    MR_HIP(hipMalloc(&b->parent, sizeof(int32_t) * (2 * T)));
-    MR_HIP(hipMalloc(&b->flags, sizeof(uint32_t) * 2 * (size_t)T));
-    MR_HIP(hipMalloc(&b->lvl, sizeof(float) * 6 * ((size_t)T / 63 + 256)));
-    MR_HIP(hipMalloc(&b->own_info, sizeof(int32_t) * 3 * (2 * T)));
-    MR_HIP(hipMalloc(&b->own_aabb, sizeof(float) * 6 * (2 * T)));
-    MR_HIP(hipMalloc(&b->nodes, sizeof(WideNode) * T));
-    MR_HIP(hipMalloc(&b->tris, sizeof(TriRec) * T));
-    MR_HIP(hipMalloc(&b->nodes4q, sizeof(Node4q) * T));
-    MR_HIP(hipMalloc(&b->leaves, sizeof(LeafRec) * ((size_t)T + 1)));      // + the null leaf
-    MR_HIP(hipMalloc(&b->p_keys, sizeof(uint32_t) * T)); MR_HIP(hipMalloc(&b->p_vals, sizeof(uint32_t) * T));
-    MR_HIP(hipMalloc(&b->p_key64, sizeof(unsigned long long) * T));
-    MR_HIP(hipMalloc(&b->p_info, sizeof(int32_t) * 3 * (2 * T))); MR_HIP(hipMalloc(&b->p_aabb, sizeof(float) * 6 * (2 * T)));
-    MR_HIP(hipMalloc(&b->p_range, sizeof(uint32_t) * 2 * T));
-    MR_HIP(hipMalloc(&b->p_parent, sizeof(int32_t) * 2 * T));
-    {   // scratch of the SAH top (k_sah_*): clusters, rebuilt nodes, one level's bins
-        const size_t C = MR_SAH_MAXC;
-        MR_HIP(hipMalloc(&b->sah_state, sizeof(SahState)));
-        MR_HIP(hipMalloc(&b->sah_nodes, sizeof(SahNode) * 2 * C));
-        MR_HIP(hipMalloc(&b->sah_bins, sizeof(SahBin) * C * 3 * MR_SAH_BINS));
-        MR_HIP(hipMalloc(&b->sah_iref, sizeof(int32_t) * C)); MR_HIP(hipMalloc(&b->sah_inode, sizeof(int32_t) * C)); MR_HIP(hipMalloc(&b->sah_top, sizeof(int32_t) * C));
-        std::vector<SahBin> z(C * 3 * MR_SAH_BINS);
-        for (auto& e : z) { e.count = 0; for (int q = 0; q < 3; q++) { e.box[q] = 0xffffffffu; e.box[3 + q] = 0u; } }
-        MR_HIP(hipMemcpy(b->sah_bins, z.data(), sizeof(SahBin) * z.size(), hipMemcpyHostToDevice));      // every split leaves its bins clean again
-    }
-    MR_HIP(hipMalloc(&b->sb_state, 16)); MR_HIP(hipMalloc(&b->sb_cnt, sizeof(uint32_t) * 2 * T)); MR_HIP(hipMalloc(&b->sb_roots, sizeof(int32_t) * (T / 3 + 2)));      // SAH bottom (k_sb_*)
-    MR_HIP(hipMalloc(&b->top85q, sizeof(Node4q) * 85));
-    MR_HIP(hipMalloc(&b->top341q, sizeof(Node4q) * 341));
-    MR_HIP(hipMalloc(&b->root_box, sizeof(float) * 8));
-    MR_HIP(hipMalloc(&b->work, sizeof(uint32_t) * MR_WSETS * MR_WSET));
-    MR_HIP(hipHostMalloc((void**)&b->err, 64, hipHostMallocMapped)); *b->err = 0u;
-    b->sort_tmp_bytes = sizeof(uint32_t) * 256 * ((T + MR_RS_TILE - 1) / MR_RS_TILE + 1);     // (digit, tile) counters of the radix sort + the digit totals
-    MR_HIP(hipMalloc(&b->sort_tmp, b->sort_tmp_bytes));
+    const int rc = bvh_allocate(b);
+    if (rc) { mirres_bvh_destroy(b); return rc; }      // the error text is check_hip's: freeing sets none
     *out = b;
     return MIRRES_OK;
 }
 
 void mirres_bvh_destroy(mirres_bvh_t* b) {
     if (!b) return;
-    void* ptrs[] = {b->ele_aabb, b->extent, b->keys_in, b->keys_out, b->vals_in, b->vals_out, b->parent, b->flags, b->own_info,
-                    b->own_aabb, b->nodes, b->tris, b->root_box, b->sort_tmp, b->work, b->redo[0], b->redo[1], b->dump_pool, b->lvl, b->nodes4q, b->leaves, b->top85q, b->top341q,
-                    b->p_keys, b->p_vals, b->p_key64, b->p_info, b->p_aabb, b->p_range, b->p_parent, b->sah_state, b->sah_nodes, b->sah_bins, b->sah_iref, b->sah_inode, b->sah_top, b->sb_state, b->sb_cnt, b->sb_roots};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : b->owned) (void)hipFree(p);
+    // grown on first use elsewhere (bvh_trace.hip ensure_redo / mirres_debug_wave_times, dump.hip, raster.hip); hipFree(NULL) is a no-op
+    (void)hipFree(b->redo[0]); (void)hipFree(b->redo[1]); (void)hipFree(b->dump_pool); (void)hipFree(b->dbg);
     if (b->err) (void)hipHostFree(b->err);
     delete b;
 }
@@ -1170,21 +1167,11 @@ int mirres_bvh_build_level(mirres_bvh_t* b, const float* vert, int V, const int3
     k_elements<<<(grd < 256 ? grd : 256), blk, 0, s>>>(vert, tri, T, b->ele_aabb, b->extent);
     k_morton<<<grd, blk, 0, s>>>(b->ele_aabb, b->extent, T, b->keys_out, b->vals_out);
     radix_sort_pairs_u32(b->keys_out, b->vals_out, b->keys_in, b->vals_in, (uint32_t*)b->sort_tmp, T, s);
-    k_hierarchy<<<grd, blk, 0, s>>>(T, b->keys_out, b->vals_out, b->ele_aabb, info, aabb, b->parent, b->flags, sorted_codes);
-    {
-        RefitLevels Lv; Lv.n = 1; Lv.a[0] = aabb + 6 * (size_t)(T - 1);
-        int n = T; float* dst = b->lvl;
-        while (n > 64 && Lv.n < 5) {
-            const int nd = (n + 63) >> 6;
-            k_refit_level<<<grid_for(nd, blk), blk, 0, s>>>(n, Lv.a[Lv.n - 1], dst);
-            Lv.a[Lv.n++] = dst; dst += 6 * (size_t)nd; n = nd;
-        }
-        k_refit_ranges<<<grd, blk, 0, s>>>(T, b->flags, Lv, aabb);
-    }
+    k_hierarchy<<<grd, blk, 0, s>>>(T, b->keys_out, b->vals_out, b->ele_aabb, info, aabb, b->flags, sorted_codes);
+    refit_boxes(T, aabb + 6 * (size_t)(T - 1), b->flags, b->lvl, aabb, s);
     k_pack<<<grd, blk, 0, s>>>(T, info, aabb, vert, tri, b->nodes, b->tris, b->root_box);
-    // the 4-wide layout of the shadow-ray / ordered closest-hit kernels: collapsed from the private hierarchy — extended-Morton tree with its upper levels rebuilt by
-    // the binned-SAH top and its lower levels by the sweep-SAH bottom (3, default), without the bottom (MIRRES_PRIVATE_TREE=2), the plain extended-Morton tree (1) — or
-    // (0) from the reference LBVH itself
+    // the private hierarchy: extended-Morton tree with its upper levels rebuilt by the binned-SAH top and its lower levels by the sweep-SAH bottom (3, default),
+    // without the bottom (MIRRES_PRIVATE_TREE=2), the plain extended-Morton tree (1) — or (0) none: the layout is collapsed from the reference LBVH itself
     static const int private_tree_env = [] { const char* e = getenv("MIRRES_PRIVATE_TREE"); return e ? atoi(e) : 3; }();
     int level = private_level >= 0 ? private_level : private_tree_env;
     if (level > 3) level = 3;
@@ -1193,10 +1180,9 @@ int mirres_bvh_build_level(mirres_bvh_t* b, const float* vert, int V, const int3
         int rc = private_step1(b, T, aabb, s); if (rc) return rc;
         if (level >= 2) { rc = private_sah_top(b, T, s); if (rc) return rc; }
         if (level >= 3) { rc = private_sah_bottom(b, T, s); if (rc) return rc; }
-        k_pack4q<true><<<grd, blk, 0, s>>>(T, b->p_info, b->p_aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
-    } else k_pack4q<false><<<grd, blk, 0, s>>>(T, info, aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
+    }
     b->private_level = level;
-    if (T - 1 >= 341 * 4) { k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top85q, 85); k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top341q, 341); }
+    finish_layout(b, vert, tri, info, aabb, s);
     MR_LAUNCH_CHECK("bvh_build");
     return MIRRES_OK;
 }
@@ -1219,12 +1205,10 @@ int mirres_bvh_upgrade(mirres_bvh_t* b, const float* vert, const int32_t* tri, c
     hipStream_t s = (hipStream_t)stream;
     if (!info) info = b->own_info;
     if (!aabb) aabb = b->own_aabb;
-    const int T = b->T, blk = 256, grd = grid_for(T, blk);
-    int rc = private_sah_top(b, T, s); if (rc) return rc;
-    rc = private_sah_bottom(b, T, s); if (rc) return rc;
-    k_pack4q<true><<<grd, blk, 0, s>>>(T, b->p_info, b->p_aabb, info, aabb, vert, tri, b->nodes4q, b->leaves);
-    if (T - 1 >= 341 * 4) { k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top85q, 85); k_top4q<<<1, 256, 0, s>>>(T, b->nodes4q, b->top341q, 341); }
+    int rc = private_sah_top(b, b->T, s); if (rc) return rc;
+    rc = private_sah_bottom(b, b->T, s); if (rc) return rc;
     b->private_level = 3;
+    finish_layout(b, vert, tri, info, aabb, s);
     MR_LAUNCH_CHECK("bvh_upgrade");
     return MIRRES_OK;
 }

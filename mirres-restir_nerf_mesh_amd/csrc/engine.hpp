@@ -102,8 +102,8 @@ struct mirres_bvh {
     float* ele_aabb = nullptr;      // [T,6]
     uint32_t* extent = nullptr;     // [6] order-preserving uint encoding of min xyz / max xyz
     uint32_t *keys_in = nullptr, *keys_out = nullptr, *vals_in = nullptr, *vals_out = nullptr;  // [T] Morton codes / element ids: *_out = k_morton output and, after the sort, the sorted pairs; *_in = the other half of the ping-pong
-    int32_t* parent = nullptr;      // [2T-1]
-    uint32_t* flags = nullptr;      // [2T] (first, last) sorted-leaf range of every internal node (k_hierarchy -> k_refit_ranges)
+    std::vector<void*> owned;       // every device allocation of mirres_bvh_create, in the order made: what mirres_bvh_destroy frees (besides the lazily grown ones below)
+    uint32_t* flags = nullptr;      // [2T] (first, last) sorted-leaf range of every internal node of the reference LBVH (k_hierarchy -> refit_boxes; the private tree's: p_range)
     float* lvl = nullptr;           // 64-ary union pyramid over the sorted leaf boxes (k_refit_level)
     void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;   // radix sort: (digit, tile) counters
     int32_t* own_info = nullptr; float* own_aabb = nullptr;  // used when the caller passes NULL
